@@ -23,6 +23,11 @@ pre-kernel is reported next to it).  The events bracket every 4th step launch of
 hipEventRecord per step drain the queue between the two kernels of a step (+30 us on a 430 us step, measured), which would
 otherwise be charged to the throughput being measured; `roofline.launches` is the number of launches that carried events.  `cpu_baseline` = the CPU restatement in oracle/ ("port": NOT PyBullet, which is not
 installable here) built -O3 -march=native on this box and timed on its host cores on a bounded, pre-rolled sample.
+
+A plain run only sets up, pre-rolls, warms up, times --steps steps and prints the line.  --full adds what the headline does not need
+and that costs time of its own: the `cpu_baseline` leg (native build + ~45 s of CPU runs; --no-cpu-baseline drops it again).
+--dump-outputs DIR writes what the last timed step returned to its caller (obs, reward, done; obs_all when the all-gather runs) as
+DIR/<name>.npy, float32, rank 0; the inputs are seeded, so two builds run with the same arguments can be compared array for array.
 """
 import argparse
 import json
@@ -230,6 +235,26 @@ def pick_threads(probe):
     return best, best_rate
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(outdir, arrays):
+    """arrays: name -> tensor whose first axis is the env.  Written as float32 .npy.  If they exceed DUMP_MAX_BYTES together, every array
+    keeps the same fixed, seeded sample of rows (one sample per row count, indices in sample_rows_<count>.npy as float64): rows keep a
+    third of the budget, and the indices (8 bytes per kept row, no more than twice a row of the narrowest array) fit in the rest."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    host = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_MAX_BYTES:
+        frac = DUMP_MAX_BYTES / (3.0 * total)
+        picks = {r: np.sort(np.random.default_rng(r).choice(r, size=max(1, int(r * frac)), replace=False)) for r in {a.shape[0] for a in host.values()}}
+        host = {k: a[picks[a.shape[0]]] for k, a in host.items()}
+        host.update({"sample_rows_%d" % r: p.astype(np.float64) for r, p in picks.items()})
+    for k, a in host.items():
+        np.save(os.path.join(outdir, k + ".npy"), np.ascontiguousarray(a))
+
+
 def _free_port():
     s = socket.socket(); s.bind(("127.0.0.1", 0)); p = s.getsockname()[1]; s.close(); return p
 
@@ -265,6 +290,8 @@ def main():
     ap.add_argument("--force-collective", action="store_true", help="initialise the process group and run the per-step all-gather / barrier / all-reduce even at world size 1 (exercises the RCCL path of configs[3] on a 1-GPU box)")
     ap.add_argument("--share-device", action="store_true", help="dry run: every rank uses cuda:0 (1-GPU box, gloo backend)")
     ap.add_argument("--dry-run", action="store_true", help="launcher / collective / JSON plumbing only, no env and no GPU (CPU test of the N>1 path)")
+    ap.add_argument("--full", action="store_true", help="also run what the headline does not need: the cpu_baseline leg (unless --no-cpu-baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's outputs (obs, reward, done, obs_all) as DIR/<name>.npy, float32")
     args = ap.parse_args()
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -336,14 +363,20 @@ def main():
     gathered = [torch.empty(world * n, odim, device=dev) for _ in range(2)] if dist is not None and not args.no_allgather else None
     obs_buf = [torch.zeros(n, odim, device=dev) for _ in range(2)]
     pending = [None, None]
+    last = {}                  # what the latest step handed back (--dump-outputs)
 
     def one_step(t):
         k = t & 1
         if pending[k] is not None:
             pending[k].wait(); pending[k] = None
-        obs = env.step(actions[t % pool], obs_out=obs_buf[k] if gathered is not None else None)[0] if env is not None else local_obs
+        if env is not None:
+            obs, last["reward"], last["done"] = env.step(actions[t % pool], obs_out=obs_buf[k] if gathered is not None else None)
+        else:
+            obs = local_obs
+        last["obs"] = obs
         if gathered is not None:
             pending[k] = dist.all_gather_into_tensor(gathered[k], obs, async_op=True)
+            last["obs_all"] = gathered[k]
 
     def drain():
         for k in range(2):
@@ -384,6 +417,8 @@ def main():
         tt = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last)
 
     finite = True
     c_end = mean_iters = 0.0
@@ -443,7 +478,7 @@ def main():
         }
         if args.dry_run:
             out["dry_run"] = True
-        if not args.no_cpu_baseline and world == 1 and not args.dry_run:
+        if args.full and not args.no_cpu_baseline and world == 1 and not args.dry_run:
             try:
                 out["cpu_baseline"] = cpu_baseline_fly(preroll=args.preroll) if fly else cpu_baseline(preroll=args.preroll)
             except Exception as ex:  # pragma: no cover

@@ -1,5 +1,6 @@
 """The committed model header (include/pih_model.h) against the reference's own asset files, parsed by tools/urdf_tables.py.
-Runs only where /root/reference exists (the build container); on the GPU box it is skipped."""
+The asset files (every URDF of the reference and the meshes these tests read, MIT-licensed, see LICENSE there) are stored
+unchanged under tests/golden/model_assets, in the reference's own layout."""
 import os
 import re
 import sys
@@ -8,8 +9,7 @@ import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference"
-pytestmark = pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "peg_in_hole_gym")), reason="reference assets not present")
+REF = os.path.join(ROOT, "tests", "golden", "model_assets")
 
 
 def _macro(name):

@@ -20,8 +20,8 @@ if [ "$PART" = "a" ]; then
   timeout -k 10 1000 python -m pytest tests -m gpu -q -s --durations=12 > $O/gpu_tests_$TAG.log 2>&1; rc=$?
   tail -16 $O/gpu_tests_$TAG.log
   [ $rc -ne 0 ] && { echo "GPU TESTS FAILED rc=$rc"; grep -nE "^(FAILED|ERROR)" $O/gpu_tests_$TAG.log | head; exit 1; }
-  for cfg in "driver_shape:--steps 20 --warmup 5" "default:--no-cpu-baseline" "two_launch:--no-cpu-baseline --schedule 9" "1024:--envs 1024 --no-cpu-baseline" "16384:--envs 16384 --no-cpu-baseline --steps 300" \
-             "scripted:--mode scripted --no-cpu-baseline --steps 300" "exit_check_every_iteration:--no-cpu-baseline --exit-check-stride 1" "fly:--task random-fly"; do
+  for cfg in "driver_shape:--steps 20 --warmup 5 --full" "default:--no-cpu-baseline" "two_launch:--no-cpu-baseline --schedule 9" "1024:--envs 1024 --no-cpu-baseline" "16384:--envs 16384 --no-cpu-baseline --steps 300" \
+             "scripted:--mode scripted --no-cpu-baseline --steps 300" "exit_check_every_iteration:--no-cpu-baseline --exit-check-stride 1" "fly:--task random-fly --full"; do
     name=${cfg%%:*}; args=${cfg#*:}
     timeout -k 10 400 python bench.py $args > $O/bench_${TAG}_$name.json 2> $O/bench_${TAG}_$name.err || { echo "BENCH $name FAILED"; tail -5 $O/bench_${TAG}_$name.err; }
     line $name $O/bench_${TAG}_$name.json

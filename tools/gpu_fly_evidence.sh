@@ -4,7 +4,7 @@
 # usage (GPU box, repo root): bash tools/gpu_fly_evidence.sh <tag>
 TAG=${1:-r03}
 R=${GRAFT_REPO_ROOT:-$(pwd)}; O=$R/gpurun_out; mkdir -p $O; cd $R
-timeout -k 10 300 python bench.py --task random-fly > $O/bench_${TAG}_fly.json 2> $O/bench_${TAG}_fly.err || { echo "FLY BENCH FAILED"; tail -20 $O/bench_${TAG}_fly.err; exit 1; }
+timeout -k 10 300 python bench.py --task random-fly --full > $O/bench_${TAG}_fly.json 2> $O/bench_${TAG}_fly.err || { echo "FLY BENCH FAILED"; tail -20 $O/bench_${TAG}_fly.err; exit 1; }
 cd /tmp && export TMPDIR=/tmp
 rm -rf $O/prof_${TAG}_fly
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_${TAG}_fly -- python $R/bench.py --task random-fly --steps 200 --warmup 20 --no-cpu-baseline > $O/profiled_bench_${TAG}_fly.json 2> $O/profiled_bench_${TAG}_fly.err || { echo "PROFILED FLY BENCH FAILED"; tail -20 $O/profiled_bench_${TAG}_fly.err; exit 1; }

@@ -5,7 +5,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}; O=$R/gpurun_out; mkdir -p $O; cd $R
 timeout -k 10 1000 python -m pytest tests -m gpu -q -s -x --durations=15 > $O/gpu_tests_$TAG.log 2>&1; rc=$?
 tail -25 $O/gpu_tests_$TAG.log
 [ $rc -ne 0 ] && { echo "GPU TESTS FAILED rc=$rc"; grep -nE "^(FAILED|ERROR)|Error|assert" $O/gpu_tests_$TAG.log | head -40; exit 1; }
-timeout -k 10 300 python bench.py --steps 20 --warmup 5 > $O/bench_${TAG}_driver.json 2> $O/bench_${TAG}_driver.err || { echo "BENCH FAILED"; tail -20 $O/bench_${TAG}_driver.err; exit 1; }
+timeout -k 10 300 python bench.py --steps 20 --warmup 5 --full > $O/bench_${TAG}_driver.json 2> $O/bench_${TAG}_driver.err || { echo "BENCH FAILED"; tail -20 $O/bench_${TAG}_driver.err; exit 1; }
 python - <<PY
 import json
 d = json.loads(open("$O/bench_${TAG}_driver.json").read().strip().splitlines()[-1])

@@ -10,11 +10,11 @@ if [ "${2:-tests}" = "tests" ]; then
   timeout -k 10 900 python -m pytest tests -m gpu -q -s > $O/gpu_tests_$TAG.log 2>&1 || { echo "GPU TESTS FAILED"; grep -E "^(FAILED|ERROR)|Error" $O/gpu_tests_$TAG.log | head -40; }
   tail -3 $O/gpu_tests_$TAG.log
 fi
-timeout -k 10 300 python bench.py --steps 20 --warmup 5 > $O/bench_${TAG}_driver.json 2> $O/bench_${TAG}_driver.err || { echo "BENCH FAILED"; tail -20 $O/bench_${TAG}_driver.err; exit 1; }
+timeout -k 10 300 python bench.py --steps 20 --warmup 5 --full > $O/bench_${TAG}_driver.json 2> $O/bench_${TAG}_driver.err || { echo "BENCH FAILED"; tail -20 $O/bench_${TAG}_driver.err; exit 1; }
 timeout -k 10 300 python bench.py --no-cpu-baseline > $O/bench_${TAG}.json 2> $O/bench_${TAG}.err || { echo "BENCH FAILED"; tail -20 $O/bench_${TAG}.err; exit 1; }
 timeout -k 10 300 python bench.py --no-cpu-baseline --schedule 5 > $O/bench_${TAG}_noprio.json 2> $O/bench_${TAG}_noprio.err || echo "NO-PRIORITY BENCH FAILED"
 timeout -k 10 300 python bench.py --no-cpu-baseline --solver-path 1 > $O/bench_${TAG}_dofspace.json 2> $O/bench_${TAG}_dofspace.err || echo "DOF-SPACE BENCH FAILED"
-timeout -k 10 300 python bench.py --task random-fly > $O/bench_${TAG}_fly.json 2> $O/bench_${TAG}_fly.err || { echo "FLY BENCH FAILED"; tail -20 $O/bench_${TAG}_fly.err; exit 1; }
+timeout -k 10 300 python bench.py --task random-fly --full > $O/bench_${TAG}_fly.json 2> $O/bench_${TAG}_fly.err || { echo "FLY BENCH FAILED"; tail -20 $O/bench_${TAG}_fly.err; exit 1; }
 python - <<PY
 import json
 for f in ("bench_${TAG}_driver.json", "bench_${TAG}.json", "bench_${TAG}_noprio.json", "bench_${TAG}_dofspace.json", "bench_${TAG}_fly.json"):
