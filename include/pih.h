@@ -98,15 +98,16 @@ typedef struct pih_config {
   int32_t enable_self_collision;
   int32_t debug;              /* 1: fill the debug buffer each step; roctx ranges "pih_step(...)" / "pih_reset" around the launches (when a roctx library is loadable) */
   int32_t schedule;           /* 1 (default): longest-job-first dispatch order from the previous step's contact counts; 0: block i = env i;
-                                 2: longest-job-first with the lightest envs as SIMD partners of the heaviest (experimental);
                                  +4: do not raise the issue priority of the wavefronts of contact-heavy envs (measurement switch);
-                                 +8 / +16: the two-launch step of rounds 1-3 (controller launch, then physics launch) instead of the fused launch,
-                                 with the controller / IK one env per LANE (+8) or one env per quad of lanes (+16) (measurement switches);
+                                 +8: no fused launch -- peg-in-hole: the two-launch step of rounds 1-3 (pih_pre_kernel: dispatch order +
+                                 controller one env per lane, then the physics launch; the step a hipGraph can capture); random-fly: the IK
+                                 inside the step wavefront;
                                  +32 (random-fly): one env per LANE in the step wavefronts (default: one env per QUAD of lanes, 16 envs per
                                  wavefront, the PGS sweep split over the quad; fused with the IK controller wavefronts while all workgroups
                                  are resident together, n <= 13 104 on 256 CUs); +64 (random-fly): every joint-limit row in every sweep
                                  (default: limit rows of joints farther than 0.25 rad from their limits are skipped and verified -- same
-                                 results bit for bit) (measurement switches) */
+                                 results bit for bit) (measurement switches).
+                                 pih_create rejects every other value (-2), among them the retired 2 / 3 and + 16 */
   int32_t enable_arm_collision; /* arm collision spheres (pih_model.h PIH_ARM_SPH_*): bit 0 vs the table plane, bit 1 vs the pipe (hand /
                                    flange / wrist spheres against the pipe's sample spheres); default 3 */
   int32_t task_id;            /* PIH_TASK_*: which task of TASK_LIST (envs/base_env.py:9-11) the handle simulates */
@@ -159,7 +160,7 @@ int pih_reset(pih_handle* h, const uint8_t* mask_dev, int hard, uint64_t seed, v
 int pih_reseed(pih_handle* h, uint64_t seed);
 /* actions_dev float[n,4]; obs_dev float[n,5]; reward_dev float[n]; done_dev uint8[n]
  * (PIH_TASK_RANDOM_FLY: actions float[n,6], obs float[n,6]).
- * peg-in-hole: ONE kernel launch (controller wavefronts + env wavefronts; pih_config.schedule + 8 / + 16: the two launches of rounds 1-3).
+ * peg-in-hole: ONE kernel launch (controller wavefronts + env wavefronts; pih_config.schedule + 8: the two launches of rounds 1-3).
  * Returns -5 (and keeps returning it) if in an earlier step of this handle an env wavefront timed out waiting for its controller wavefront. */
 int pih_step(pih_handle* h, const float* actions_dev, float* obs_dev, float* reward_dev, uint8_t* done_dev, void* stream);
 /* k consecutive steps with the same action buffer (scripted mode ignores actions: may be NULL) in one call */

@@ -1,4 +1,5 @@
 """Build libpih_hip.so (gfx950) in-tree with hipcc.  Used by __graft_entry__.build() and by developers."""
+import glob
 import os
 import subprocess
 import sys
@@ -6,8 +7,9 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "pih_hip.hip")
 OUT = os.path.join(HERE, "libpih_hip.so")
-DEPS = [SRC, os.path.join(HERE, "pih_device.h"), os.path.join(HERE, "pih_common.h"), os.path.join(HERE, "pih_wave.h"), os.path.join(HERE, "pih_step.h"), os.path.join(HERE, "pih_fly.h"), os.path.join(HERE, "pih_render.h"), os.path.join(HERE, "pih_math.h"),
-        os.path.join(HERE, "..", "..", "include", "pih.h"), os.path.join(HERE, "..", "..", "include", "pih_model.h")]
+DEPS = [SRC] + glob.glob(os.path.join(HERE, "*.h")) + glob.glob(os.path.join(HERE, "..", "..", "include", "*.h"))
+# compiler flags of the device code (tools/isa_fingerprint.py compiles with the same ones)
+FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-value", "-fno-slp-vectorize", "-fno-hip-fp32-correctly-rounded-divide-sqrt", "-ffast-math"]
 
 
 def needs_build():
@@ -21,7 +23,7 @@ def build(force=False, verbose=False):
     if not force and not needs_build():
         return OUT
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    cmd = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-shared", "-fPIC", "-Wno-unused-value", "-fno-slp-vectorize", "-fno-hip-fp32-correctly-rounded-divide-sqrt", "-ffast-math", "-o", OUT, SRC]
+    cmd = [hipcc] + FLAGS + ["-shared", "-o", OUT, SRC]
     if verbose:
         cmd.insert(1, "-Rpass-analysis=kernel-resource-usage")
         print(" ".join(cmd))

@@ -151,12 +151,6 @@ struct InlineIk {      // the step runs the IK itself, one env per lane (the hos
     ik_chain<Ur5Chain>(sw, ikT, P, q, tp, tq, qs);
   }
 };
-struct RecordIk {      // the targets were written into the state record before this launch (pih_fly_pre_kernel; measurement switch)
-  PIH_HD void operator()(const real*, const real* S, const real*, const Params&, real* qs) const {
-#pragma unroll
-    for (int i = 0; i < NJ; i++) qs[i] = S[PIH_F_TARGET + i];
-  }
-};
 
 // "these 24 values are in registers NOW": an empty asm that takes them as read-write register operands, so that the loads that produce
 // them are all issued, and waited for once, before it (GPU); nothing on the host
@@ -187,8 +181,8 @@ struct FlyStamp {
 struct FlyStamp { FlyStamp(real*, bool) {} void operator()(int) {} };
 #endif
 
-// One dt of one env.  S: the env's state record (a per-lane local array); mem: this lane's contact-row scratch; ctl: one of the above
-// (or the mailbox reader of the fused launch, pih_hip.hip).
+// One dt of one env.  S: the env's state record (a per-lane local array); mem: this lane's contact-row scratch; ctl: InlineIk or the
+// mailbox reader of the fused launch (MailboxIk, pih_hip.hip).
 // Q: NoQuad (one env per lane) or the quad primitives (QuadDpp / the host's lockstep threads, pih_ikq.h) of the one-env-per-quad layout.
 template <class Ctl = InlineIk, class Q = NoQuad, class Mem>
 PIH_HD void step_env(real* S, const Params& P, int env_global, const real* action, real* obs, real* reward, unsigned char* done, Mem mem, real* dbg, Ctl ctl = Ctl(), Q quad = Q()) {

@@ -20,16 +20,8 @@ using namespace pih;
 // 3x3 PGS block per iteration), and at 4096 envs there are only two rounds of resident waves, so a heavy env that starts
 // late leaves most of the chip idle at the tail.  This single-workgroup counting sort orders the envs by the contact count
 // of their PREVIOUS step (descending); pih_step_kernel maps blockIdx through it.  Results do not depend on block order.
-// Launch 1 of a step.  Block 0: longest-job-first dispatch order (counting sort of the envs by their previous-step contact
-// count, most contacts first).  Blocks 1..: the controller (action / state machine -> IK -> joint targets), ONE ENV PER QUAD OF LANES
-// (pih_ikq.h: 64 envs per block, 16 per wavefront; rounds 1-3 ran one env per lane: 64 wavefronts walking ~1 000 dependent instructions
-// per IK iteration -- the quad shortens that chain to ~600 on 256 wavefronts).  The two parts touch disjoint state words.
 constexpr int PRE_THREADS = 256;
-// sched_k > 0 (config.schedule = 2): "light seeds".  With n envs on m wave slots and n / m around 2, longest-job-first pairs the
-// heaviest env of the launch with the lightest one in the same slot -- the launch then ends a whole light env after the heaviest one.
-// Here the first wave of m blocks is the m - sched_k heaviest envs plus the sched_k LIGHTEST ones; the slots of those finish early, take
-// a second and a third light env, and the slots of the heaviest envs are never handed a second one.  sched_heads = m - sched_k.
-__device__ __forceinline__ void pre_sort_block(float* __restrict__ state, int* __restrict__ order, int n, int sched_heads, int sched_k) {
+__device__ __forceinline__ void pre_sort_block(float* __restrict__ state, int* __restrict__ order, int n) {
   const int t = threadIdx.x;
   if (!order) return;
   __shared__ int hist[64], base[64];
@@ -46,38 +38,23 @@ __device__ __forceinline__ void pre_sort_block(float* __restrict__ state, int* _
   for (int e = t; e < n; e += PRE_THREADS) {
     int k = (int)state[(size_t)e * PIH_STATE_WORDS + PIH_S_NCONTACT];
     k = k < 0 ? 0 : (k > 63 ? 63 : k);
-    int r = atomicAdd(&base[63 - k], 1);
-    if (sched_k > 0 && n > sched_heads + sched_k && r >= sched_heads) r = r >= n - sched_k ? sched_heads + (n - 1 - r) : r + sched_k;
+    const int r = atomicAdd(&base[63 - k], 1);
     order[r] = e;
   }
 }
 
+// Launch 1 of the two-launch step of rounds 1-3, kept as the reference of the fused launch (pih_config.schedule + 8; the only step a
+// hipGraph can capture).  Block 0: the dispatch order above.  Blocks 1..: the controller (action / state machine -> IK -> joint targets)
+// one env per LANE, 64 envs per block on the block's first wavefront (controller_targets: ik_chain).
 __global__ void __launch_bounds__(PRE_THREADS) pih_pre_kernel(Params P, float* __restrict__ state, const float* __restrict__ actions,
-                                                               int* __restrict__ order, int n, int sched_heads, int sched_k) {
+                                                               int* __restrict__ order, int n) {
   const int t = threadIdx.x;
-  if (blockIdx.x == 0) { pre_sort_block(state, order, n, sched_heads, sched_k); return; }
-  // controller: one env per QUAD of lanes (pih_ikq.h), 64 envs per block = 4 wavefronts of 16 envs
-  const int env = (blockIdx.x - 1) * 64 + (t >> 2);
-  if (env >= n) return;                                   // (uniform per quad: DPP never reads a lane that has left)
-  float* S = state + (size_t)env * PIH_STATE_WORDS;
-  if (!P.autoreset && S[PIH_S_DONE] != 0) return;      // finished envs keep their last values (envs/base_env.py:62,66)
-  float a[4] = {0, 0, 0, 0};
-  if (actions) { a[0] = actions[env * 4]; a[1] = actions[env * 4 + 1]; a[2] = actions[env * 4 + 2]; a[3] = actions[env * 4 + 3]; }
-  QuadDpp qd; qd.l = t & 3;
-  controller_targets_quad(qd, S, P, a);
-}
-
-// The round 1-3 controller launch, kept as a MEASUREMENT SWITCH (pih_config.schedule bit 3): one env per LANE, 64 envs per block on the
-// block's first wavefront (controller_targets: ik_chain, ~1 000 dependent instructions per IK iteration).  A/B partner of pih_pre_kernel.
-__global__ void __launch_bounds__(PRE_THREADS) pih_pre_lane_kernel(Params P, float* __restrict__ state, const float* __restrict__ actions,
-                                                                    int* __restrict__ order, int n, int sched_heads, int sched_k) {
-  const int t = threadIdx.x;
-  if (blockIdx.x == 0) { pre_sort_block(state, order, n, sched_heads, sched_k); return; }
+  if (blockIdx.x == 0) { pre_sort_block(state, order, n); return; }
   if (t >= 64) return;
   const int env = (blockIdx.x - 1) * 64 + t;
   if (env >= n) return;
   float* S = state + (size_t)env * PIH_STATE_WORDS;
-  if (!P.autoreset && S[PIH_S_DONE] != 0) return;
+  if (!P.autoreset && S[PIH_S_DONE] != 0) return;      // finished envs keep their last values (envs/base_env.py:62,66)
   float a[4] = {0, 0, 0, 0};
   if (actions) { a[0] = actions[env * 4]; a[1] = actions[env * 4 + 1]; a[2] = actions[env * 4 + 2]; a[3] = actions[env * 4 + 3]; }
   controller_targets(S, P, a);
@@ -88,8 +65,8 @@ __global__ void __launch_bounds__(PRE_THREADS) pih_pre_lane_kernel(Params P, flo
 // dependent launches, on 64 of the chip's 1 024 SIMDs) and then pih_step_kernel (313 us at 4 096 envs).  Here the step kernel's grid is
 // G = ceil(n / 64) CONTROLLER wavefronts (blocks 0 .. G - 1, dispatched first) followed by the n env wavefronts:
 //   * a controller wavefront runs controller_compute for 64 envs, one per lane, from the envs' state records as the previous launch left
-//     them, writes each env's 13 controller words into its mailbox record and publishes the group with a release store of the launch's
-//     epoch; it never waits for anything;
+//     them, writes each env's 13 controller words into its mailbox record and publishes the group with the launch's epoch
+//     (pih_mailbox.h); it never waits for anything;
 //   * an env wavefront does forward kinematics, collision detection and the articulated-body sweep (~22 us), then waits -- bounded,
 //     s_sleep between polls -- for its group's flag and takes the controller words from the mailbox (Wave::await_controller); the
 //     controller needs ~25 us, so the first round of env waves waits a few us and the second round not at all;
@@ -133,18 +110,10 @@ __global__ void __launch_bounds__(64, 2) pih_step_kernel(Params P, float* __rest
         float* m = F.mail + (size_t)env * CTRL_WORDS;
         const float ov[13] = {o.target[0], o.target[1], o.target[2], o.target[3], o.target[4], o.target[5], o.target[6], o.target[7], o.target[8], o.fsm, o.fsmt, o.grasp_angle, o.attach_qz};
 #pragma unroll
-        for (int i = 0; i < 13; i++) __hip_atomic_store(m + i, ov[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        for (int i = 0; i < 13; i++) mail_store(m + i, ov[i]);
       }
     }
-    // The mailbox stores of all 64 lanes are acknowledged before the group is published: an explicit  s_waitcnt vmcnt(0).  The
-    // workgroup-scope release fence alone compiles to NO wait (the waves of a workgroup share their CU's L1, so the memory model needs none
-    // for that scope), and the flag store then overtook mailbox stores still in flight -- with 640+ workgroups in a random-fly launch a
-    // step wavefront read one stale target word in ~ 1 of 200 groups (tests/test_gpu_fly.py, 12 000 envs); an agent-scope release would
-    // add an L2 write-back (+ 50 us per step, section 6.0 of DESIGN.md) that write-through stores do not need.
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __asm__ volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (lane == 0) __hip_atomic_store(F.flags + blockIdx.x, F.epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // ... before the group is published
+    mailbox_publish(F.flags, F.epoch);
     return;
   }
   __shared__ Shared sh;
@@ -316,45 +285,21 @@ __global__ void pih_gather_kernel(const float* __restrict__ state, float* __rest
 // in the quad layout (four per CU; the kernel needs 450 registers, i.e. one wave per SIMD, anyway).
 // (Round 3, profiles/r03_fly_envs_per_wave.txt: packing FEWER envs into a wave of the lane layout did not shorten the launch, and with 120 KB
 //  of LDS per wave it cost rounds.  The quad layout does not idle the other lanes: it gives them a share of the PGS sweep.)
-// Launch 1 of a random-fly step: the controller ur_execute (envs/utils.py:70-82) -- getQuaternionFromEuler + calculateInverseKinematics --
-// with one env per QUAD of lanes (pih_ikq.h); writes the IK targets into the state record (words PIH_F_TARGET .., structure-of-arrays).
-// 256 threads = 64 envs per block.  (Rounds 2-3 ran the IK inside the one-env-per-lane step kernel, where it was 60 % of the
-// instruction stream of 64 lone wavefronts.)
-__global__ void __launch_bounds__(256) pih_fly_pre_kernel(Params P, float* __restrict__ state, const float* __restrict__ actions, int n) {
-  const int env = blockIdx.x * 64 + (threadIdx.x >> 2);
-  if (env >= n) return;
-  if (!P.autoreset && state[(size_t)PIH_F_DONE * n + env] != 0) return;      // frozen (envs/base_env.py:62,66): targets stay
-  QuadDpp qd; qd.l = threadIdx.x & 3;
-  const int j0 = 2 * qd.l, j1 = j0 + 1;
-  const QuadSlots sl = ikq_slots<Ur5Chain>(qd);
-  float q0 = j0 < fly::NJ ? state[(size_t)(PIH_F_Q + j0) * n + env] : 0.0f, q1 = j1 < fly::NJ ? state[(size_t)(PIH_F_Q + j1) * n + env] : 0.0f;
-  const float* a = actions + (size_t)env * PIH_FLY_ACTION_DIM;
-  const Q4 tq = quat_from_euler(a[3], a[4], a[5]);
-  const V3 tp = mk(a[0] - state[(size_t)PIH_F_OFFSET * n + env], a[1] - state[(size_t)(PIH_F_OFFSET + 1) * n + env], a[2] - state[(size_t)(PIH_F_OFFSET + 2) * n + env]);
-  ikq_solve(qd, sl, P, tp, tq, q0, q1);
-  if (j0 < fly::NJ) state[(size_t)(PIH_F_TARGET + j0) * n + env] = q0;
-  if (j1 < fly::NJ) state[(size_t)(PIH_F_TARGET + j1) * n + env] = q1;
-}
-
+//
 // The fused random-fly launch (round 4, as the peg-in-hole one): the first G = ceil(n / 64) blocks are CONTROLLER wavefronts (the IK of 64
 // envs, one per lane, straight into a mailbox [group][word][lane], then the epoch into the block's flag), the following blocks the step
 // wavefronts (ceil(n / 16) in the quad layout, G in the lane layout), whose lanes read their targets from the mailbox right before the PGS
 // loop -- after forward kinematics, the articulated-body sweeps, collision detection and all response rows.  Every workgroup of the launch
 // carries the step's dynamic LDS, and a step wavefront spins on its controller's flag, so the layout is used only while ALL workgroups are
-// resident at once (pih_create: quad layout 4 per CU, lane layout 1 per CU); bigger batches run the IK inside the step wavefront (MODE 0).
-// MODE 1: targets from a pre-launch (pih_fly_pre_kernel; measurement switch).
+// resident at once (pih_create: quad layout 4 per CU, lane layout 1 per CU); bigger batches run the IK inside the step wavefront
+// (FUSED = false).
 struct FlyFused { int G, epoch; float* mail; int* flags; int* err; };
 struct MailboxIk {
   const int* flag; const float* mail; int* err; int epoch, env, n;
   __device__ __forceinline__ void operator()(const float*, const float*, const float*, const Params&, float* qs) const {
-    int tries = 0;      // (relaxed agent-scope atomics + workgroup fences: see Wave::await_controller)
-    while (__builtin_amdgcn_readfirstlane(__hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) < epoch) {
-      __builtin_amdgcn_s_sleep(4);
-      if (++tries > (1 << 21)) { __hip_atomic_store(err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); break; }
-    }
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    mailbox_await(flag, epoch, err, true);
 #pragma unroll
-    for (int i = 0; i < fly::NJ; i++) qs[i] = __hip_atomic_load(mail + ((size_t)(env >> 6) * fly::NJ + i) * 64 + (env & 63), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    for (int i = 0; i < fly::NJ; i++) qs[i] = mail_load(mail + ((size_t)(env >> 6) * fly::NJ + i) * 64 + (env & 63));
   }
 };
 // QUAD: one env per quad of lanes (pih_fly.h): a step wavefront holds 16 envs, the PGS sweep is split over the quad; the controller
@@ -380,12 +325,12 @@ struct FlyQuad : QuadDpp {
   __device__ __forceinline__ int wave_or(int x) const { return fly_wave_or(x); }
   __device__ __forceinline__ bool wave_any(bool x) const { return __builtin_amdgcn_ballot_w64(x) != 0; }
 };
-template <int MODE, bool QUAD = false>
+template <bool FUSED, bool QUAD>
 __global__ void __launch_bounds__(64, 1) pih_fly_step_kernel(Params P, float* __restrict__ state, const float* __restrict__ actions,
                                                              float* __restrict__ obs, float* __restrict__ reward,
                                                              unsigned char* __restrict__ done, float* __restrict__ dbg, int n, FlyFused F) {
   extern __shared__ float lanemem[];
-  if (MODE == 2 && (int)blockIdx.x < F.G) {
+  if (FUSED && (int)blockIdx.x < F.G) {
     // ---- controller role
     __builtin_amdgcn_s_setprio(3);
     const int env = blockIdx.x * 64 + threadIdx.x;
@@ -399,15 +344,12 @@ __global__ void __launch_bounds__(64, 1) pih_fly_step_kernel(Params P, float* __
       for (int k = 0; k < PIH_FLY_ACTION_DIM; k++) a[k] = actions[(size_t)env * PIH_FLY_ACTION_DIM + k];
       fly::InlineIk()(q, S3, a, P, qs);
 #pragma unroll
-      for (int i = 0; i < fly::NJ; i++) __hip_atomic_store(F.mail + ((size_t)blockIdx.x * fly::NJ + i) * 64 + threadIdx.x, qs[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      for (int i = 0; i < fly::NJ; i++) mail_store(F.mail + ((size_t)blockIdx.x * fly::NJ + i) * 64 + threadIdx.x, qs[i]);
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __asm__ volatile("s_waitcnt vmcnt(0)" ::: "memory");      // (see the peg-in-hole controller role: the stores are acknowledged before the flag)
-    __syncthreads();
-    if (threadIdx.x == 0) __hip_atomic_store(F.flags + blockIdx.x, F.epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    mailbox_publish(F.flags, F.epoch);
     return;
   }
-  const int blk = MODE == 2 ? blockIdx.x - F.G : blockIdx.x;
+  const int blk = FUSED ? blockIdx.x - F.G : blockIdx.x;
   const int env = QUAD ? blk * 16 + (int)(threadIdx.x >> 2) : blk * 64 + (int)threadIdx.x;
   if (env >= n) return;
   const bool writer = !QUAD || (threadIdx.x & 3) == 0;      // (the four lanes of a quad hold identical results)
@@ -427,12 +369,11 @@ __global__ void __launch_bounds__(64, 1) pih_fly_step_kernel(Params P, float* __
   float o[PIH_FLY_OBS_DIM], r; unsigned char d;
   fly::LaneMem mem; mem.p = lanemem + threadIdx.x; mem.stride = 64;
   float* dbge = dbg ? dbg + (size_t)env * PIH_DEBUG_WORDS : nullptr;
-  if constexpr (MODE == 2) {
+  if constexpr (FUSED) {
     MailboxIk mb; mb.flag = F.flags + (env >> 6); mb.mail = F.mail; mb.err = F.err; mb.epoch = F.epoch; mb.env = env; mb.n = n;
     if constexpr (QUAD) { FlyQuad qd; qd.l = threadIdx.x & 3; fly::step_env(S, P, P.env0 + env, a, o, &r, &d, mem, dbge, mb, qd); }
     else fly::step_env(S, P, P.env0 + env, a, o, &r, &d, mem, dbge, mb, FlyLane());
-  } else if constexpr (MODE == 1) fly::step_env(S, P, P.env0 + env, a, o, &r, &d, mem, dbge, fly::RecordIk(), FlyLane());
-  else if constexpr (QUAD) { FlyQuad qd; qd.l = threadIdx.x & 3; fly::step_env(S, P, P.env0 + env, a, o, &r, &d, mem, dbge, fly::InlineIk(), qd); }
+  } else if constexpr (QUAD) { FlyQuad qd; qd.l = threadIdx.x & 3; fly::step_env(S, P, P.env0 + env, a, o, &r, &d, mem, dbge, fly::InlineIk(), qd); }
   else fly::step_env(S, P, P.env0 + env, a, o, &r, &d, mem, dbge, fly::InlineIk(), FlyLane());
   if (writer) {
 #pragma unroll
@@ -515,7 +456,6 @@ struct pih_handle {
   pih_config cfg;
   Params P;
   int device = 0;
-  int sched_k = 0, sched_heads = 0;   // config.schedule = 2: light seeds in the first wave of blocks (see pih_pre_kernel)
   bool fly = false;         // PIH_TASK_RANDOM_FLY: structure-of-arrays state, one env per lane
   bool rewind_pending = false;   // pih_reseed: the envs reset by the next pih_reset restart their draw sequence
   int words = PIH_STATE_WORDS;
@@ -620,6 +560,27 @@ int pih_destroy(pih_handle* h) {
   return 0;
 }
 
+// Fused launch, both tasks (pih_mailbox.h): a zeroed mailbox of `mail_words` floats, one flag per group of 64 envs, and the error word.
+// The error word lives in pinned, device-mapped HOST memory: an env wavefront that gives up waiting stores 1 there (system scope), and the
+// next pih_step / pih_timing2 on the handle sees it without synchronising anything.
+static int mailbox_alloc(pih_handle* h, size_t mail_words) {
+  const size_t G = ((size_t)h->cfg.n_envs + 63) / 64;
+  HIPCHK(h, hipMalloc(&h->mail, mail_words * sizeof(float)));
+  HIPCHK(h, hipMemset(h->mail, 0, mail_words * sizeof(float)));
+  HIPCHK(h, hipMalloc(&h->flags, G * sizeof(int)));
+  HIPCHK(h, hipMemset(h->flags, 0, G * sizeof(int)));
+  HIPCHK(h, hipHostMalloc((void**)&h->errw_host, sizeof(int), hipHostMallocMapped));
+  *h->errw_host = 0;
+  HIPCHK(h, hipHostGetDevicePointer((void**)&h->errw, const_cast<int*>(h->errw_host), 0));
+  return 0;
+}
+// the epoch of the next fused launch, or -5 once an env wavefront of an EARLIER launch of this handle timed out (from then on every step
+// fails loudly)
+static int next_epoch(pih_handle* h) {
+  if (*h->errw_host) { h->err = CTRL_TIMEOUT_MSG; return -5; }
+  return ++h->epoch;
+}
+
 // allocation + first reset; on any failure the caller (pih_create) destroys the half-built handle
 static int create_impl(pih_handle* h, const float* offsets_host, float** offd) {
   const pih_config* cfg = &h->cfg;
@@ -634,32 +595,22 @@ static int create_impl(pih_handle* h, const float* offsets_host, float** offd) {
   if (h->fly) {
     // (dynamic LDS beyond the default 64 KB limit: the per-lane contact rows and candidate staging of 64 envs are LANE_WORDS * 64 words)
     static_assert((size_t)fly::LANE_WORDS * 64 * sizeof(float) <= 160 * 1024, "the random-fly kernel's per-wave LDS exceeds a CU's 160 KB");
-    HIPCHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(pih_fly_step_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(fly::LANE_WORDS * 64 * sizeof(float))));
-    HIPCHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(pih_fly_step_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(fly::LANE_WORDS * 64 * sizeof(float))));
-    HIPCHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(pih_fly_step_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(fly::LANE_WORDS * 64 * sizeof(float))));
-    HIPCHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(pih_fly_step_kernel<2, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(fly::LANE_WORDS_Q * 64 * sizeof(float))));
-    HIPCHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(pih_fly_step_kernel<0, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(fly::LANE_WORDS_Q * 64 * sizeof(float))));
+    HIPCHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(pih_fly_step_kernel<false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(fly::LANE_WORDS * 64 * sizeof(float))));
+    HIPCHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(pih_fly_step_kernel<true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(fly::LANE_WORDS * 64 * sizeof(float))));
+    HIPCHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(pih_fly_step_kernel<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(fly::LANE_WORDS_Q * 64 * sizeof(float))));
+    HIPCHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(pih_fly_step_kernel<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(fly::LANE_WORDS_Q * 64 * sizeof(float))));
     {
       // fused launch (controller wavefronts + step wavefronts in one grid) while both sets of workgroups -- each with the step's 120 KB of
-      // LDS -- fit the chip's CUs at once; schedule + 8: IK inside the step wavefront, + 16: IK as a quad-per-env pre-launch (switches)
+      // LDS -- fit the chip's CUs at once; schedule + 8: IK inside the step wavefront (switch)
       int cus = 0; HIPCHK(h, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device));
       const int G = (cfg->n_envs + 63) / 64;
       // One env per QUAD of lanes in the step wavefronts (38 KB of LDS: four workgroups per CU) unless schedule + 32; its fused launch needs
       // the G controller workgroups and the ceil(n / 16) step workgroups resident together: 4 per CU (n <= 13 104 on 256 CUs); bigger
       // batches run the IK inside the quad's step wavefront.  The lane layout (120 KB per workgroup) fuses while 2 G <= CUs.
-      h->flyquad = (cfg->schedule & (32 | 16)) == 0;
-      const bool nofuse = (cfg->schedule & (8 | 16)) != 0;
-      h->fused = !nofuse && (h->flyquad ? G + (cfg->n_envs + 15) / 16 <= 4 * cus : 2 * G <= cus);
-      if (h->fused) {
-        // mailbox [group][word][64 lanes]: the two 128-byte lines of a (group, word) hold no other group's targets
-        HIPCHK(h, hipMalloc(&h->mail, (size_t)G * 64 * fly::NJ * sizeof(float)));
-        HIPCHK(h, hipMemset(h->mail, 0, (size_t)G * 64 * fly::NJ * sizeof(float)));
-        HIPCHK(h, hipMalloc(&h->flags, (size_t)G * sizeof(int)));
-        HIPCHK(h, hipMemset(h->flags, 0, (size_t)G * sizeof(int)));
-        HIPCHK(h, hipHostMalloc((void**)&h->errw_host, sizeof(int), hipHostMallocMapped));
-        *h->errw_host = 0;
-        HIPCHK(h, hipHostGetDevicePointer((void**)&h->errw, const_cast<int*>(h->errw_host), 0));
-      }
+      h->flyquad = (cfg->schedule & 32) == 0;
+      h->fused = (cfg->schedule & 8) == 0 && (h->flyquad ? G + (cfg->n_envs + 15) / 16 <= 4 * cus : 2 * G <= cus);
+      // mailbox [group][word][64 lanes]: the two 128-byte lines of a (group, word) hold no other group's targets
+      if (h->fused) { int rc = mailbox_alloc(h, (size_t)G * 64 * fly::NJ); if (rc) return rc; }
     }
     const int nb64 = (cfg->n_envs + 63) / 64;
     hipLaunchKernelGGL(pih_fly_init_offsets_kernel, dim3(nb64), dim3(64), 0, 0, h->state, *offd, cfg->n_envs);
@@ -670,33 +621,18 @@ static int create_impl(pih_handle* h, const float* offsets_host, float** offd) {
   }
   HIPCHK(h, hipMalloc(&h->ovf, ((size_t)cfg->n_envs * OVF_WORDS + OVF_PAD_WORDS) * sizeof(float)));
   HIPCHK(h, hipMemset(h->ovf, 0, ((size_t)cfg->n_envs * OVF_WORDS + OVF_PAD_WORDS) * sizeof(float)));
-  if (cfg->schedule & 3) HIPCHK(h, hipMalloc(&h->order, (size_t)cfg->n_envs * sizeof(int)));
-  // fused launch unless a measurement switch asks for the two-launch path (schedule + 8: controller one env per lane, + 16: one env per
-  // quad) or for the experimental partner-aware order (schedule & 3 == 2, which only the pre-kernel's sort implements)
-  h->fused = (cfg->schedule & (8 | 16)) == 0 && (cfg->schedule & 3) != 2;
+  // fused launch unless schedule + 8 asks for the two-launch step; the longest-job-first order (schedule & 1) is built by the env
+  // wavefronts in the bin buffers (fused) or by block 0 of pih_pre_kernel in `order` (two launches)
+  h->fused = (cfg->schedule & 8) == 0;
   if (h->fused) {
-    const int n = cfg->n_envs, G = (n + 63) / 64;
-    HIPCHK(h, hipMalloc(&h->mail, (size_t)n * CTRL_WORDS * sizeof(float)));
-    HIPCHK(h, hipMemset(h->mail, 0, (size_t)n * CTRL_WORDS * sizeof(float)));
-    HIPCHK(h, hipMalloc(&h->flags, (size_t)G * sizeof(int)));
-    HIPCHK(h, hipMemset(h->flags, 0, (size_t)G * sizeof(int)));
-    // the error word lives in pinned, device-mapped HOST memory: an env wavefront that gives up waiting stores 1 there (system scope), and
-    // the next pih_step / pih_timing2 on the handle sees it without synchronising anything
-    HIPCHK(h, hipHostMalloc((void**)&h->errw_host, sizeof(int), hipHostMallocMapped));
-    *h->errw_host = 0;
-    HIPCHK(h, hipHostGetDevicePointer((void**)&h->errw, const_cast<int*>(h->errw_host), 0));
-    if (cfg->schedule & 3) {
-      h->bin_ints = 64 + (size_t)64 * n;
+    int rc = mailbox_alloc(h, (size_t)cfg->n_envs * CTRL_WORDS);
+    if (rc) return rc;
+    if (cfg->schedule & 1) {
+      h->bin_ints = 64 + (size_t)64 * cfg->n_envs;
       HIPCHK(h, hipMalloc(&h->bins, 3 * h->bin_ints * sizeof(int)));
       HIPCHK(h, hipMemset(h->bins, 0, 3 * h->bin_ints * sizeof(int)));
     }
-  }
-  if ((cfg->schedule & 3) == 2) {
-    int cus = 0; HIPCHK(h, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device));
-    const int slots = 8 * cus;                    // two 256-VGPR wavefronts on each of the 4 SIMDs of a CU
-    h->sched_k = slots / 16;                      // (0 < sched_k < slots by construction; pih_pre_kernel ignores it unless n > slots)
-    h->sched_heads = slots - h->sched_k;
-  }
+  } else if (cfg->schedule & 1) HIPCHK(h, hipMalloc(&h->order, (size_t)cfg->n_envs * sizeof(int)));
   hipLaunchKernelGGL(pih_init_offsets_kernel, dim3((cfg->n_envs + 63) / 64), dim3(64), 0, 0, h->state, *offd, cfg->n_envs);
   hipLaunchKernelGGL(pih_reset_kernel, dim3(cfg->n_envs), dim3(64), 0, 0, h->P, h->state, (const unsigned char*)nullptr, 0, 0);
   // the first launch (epoch 1) reads bin buffer 1: every env once, ordered by the contact counts of the reset state
@@ -710,6 +646,11 @@ int pih_create(const pih_config* cfg, const float* offsets_host, pih_handle** ou
   if (!cfg || !out || cfg->n_envs <= 0) { g_err = "pih_create: bad arguments"; return -2; }
   if (cfg->task_id != PIH_TASK_PEG_IN_HOLE && cfg->task_id != PIH_TASK_RANDOM_FLY) { g_err = "pih_create: unknown task_id"; return -2; }
   if (cfg->task_id == PIH_TASK_RANDOM_FLY && (cfg->object_id < 0 || cfg->object_id >= PIH_FLY_NOBJ)) { g_err = "pih_create: unknown object_id for the random-fly task"; return -2; }
+  // the switches of include/pih.h: order 0 / 1 plus the bits 4, 8, 32, 64; every other value selects a retired path or nothing
+  if ((cfg->schedule & 3) >= 2 || (cfg->schedule & ~(3 | 4 | 8 | 32 | 64)) != 0) {
+    g_err = "pih_create: schedule = " + std::to_string(cfg->schedule) + " is not supported (0 or 1, plus any of 4, 8, 32, 64)";
+    return -2;
+  }
   int ndev = 0;
   hipError_t e = hipGetDeviceCount(&ndev);
   if (e != hipSuccess || ndev == 0) { g_err = "pih_create: no HIP device (this library has no CPU path)"; return -3; }
@@ -764,31 +705,26 @@ static int launch_step(pih_handle* h, const float* actions, float* obs, float* r
     t = &h->ev[h->ev_used++];
     HIPCHK(h, hipEventRecord(t->a, s));
   }
-  // measurement switches.  peg-in-hole two-launch path: + 8 = controller one env per lane, + 16 = one env per quad.  random-fly: default =
-  // the fused launch (IK in controller wavefronts of the same grid; batches beyond 8192 envs: IK inside the step wavefront), + 8 = IK
-  // inside the step wavefront, + 16 = the quad-per-env pre-launch
-  const bool lane_ctrl = (h->cfg.schedule & 8) != 0;
+  // random-fly: the fused launch (IK in controller wavefronts of the same grid) while all its workgroups fit the chip at once, else (and
+  // with schedule + 8) the IK inside the step wavefront.  peg-in-hole: the fused launch, or with schedule + 8 the two-launch step.
   if (h->fly) {
     const int G = (h->cfg.n_envs + 63) / 64; const size_t lds = (size_t)fly::LANE_WORDS * 64 * sizeof(float);
     FlyFused FF; memset(&FF, 0, sizeof FF);
     if (h->fused) {
-      if (*h->errw_host) { h->err = CTRL_TIMEOUT_MSG; return -5; }
-      FF.G = G; FF.epoch = ++h->epoch; FF.mail = h->mail; FF.flags = h->flags; FF.err = h->errw;
+      const int e = next_epoch(h);
+      if (e < 0) return e;
+      FF.G = G; FF.epoch = e; FF.mail = h->mail; FF.flags = h->flags; FF.err = h->errw;
       if (t) HIPCHK(h, hipEventRecord(t->b, s));
       if (h->flyquad)
-        hipLaunchKernelGGL((pih_fly_step_kernel<2, true>), dim3(G + (h->cfg.n_envs + 15) / 16), dim3(64), (size_t)fly::LANE_WORDS_Q * 64 * sizeof(float), s, h->P, h->state, actions, obs, reward, done, h->dbg, h->cfg.n_envs, FF);
+        hipLaunchKernelGGL((pih_fly_step_kernel<true, true>), dim3(G + (h->cfg.n_envs + 15) / 16), dim3(64), (size_t)fly::LANE_WORDS_Q * 64 * sizeof(float), s, h->P, h->state, actions, obs, reward, done, h->dbg, h->cfg.n_envs, FF);
       else
-        hipLaunchKernelGGL(pih_fly_step_kernel<2>, dim3(2 * G), dim3(64), lds, s, h->P, h->state, actions, obs, reward, done, h->dbg, h->cfg.n_envs, FF);
-    } else if (h->cfg.schedule & 16) {
-      hipLaunchKernelGGL(pih_fly_pre_kernel, dim3(G), dim3(256), 0, s, h->P, h->state, actions, h->cfg.n_envs);
-      if (t) HIPCHK(h, hipEventRecord(t->b, s));
-      hipLaunchKernelGGL(pih_fly_step_kernel<1>, dim3(G), dim3(64), lds, s, h->P, h->state, actions, obs, reward, done, h->dbg, h->cfg.n_envs, FF);
+        hipLaunchKernelGGL((pih_fly_step_kernel<true, false>), dim3(2 * G), dim3(64), lds, s, h->P, h->state, actions, obs, reward, done, h->dbg, h->cfg.n_envs, FF);
     } else {
       if (t) HIPCHK(h, hipEventRecord(t->b, s));
       if (h->flyquad)
-        hipLaunchKernelGGL((pih_fly_step_kernel<0, true>), dim3((h->cfg.n_envs + 15) / 16), dim3(64), (size_t)fly::LANE_WORDS_Q * 64 * sizeof(float), s, h->P, h->state, actions, obs, reward, done, h->dbg, h->cfg.n_envs, FF);
+        hipLaunchKernelGGL((pih_fly_step_kernel<false, true>), dim3((h->cfg.n_envs + 15) / 16), dim3(64), (size_t)fly::LANE_WORDS_Q * 64 * sizeof(float), s, h->P, h->state, actions, obs, reward, done, h->dbg, h->cfg.n_envs, FF);
       else
-        hipLaunchKernelGGL(pih_fly_step_kernel<0>, dim3(G), dim3(64), lds, s, h->P, h->state, actions, obs, reward, done, h->dbg, h->cfg.n_envs, FF);
+        hipLaunchKernelGGL((pih_fly_step_kernel<false, false>), dim3(G), dim3(64), lds, s, h->P, h->state, actions, obs, reward, done, h->dbg, h->cfg.n_envs, FF);
     }
     if (t) HIPCHK(h, hipEventRecord(t->c, s));
     HIPCHK(h, hipGetLastError());
@@ -796,16 +732,15 @@ static int launch_step(pih_handle* h, const float* actions, float* obs, float* r
   }
   FusedArgs F; memset(&F, 0, sizeof F);
   if (h->fused) {
-    if (*h->errw_host) { h->err = CTRL_TIMEOUT_MSG; return -5; }     // an EARLIER step of this handle timed out: fail loudly from here on
     // one launch: controller wavefronts first, then the env wavefronts
-    const int e = ++h->epoch;
+    const int e = next_epoch(h);
+    if (e < 0) return e;
     F.G = (h->cfg.n_envs + 63) / 64; F.n = h->cfg.n_envs; F.epoch = e; F.mail = h->mail; F.flags = h->flags; F.err = h->errw;
     if (h->bins) { F.bcur = h->bins + (size_t)(e % 3) * h->bin_ints; F.bnext = h->bins + (size_t)((e + 1) % 3) * h->bin_ints; F.bzero = h->bins + (size_t)((e + 2) % 3) * h->bin_ints; }
     if (t) HIPCHK(h, hipEventRecord(t->b, s));
     hipLaunchKernelGGL(pih_step_kernel, dim3(F.G + h->cfg.n_envs), dim3(64), 0, s, h->P, h->state, actions, obs, reward, done, h->dbg, h->ovf, (const int*)nullptr, F);
   } else {
-    if (lane_ctrl) hipLaunchKernelGGL(pih_pre_lane_kernel, dim3(1 + (h->cfg.n_envs + 63) / 64), dim3(PRE_THREADS), 0, s, h->P, h->state, actions, h->order, h->cfg.n_envs, h->sched_heads, h->sched_k);
-    else hipLaunchKernelGGL(pih_pre_kernel, dim3(1 + (h->cfg.n_envs + 63) / 64), dim3(PRE_THREADS), 0, s, h->P, h->state, actions, h->order, h->cfg.n_envs, h->sched_heads, h->sched_k);
+    hipLaunchKernelGGL(pih_pre_kernel, dim3(1 + (h->cfg.n_envs + 63) / 64), dim3(PRE_THREADS), 0, s, h->P, h->state, actions, h->order, h->cfg.n_envs);
     if (t) HIPCHK(h, hipEventRecord(t->b, s));
     hipLaunchKernelGGL(pih_step_kernel, dim3(h->cfg.n_envs), dim3(64), 0, s, h->P, h->state, actions, obs, reward, done, h->dbg, h->ovf, (const int*)h->order, F);
   }

@@ -1,8 +1,8 @@
 // pih_ikq.h -- calculateInverseKinematics (envs/utils.py:67,79; envs/peg_in_hole.py:135-196) with ONE ENV PER QUAD of lanes.
 //
 // Why: the controller is 20 strictly sequential damped-least-squares iterations per env-step.  With one env per LANE (rounds 1-3) a
-// wavefront walks ~1 000 dependent VALU instructions per iteration for 64 envs on ONE SIMD: pih_pre_kernel ran on 64 of the chip's 1 024
-// SIMDs for 35 us of every 370-us step, and the same chain was 60 % of the random-fly step.  A lone wavefront issues one instruction per
+// wavefront walks ~1 000 dependent VALU instructions per iteration for 64 envs on ONE SIMD: the controller launch of rounds 1-3 ran on 64
+// of the chip's 1 024 SIMDs for 35 us of every 370-us step, and the same chain was 60 % of the random-fly step.  A lone wavefront issues one instruction per
 // 4 cycles whatever it is, so only a SHORTER chain helps -- more waves do not.  Here the four lanes of a quad share one env:
 //   * lane l owns transforms 2 l and 2 l + 1 of the chain  [joint 0 .. joint N-1, end-effector frame, (identity)]  -- 8 slots;
 //   * the world frames are an inclusive prefix "product" of rigid transforms over the quad: one local compose + two Hillis-Steele
@@ -196,55 +196,4 @@ template <class Q> PIH_HD void ikq_solve(const Q& qd, const QuadSlots& s, const 
   }
 }
 
-// controller_targets (pih_common.h) with ONE ENV PER QUAD of lanes: the scalar parts (state machine, targets) are replicated in the four
-// lanes, the end-effector pose and the IK run quad-parallel; lane l of the quad writes the targets of joints 2 l and 2 l + 1.  All four
-// lanes of a quad take the same branches (every condition is a function of the env's state record).  `Q`: quad primitives.
-template <class Q> PIH_HD void controller_targets_quad(const Q& qd, real* S, const Params& P, const real* action) {
-  const int l = qd.lane4();
-  const QuadSlots sl = ikq_slots<PandaChain>(qd);
-  real q0 = 2 * l < 7 ? S[PIH_S_QARM + 2 * l] : (real)0, q1 = 2 * l + 1 < 7 ? S[PIH_S_QARM + 2 * l + 1] : (real)0;
-  V3 eep; M3 eeR; ikq_ee(qd, sl, q0, q1, eep, eeR);
-  auto store = [&]() __attribute__((always_inline)) {
-    if (2 * l < 7) S[PIH_S_TARGET + 2 * l] = q0;
-    if (2 * l + 1 < 7) S[PIH_S_TARGET + 2 * l + 1] = q1;
-  };
-  if (P.mode == 0) {
-    V3 tl = mk(action[0] - S[PIH_S_OFFSET], action[1] - S[PIH_S_OFFSET + 1], action[2] - S[PIH_S_OFFSET + 2]);
-    V3 tp = vel_constraint(eep, tl, P.dv);
-    Q4 tq = quat_from_euler(0, -PIH_PI, 0);
-    ikq_solve(qd, sl, P, tp, tq, q0, q1);
-    store();
-    if (l == 3) { S[PIH_S_TARGET + 7] = action[3]; S[PIH_S_TARGET + 8] = action[3]; }
-  } else {
-    int st = (int)S[PIH_S_FSM];
-    int nstep = (int)(S[PIH_S_FSMT] * (real)240 + (real)0.5) + 1;
-    const int st_prev = st;
-    if (nstep >= FSM_STEPS[st]) { st += 1; nstep = 0; if (st >= 10) st = 0; }
-    real tip[7]; tip_pose_serial(S, tip);
-    Q4 tornq; tornq.x = tip[3]; tornq.y = tip[4]; tornq.z = tip[5]; tornq.w = tip[6];
-    V3 rv = mul(q_to_m(tornq), mk(0, S[PIH_S_RANDY], 0));
-    V3 tpos = mk(tip[0], tip[1], tip[2]) + rv;
-    V3 tp = vel_constraint(eep, tpos, P.dv);
-    real yaw = yaw_from_quat(tornq);
-    V3 hole = ld3(HOLE_POS);
-    Q4 tq; tq.x = 0; tq.y = 0; tq.z = 0; tq.w = 1;
-    int do_ik = 0;
-    if (st == 1) { tp.z += (real)0.05; tq = quat_from_euler(0, -PIH_PI, PIH_PI / 2 + yaw); do_ik = 1; }
-    else if (st == 2) { tp.z -= (real)0.01; tq = quat_from_euler(0, -PIH_PI, PIH_PI / 2 + yaw); do_ik = 1; }
-    else if (st == 4) { tp = vel_constraint(eep, hole - mk((real)0.2, 0, 0), P.dv); tq = quat_from_euler(0, -PIH_PI, -PIH_PI); do_ik = 1; }
-    else if (st == 5) { tp = vel_constraint(eep, hole - mk((real)0.04, 0, 0), P.dv); tq = quat_from_euler(0, -PIH_PI, -PIH_PI); do_ik = 1; }
-    else if (st == 6) { tp = hole; tq = quat_from_euler(0, -PIH_PI, -PIH_PI); do_ik = 1; }
-    else if (st == 8) { tp = mk((real)0.2, (real)-0.6, (real)0.4); tq = quat_from_euler(0, -PIH_PI, PIH_PI / 2); do_ik = 1; }
-    if (do_ik) { ikq_solve(qd, sl, P, tp, tq, q0, q1); store(); }
-    // (the state-machine words are written after every read of them above, by one lane: the four lanes of the quad read the same record)
-    if (l == 3) {
-      S[PIH_S_FSM] = (real)st; S[PIH_S_FSMT] = (real)nstep * (real)(1.0 / 240.0);
-      if (st == 2 && st_prev != 2) S[PIH_S_GRASP_ANGLE] = (real)atan2(rv.y, rv.x);
-      if (st == 4 && st_prev != 4) S[PIH_S_ATTACH_QZ] = tip[5];
-      const bool closed = st >= 3 && st < 7;
-      const real ft = closed ? (real)0.006 : (real)0.02;
-      S[PIH_S_TARGET + 7] = ft; S[PIH_S_TARGET + 8] = ft;
-    }
-  }
-}
 }  // namespace pih

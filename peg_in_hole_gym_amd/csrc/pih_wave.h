@@ -6,13 +6,14 @@
 #pragma once
 #include <type_traits>
 #include "pih_common.h"
+#include "pih_mailbox.h"
 
 namespace pih {
 
 struct Wave {
   int l;
   int counter;
-  static constexpr bool controller_inline = false;          // the controller runs in pih_pre_kernel, one env per lane
+  static constexpr bool controller_inline = false;          // the controller runs in its own wavefronts (fused launch) or in pih_pre_kernel
   real* dbg = nullptr; int dbgmode = 0; long long t0 = 0, t1 = 0;   // diagnostic shader-clock stamps (config.debug == 2; never read by the kernel)
   PIH_HD void stamp(int k) { if (dbg && dbgmode == 2) { long long t = __builtin_readcyclecounter(); if (l == 0) dbg[900 + k] = (real)(t - t0); t0 = t; } }   // sub-phases
   // debug words 940..949: start / end of the env's wave on the chip-wide 100 MHz clock (s_memrealtime; three 16-bit pieces each), HW_ID, XCC_ID: the
@@ -36,27 +37,16 @@ struct Wave {
     else __builtin_amdgcn_s_setprio(0);
   }
   // Fused launch (pih_step_kernel with a controller role, round 4): the env's controller output arrives in a 16-word mailbox record,
-  // published by the controller wavefront of the env's group of 64 with a release store of the launch's epoch to the group's flag.
-  // Wave-uniform bounded wait (s_sleep between polls; on time-out the error word is set and the step proceeds with the targets it has --
-  // a launch can never hang on this), then the 13 controller words go into the LDS copy of the state record.  cmail == nullptr:
-  // two-launch path (pih_pre_kernel wrote the record before this kernel started), nothing to do.
+  // published by the controller wavefront of the env's group of 64 (pih_mailbox.h).  After the wait the 13 controller words go into the
+  // LDS copy of the state record.  cmail == nullptr: two-launch path (pih_pre_kernel wrote the record before this kernel started), nothing
+  // to do.
   const int* cflags = nullptr; const real* cmail = nullptr; int* cerr = nullptr; int cepoch = 0, cenv = 0;
   PIH_HD void await_controller(Shared& sh) {
     if (!cmail) return;
-    const int* f = cflags + (cenv >> 6);
-    int tries = 0;
-    // (flag and mailbox words are RELAXED agent-scope atomics: loads and stores that are coherent across the chip's eight L2s by
-    //  themselves.  An agent-scope acquire would invalidate, and a release write back, the whole L2 of the XCD -- measured: + 50 us per
-    //  launch with 4 096 acquires.  Order: the controller completes its mailbox stores (workgroup-scope release fence = wait for the
-    //  stores to be acknowledged) before it stores the flag; this wave reads the mailbox after it has seen the flag.)
-    while (__builtin_amdgcn_readfirstlane(__hip_atomic_load(f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) < cepoch) {
-      __builtin_amdgcn_s_sleep(4);
-      if (++tries > (1 << 21)) { if (l == 0) __hip_atomic_store(cerr, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); break; }   // (host-mapped word: the next pih_step fails with -5)
-    }
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    mailbox_await(cflags + (cenv >> 6), cepoch, cerr, l == 0);
     __syncthreads();
     if (l < 13) {
-      const real v = __hip_atomic_load(cmail + (size_t)cenv * CTRL_WORDS + l, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      const real v = mail_load(cmail + (size_t)cenv * CTRL_WORDS + l);
       const int word = l < 9 ? PIH_S_TARGET + l : (l == 9 ? (int)PIH_S_FSM : l == 10 ? (int)PIH_S_FSMT : l == 11 ? (int)PIH_S_GRASP_ANGLE : (int)PIH_S_ATTACH_QZ);
       sh.S[word] = v;
     }

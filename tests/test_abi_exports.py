@@ -19,6 +19,24 @@ def test_every_declared_symbol_is_exported():
     assert sorted(_lib.EXPORTS) == names
 
 
+def test_create_rejects_retired_schedule_values():
+    """pih_config.schedule values that select a retired path (2, 3: the "light seeds" order; + 16: the quad-per-env controller / IK
+    pre-launch) or none at all (+ 128) fail in pih_create with -2 and a message that names the value.  The check precedes the device
+    check, so it runs without a GPU."""
+    import __graft_entry__ as ge
+    ge.build()
+    from peg_in_hole_gym_amd import _lib
+    L = _lib.load()
+    for sched in (2, 3, 17, 1 + 128):
+        for task in (0, 1):
+            c = _lib.default_config(n_envs=64, schedule=sched, task_id=task)
+            h = ctypes.c_void_p()
+            assert L.pih_create(ctypes.byref(c), None, ctypes.byref(h)) == -2, (sched, task)
+            msg = L.pih_last_error(None).decode()
+            assert "schedule" in msg and str(sched) in msg, msg
+            assert not h.value
+
+
 def test_config_struct_layout_matches_header(tmp_path):
     """Every field of struct pih_config: offset and size as the C compiler lays out include/pih.h == the ctypes mirror in _lib.py
     (a probe compiled with gcc prints offsetof / sizeof for each field name found in the ctypes structure)."""

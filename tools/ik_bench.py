@@ -1,5 +1,5 @@
-"""Time the stand-alone batched IK (pih_ik: one problem per QUAD of lanes) and the controller launch of a step with both layouts
-(pih_config.schedule bit 3 = the round 1-3 one-env-per-lane controller) -- measurement tool for DESIGN section 6.3.
+"""Time the stand-alone batched IK (pih_ik: one problem per QUAD of lanes) and a step fused and with pih_config.schedule bit 3 (peg-in-hole:
+the round 1-3 controller launch, one env per lane; random-fly: the IK inside the step wavefront) -- measurement tool for DESIGN section 6.3.
 usage (GPU box): python tools/ik_bench.py"""
 import os
 import sys
@@ -51,10 +51,10 @@ if __name__ == "__main__":
         print("pih_ik n=%5d: %.1f us (20 iterations), %.1f us (10), %.1f us (0) -> %.2f us per iteration, %.0f cycles at 2.4 GHz" % (n, t20, t10, t0, (t20 - t10) / 10, (t20 - t10) / 10 * 2400))
     for task, name in ((0, "peg-in-hole"), (1, "random-fly")):
         for n in (1024, 4096, 16384):
-            f = time_pre(n, 1, task); q = time_pre(n, 1 + 16, task); l = time_pre(n, 1 + 8, task)
-            print("%s n=%5d: default (ONE fused launch%s) %.1f + %.1f us; controller / IK as a pre-launch, one env per QUAD %.1f + %.1f us; %s %.1f + %.1f us" % (
-                name, n, "; random-fly: step wavefronts one env per quad of lanes, beyond 13 104 envs the IK inside them" if task else "", f[0], f[1], q[0], q[1],
-                "IK inside the step wavefront (quad layout)" if task else "pre-launch, one env per LANE", l[0], l[1]))
+            f = time_pre(n, 1, task); l = time_pre(n, 1 + 8, task)
+            print("%s n=%5d: default (ONE fused launch%s) %.1f + %.1f us; %s %.1f + %.1f us" % (
+                name, n, "; random-fly: step wavefronts one env per quad of lanes, beyond 13 104 envs the IK inside them" if task else "", f[0], f[1],
+                "IK inside the step wavefront (quad layout)" if task else "controller as a pre-launch, one env per LANE", l[0], l[1]))
             if task:
                 a = time_pre(n, 1 + 32, task); b = time_pre(n, 1 + 32 + 8, task)
                 print("%s n=%5d: step wavefronts one env per LANE (schedule + 32): fused (up to 8 192 envs) %.1f + %.1f us; IK inside %.1f + %.1f us" % (name, n, a[0], a[1], b[0], b[1]))
