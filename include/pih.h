@@ -34,6 +34,36 @@ extern "C" {
 #define PIH_OBS_DIM 5         /* envs/peg_in_hole.py:13: finger1, finger2, ee x, y, z */
 #define PIH_DEBUG_WORDS 1024
 
+/* debug buffer word offsets (float32; PIH_FIELD_DEBUG, PIH_DEBUG_WORDS per env, written while config.debug != 0).  The two tasks lay
+ * out the words below 900 differently; the timing words from 900 on (config.debug = 2, GPU only) are common. */
+enum {
+  /* peg-in-hole */
+  PIH_DBG_UDOT = 0,            /* free acceleration per DOF (38) */
+  PIH_DBG_NCONTACT = 38,
+  PIH_DBG_PGS_ITERS = 39,
+  PIH_DBG_CONTACT = 40,        /* + PIH_DBG_CONTACT_STRIDE c: contact c = link a, link b, point (3), normal (3), depth, mu, key, normal multiplier */
+  PIH_DBG_CONTACT_STRIDE = 12,
+  PIH_DBG_CONTACT_KEY = 10,    /* word of a contact record: warm-start key */
+  PIH_DBG_CONTACT_LAMBDA = 11, /* word of a contact record: normal multiplier after the solve */
+  PIH_DBG_DINV = 640,          /* + r: dinv of contact row r (3 rows per contact: n, t1, t2) */
+  /* random-fly */
+  PIH_DBG_FLY_UDOT = 0,        /* free acceleration per DOF (12: 6 joints + the object's twist) */
+  PIH_DBG_FLY_NCONTACT = 12,
+  PIH_DBG_FLY_PGS_ITERS = 13,
+  PIH_DBG_FLY_LIMIT_ROWS = 14, /* 0: no joint-limit row; 1: limit rows of some joint from the start; 2: the solve was repeated with every limit row */
+  PIH_DBG_FLY_CAND = 16,       /* + PIH_DBG_FLY_CAND_STRIDE k: contact candidate k = valid (0 / 1), link, point (3), normal (3), depth, compacted index */
+  PIH_DBG_FLY_CAND_STRIDE = 10,
+  PIH_DBG_FLY_LAMBDA = 200,    /* + c: normal multiplier of compacted contact c */
+  /* both tasks, config.debug = 2 */
+  PIH_DBG_CYCLES = 900,        /* + k: shader-clock cycles of phase k.  peg-in-hole: 0 fk, 1 controller rows, 2 collide, 3 aba, 4 rows, 5 pgs,
+                                  6 integrate, 7 fk2, and the sub-phase stamps 8, 9, 10, 15; random-fly: 0 kinematics + candidates, 1 aba, 2 motor rows,
+                                  3 contact rows, 4 IK targets, 5 pgs, 6 integrate */
+  PIH_DBG_T_START = 940,       /* start of the env's wavefront on the chip-wide 100 MHz clock, as bits 0..15, 16..31, 32..47 (3) */
+  PIH_DBG_T_END = 943,         /* its end, the same way (3).  random-fly writes 940 .. 947 on the wavefront's first env only */
+  PIH_DBG_HW_ID = 946,         /* HW_ID register of the wavefront, low 16 bits */
+  PIH_DBG_XCC_ID = 947
+};
+
 /* state record word offsets (float32) */
 enum {
   PIH_S_QARM = 0, PIH_S_QDARM = 9, PIH_S_POS = 18, PIH_S_QUAT = 21, PIH_S_VLIN = 25, PIH_S_VANG = 28,
@@ -186,8 +216,10 @@ int pih_render_ex(pih_handle* h, float* out_dev, int width, int height, int env_
  * sin(2 angle), cos(2 angle), width in pixels; meta_dev (may be NULL) float[env_count, 5] = x, y, angle [deg], width, length.
  * The reference rasterises with skimage.draw.polygon (absent here: parity unpinned); restated as its even-odd crossing test. */
 int pih_grasp_labels(pih_handle* h, float* out_dev, float* meta_dev, int size, int env_begin, int env_count, void* stream);
-/* kernel timing with HIP events on the launch stream: average ms per step (pre-kernel + step kernel) since the last call with
- * reset=1; pih_timing2 also splits it into the controller/sort launch and the physics launch */
+/* kernel timing with HIP events on the launch stream: average ms per step since the last call with reset=1.  pih_timing2 splits it
+ * at the event recorded right before the step kernel's launch: step_ms is the step kernel; pre_ms is the kernel before it (controller +
+ * dispatch order) in the two-launch peg-in-hole step (schedule + 8), and under the fused launch -- where no such kernel runs and the
+ * controller is part of the step kernel -- only the gap between two event records, close to 0 */
 int pih_timing(pih_handle* h, int reset, double* avg_ms_out, int64_t* launches_out);
 int pih_timing2(pih_handle* h, int reset, double* pre_ms_out, double* step_ms_out, int64_t* launches_out);
 /* enable = 0: off; 1: every step launch is bracketed by events; k > 1: every k-th launch only.  (Three hipEventRecord per step drain

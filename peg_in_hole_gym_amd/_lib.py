@@ -6,17 +6,24 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PIH_LIB_PATH") or os.path.join(_HERE, "csrc", "libpih_hip.so")   # override: A/B of builds on one box
 
-STATE_WORDS = 256
-DEBUG_WORDS = 1024
-ACTION_DIM = 4
-OBS_DIM = 5
+# sizes, fields, tasks and word offsets of include/pih.h, named as there minus "PIH_" (tests/test_abi_exports.py compares all of them with the header)
+ABI_VERSION = 4
+STATE_WORDS, DEBUG_WORDS, ACTION_DIM, OBS_DIM = 256, 1024, 4, 5
+FLY_STATE_WORDS, FLY_ACTION_DIM, FLY_OBS_DIM = 48, 6, 6
 FIELD_STATE, FIELD_TIP_POSE, FIELD_CONTACT_FORCE, FIELD_DEBUG, FIELD_EE_POS = 0, 1, 2, 3, 4
-# state record word offsets (include/pih.h)
+TASK_PEG_IN_HOLE, TASK_RANDOM_FLY = 0, 1
+# state record word offsets (PIH_S_*)
 S_QARM, S_QDARM, S_POS, S_QUAT, S_VLIN, S_VANG, S_QJ, S_QDJ, S_TARGET = 0, 9, 18, 21, 25, 28, 31, 54, 77
 S_FSM, S_FSMT, S_DONE, S_GRASP, S_RANDY, S_RNG_HI, S_RNG, S_STEPS, S_OFFSET = 86, 87, 88, 89, 90, 91, 92, 93, 94
-S_SPARE, S_TIP, S_CFORCE, S_NCONTACT, S_PGS_ITERS, S_INVALID, S_CACHE_N = 97, 98, 105, 106, 107, 112, 128
-TASK_PEG_IN_HOLE, TASK_RANDOM_FLY = 0, 1
-ABI_VERSION = 4
+S_SPARE, S_TIP, S_CFORCE, S_NCONTACT, S_PGS_ITERS, S_EE, S_GRASP_ANGLE, S_INVALID, S_ATTACH_QZ, S_SOLVER = 97, 98, 105, 106, 107, 108, 111, 112, 113, 114
+S_CACHE_N, S_CACHE_KEY, S_CACHE_LAMBDA = 128, 129, 177
+# random-fly record word offsets (PIH_F_*)
+F_Q, F_QD, F_TARGET, F_OPOS, F_OQUAT, F_OVLIN, F_OVANG, F_DONE, F_STEPS, F_RNG, F_RNG_HI, F_OFFSET, F_SPARE, F_INVALID, F_EE, F_CFORCE, F_NCONTACT = \
+    0, 6, 12, 18, 21, 25, 28, 31, 32, 33, 34, 35, 38, 39, 40, 43, 44
+# debug buffer word offsets (PIH_DBG_*; the tables are in include/pih.h and DESIGN.md): peg-in-hole, random-fly, the timing words of both
+DBG_UDOT, DBG_NCONTACT, DBG_PGS_ITERS, DBG_CONTACT, DBG_CONTACT_STRIDE, DBG_CONTACT_KEY, DBG_CONTACT_LAMBDA, DBG_DINV = 0, 38, 39, 40, 12, 10, 11, 640
+DBG_FLY_UDOT, DBG_FLY_NCONTACT, DBG_FLY_PGS_ITERS, DBG_FLY_LIMIT_ROWS, DBG_FLY_CAND, DBG_FLY_CAND_STRIDE, DBG_FLY_LAMBDA = 0, 12, 13, 14, 16, 10, 200
+DBG_CYCLES, DBG_T_START, DBG_T_END, DBG_HW_ID, DBG_XCC_ID = 900, 940, 943, 946, 947
 
 EXPORTS = ["pih_default_config", "pih_abi_version", "pih_task_dims", "pih_object_name", "pih_create", "pih_destroy", "pih_reset", "pih_reseed", "pih_step", "pih_step_n",
            "pih_get_state", "pih_set_state", "pih_ik", "pih_ik_ur5", "pih_render", "pih_render_ex", "pih_grasp_labels", "pih_timing", "pih_timing2", "pih_set_timing", "pih_last_error"]
@@ -80,12 +87,6 @@ def load():
         raise PihError("%s has ABI version %d, this package expects %d: rebuild it" % (LIB_PATH, L.pih_abi_version(), ABI_VERSION))
     _lib = L
     return L
-
-
-FLY_STATE_WORDS, FLY_ACTION_DIM, FLY_OBS_DIM = 48, 6, 6
-# random-fly record word offsets (include/pih.h PIH_F_*)
-F_Q, F_QD, F_TARGET, F_OPOS, F_OQUAT, F_OVLIN, F_OVANG, F_DONE, F_STEPS, F_RNG, F_RNG_HI, F_OFFSET, F_SPARE, F_INVALID, F_EE, F_CFORCE, F_NCONTACT = \
-    0, 6, 12, 18, 21, 25, 28, 31, 32, 33, 34, 35, 38, 39, 40, 43, 44
 
 
 def task_dims(task_id):

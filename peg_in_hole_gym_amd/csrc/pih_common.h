@@ -19,6 +19,7 @@
 // sequential-impulse PGS runs with one lane per DOF; the Jacobian entries are recomputed on the fly from the
 // contact point/direction so only the response rows (W = M^-1 J^T) are staged in LDS.
 #pragma once
+#include <string.h>
 #include "../../include/pih.h"
 #include "../../include/pih_model.h"
 #include "pih_math.h"
@@ -36,6 +37,8 @@ constexpr int WPS = 39;       // LDS row stride of a contact response row: entry
 constexpr int WMS = 31;       // row stride of the staged pipe-motor response rows (29 used)
 constexpr int NMOT = 32;      // 9 arm + 23 pipe joint motors
 constexpr int NLIM = 18;
+static_assert(PIH_DBG_UDOT + ND <= PIH_DBG_NCONTACT && PIH_DBG_CONTACT + PIH_DBG_CONTACT_STRIDE * CMAX <= PIH_DBG_DINV &&
+              PIH_DBG_DINV + 3 * CMAX <= PIH_DBG_CYCLES && PIH_DBG_XCC_ID < PIH_DEBUG_WORDS, "debug words of the peg-in-hole step (include/pih.h PIH_DBG_*) overlap");
 
 PIH_CONST int L_PARENT[NL] = PIH_LINK_PARENT;
 PIH_CONST int L_JTYPE[NL] = PIH_LINK_JTYPE;
@@ -116,6 +119,26 @@ struct Params {
   int checkstride;   // cadence of the PGS early-exit test (pih_config.exit_check_stride): 1 = every iteration (Bullet)
   uint64_t seed;
 };
+
+// The library defaults of pih_config (pih_default_config) and the one mapping pih_config -> Params, host code shared by libpih_hip.so
+// and the test-only host build (tests/emul), so that both run on the same parameters.
+inline void config_defaults(pih_config* c) {
+  memset(c, 0, sizeof *c);
+  c->n_envs = 1; c->env_index0 = 0; c->mode = 0; c->solver_iters = 50; c->ik_iters = 20; c->max_episode_steps = 2227; c->auto_reset = 0;
+  c->enable_self_collision = 1; c->enable_arm_collision = 3; c->task_id = PIH_TASK_PEG_IN_HOLE; c->debug = 0; c->schedule = 1; c->exit_check_stride = 16;
+  c->seed = 0; c->dt = 1.0f / 240.0f; c->residual_threshold = 1e-7f; c->erp = 0.2f; c->warmstart = 0.85f; c->contact_margin = 0.005f;
+  c->linear_slop = 1e-5f; c->ik_damping = 0.5f; c->ik_residual = 1e-4f; c->dv = 2.0f / 240.0f;
+}
+inline Params params_from_config(const pih_config* c) {
+  Params P;
+  P.dt = (real)c->dt; P.resid = (real)c->residual_threshold; P.erp = (real)c->erp; P.warm = (real)c->warmstart; P.margin = (real)c->contact_margin;
+  P.slop = (real)c->linear_slop; P.ikdamp = (real)c->ik_damping; P.ikres = (real)c->ik_residual; P.dv = (real)c->dv;
+  P.iters = c->solver_iters; P.ikiters = c->ik_iters; P.mode = c->mode; P.maxsteps = c->max_episode_steps; P.autoreset = c->auto_reset;
+  P.selfcol = c->enable_self_collision; P.armcol = c->enable_arm_collision; P.debug = c->debug; P.env0 = c->env_index0; P.seed = c->seed;
+  P.pgsmode = c->solver_path; P.attachball = c->attach_ball; P.noprio = (c->schedule & 4) != 0; P.nospec = (c->schedule & 64) != 0;
+  P.checkstride = c->exit_check_stride < 1 ? 1 : c->exit_check_stride; P.object = c->object_id;
+  return P;
+}
 
 // dof index of link L: arm link i -> i ; pipe root (link 9) -> 9..14 (lin xyz, ang xyz) ; pipe link L>=10 -> L+5
 PIH_HD int link_dof(int L) { return L < ANL ? L : (L == ANL ? 9 : L + 5); }

@@ -31,6 +31,8 @@ constexpr int NJ = 6, FND = 12, NS = PIH_FLY_OBJ_MAXSPH;   // object spheres, pa
 constexpr int NA = 5;                                       // arm-vs-table slots: links 1..5 (the shoulder cannot reach the table)
 constexpr int NC = 2 * NS + NA;    // contact slots: sphere s vs its deepest arm capsule, sphere s vs the table, arm link 1 + a vs the table
 constexpr int SW = PIH_FLY_STATE_WORDS;
+static_assert(PIH_DBG_FLY_UDOT + FND <= PIH_DBG_FLY_NCONTACT && PIH_DBG_FLY_CAND + PIH_DBG_FLY_CAND_STRIDE * NC <= PIH_DBG_FLY_LAMBDA &&
+              PIH_DBG_FLY_LAMBDA + NC <= PIH_DBG_CYCLES, "debug words of the random-fly step (include/pih.h PIH_DBG_FLY_*) overlap");
 constexpr int CW = 24;             // words of one contact row record in lane memory
 constexpr int KW = 8;              // words of one contact CANDIDATE of a slot (staged for the rolled row-build loop)
 constexpr int CAND0 = NC * CW;     // candidates follow the (compacted) row records
@@ -168,14 +170,14 @@ static_assert(CW == 24, "PIH_FLY_PIN24 names the 24 words of a contact record");
 #endif
 static_assert(CWQ == 9, "PIH_FLY_PIN9 names the 9 words of a lane's share of a contact record");
 
-// Diagnostic phase stamps (config.debug = 2, GPU only): shader-clock cycles since the previous stamp into debug word 900 + k of the env
+// Diagnostic phase stamps (config.debug = 2, GPU only): shader-clock cycles since the previous stamp into debug word PIH_DBG_CYCLES + k of the env
 // (tools/fly_trace.py): 0 kinematics + inertias + collision candidates, 1 articulated-body sweeps, 2 motor response rows, 3 contact rows,
 // 4 wait for / computation of the IK targets, 5 PGS, 6 integration + outputs.
 #ifndef PIH_PLATFORM_DEFINED
 struct FlyStamp {
   real* dbg; long long t;
   PIH_HD FlyStamp(real* d, bool on) : dbg(on ? d : nullptr), t(0) { if (dbg) t = (long long)__builtin_readcyclecounter(); }
-  PIH_HD void operator()(int k) { if (dbg) { const long long n = (long long)__builtin_readcyclecounter(); dbg[900 + k] = (real)(n - t); t = n; } }
+  PIH_HD void operator()(int k) { if (dbg) { const long long n = (long long)__builtin_readcyclecounter(); dbg[PIH_DBG_CYCLES + k] = (real)(n - t); t = n; } }
 };
 #else
 struct FlyStamp { FlyStamp(real*, bool) {} void operator()(int) {} };
@@ -330,7 +332,7 @@ PIH_HD void step_env(real* S, const Params& P, int env_global, const real* actio
     u[9] = ow.x + dt * udot[9]; u[10] = ow.y + dt * udot[10]; u[11] = ow.z + dt * udot[11];
     if (dbg && P.debug) {
 #pragma unroll
-      for (int i = 0; i < FND; i++) dbg[i] = udot[i];
+      for (int i = 0; i < FND; i++) dbg[PIH_DBG_FLY_UDOT + i] = udot[i];
     }
     stamp(1);
     // ---- unit-impulse responses of the arm from the articulated quantities: generalized impulse g (per joint) plus a linear
@@ -427,11 +429,11 @@ PIH_HD void step_env(real* S, const Params& P, int env_global, const real* actio
         mem.at(b + 12) = no.x; mem.at(b + 13) = no.y; mem.at(b + 14) = no.z; mem.at(b + 15) = rxn.x; mem.at(b + 16) = rxn.y; mem.at(b + 17) = rxn.z;
         mem.at(b + 18) = wo.x; mem.at(b + 19) = wo.y; mem.at(b + 20) = wo.z; mem.at(b + 21) = di; mem.at(b + 22) = (vb - ju) * di; mem.at(b + 23) = 0;
         }
-        if (dbg && P.debug) { real* d = dbg + 16 + 10 * k; d[0] = 1; d[1] = (real)la; d[2] = p.x; d[3] = p.y; d[4] = p.z; d[5] = n.x; d[6] = n.y; d[7] = n.z; d[8] = depth; d[9] = (real)nc; }
+        if (dbg && P.debug) { real* d = dbg + PIH_DBG_FLY_CAND + PIH_DBG_FLY_CAND_STRIDE * k; d[0] = 1; d[1] = (real)la; d[2] = p.x; d[3] = p.y; d[4] = p.z; d[5] = n.x; d[6] = n.y; d[7] = n.z; d[8] = depth; d[9] = (real)nc; }
         nc++;
       } else if (dbg && P.debug) {
-        real* d = dbg + 16 + 10 * k;
-        for (int t = 0; t < 10; t++) d[t] = 0;
+        real* d = dbg + PIH_DBG_FLY_CAND + PIH_DBG_FLY_CAND_STRIDE * k;
+        for (int t = 0; t < PIH_DBG_FLY_CAND_STRIDE; t++) d[t] = 0;
       }
     }
     // Quad layout: the lane's share of the first KR contact records moves from lane memory into registers (zeros beyond the env's last
@@ -661,7 +663,7 @@ PIH_HD void step_env(real* S, const Params& P, int env_global, const real* actio
         it++; conv = one(true);
       }
     }
-    if (dbg && P.debug) dbg[14] = redone ? (real)2 : (real)(limmask0 != 0);      // 1: limit rows of some joint from the start; 2: the solve was repeated with every limit row
+    if (dbg && P.debug) dbg[PIH_DBG_FLY_LIMIT_ROWS] = redone ? (real)2 : (real)(limmask0 != 0);      // 1: limit rows of some joint from the start; 2: the solve was repeated with every limit row
     if constexpr (Q::QUAD) {
 #pragma unroll
       for (int c = 0; c < KR; c++) if (c < nc) mem.at(c * CWQ + 8) = lamr[c];
@@ -673,8 +675,8 @@ PIH_HD void step_env(real* S, const Params& P, int env_global, const real* actio
     real cf = 0;
     for (int c = 0; c < nc; c++) cf += mem.at(c * RW + RW - 1);
     if (dbg && P.debug) {
-      dbg[12] = (real)nc; dbg[13] = (real)it;
-      for (int c = 0; c < nc; c++) dbg[200 + c] = mem.at(c * RW + RW - 1);    // lambda_n of compacted contact c (contact records occupy words 16 .. 16 + 10 NC)
+      dbg[PIH_DBG_FLY_NCONTACT] = (real)nc; dbg[PIH_DBG_FLY_PGS_ITERS] = (real)it;
+      for (int c = 0; c < nc; c++) dbg[PIH_DBG_FLY_LAMBDA + c] = mem.at(c * RW + RW - 1);    // lambda_n of compacted contact c (the candidate records end below it)
     }
     stamp(5);
     // ---- integrate

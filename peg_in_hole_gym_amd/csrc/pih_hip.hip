@@ -21,6 +21,11 @@ using namespace pih;
 // late leaves most of the chip idle at the tail.  This single-workgroup counting sort orders the envs by the contact count
 // of their PREVIOUS step (descending); pih_step_kernel maps blockIdx through it.  Results do not depend on block order.
 constexpr int PRE_THREADS = 256;
+// the dispatch-order bin of an env with `ncontact` contacts in its previous step, of 64: bin 0 = most contacts (63 and more)
+__device__ __forceinline__ int contact_bin(float ncontact) {
+  const int k = (int)ncontact;
+  return 63 - (k < 0 ? 0 : (k > 63 ? 63 : k));
+}
 __device__ __forceinline__ void pre_sort_block(float* __restrict__ state, int* __restrict__ order, int n) {
   const int t = threadIdx.x;
   if (!order) return;
@@ -28,17 +33,13 @@ __device__ __forceinline__ void pre_sort_block(float* __restrict__ state, int* _
   if (t < 64) hist[t] = 0;
   __syncthreads();
   for (int e = t; e < n; e += PRE_THREADS) {
-    int k = (int)state[(size_t)e * PIH_STATE_WORDS + PIH_S_NCONTACT];
-    k = k < 0 ? 0 : (k > 63 ? 63 : k);
-    atomicAdd(&hist[63 - k], 1);          // bin 0 = most contacts
+    atomicAdd(&hist[contact_bin(state[(size_t)e * PIH_STATE_WORDS + PIH_S_NCONTACT])], 1);
   }
   __syncthreads();
   if (t == 0) { int acc = 0; for (int b = 0; b < 64; b++) { base[b] = acc; acc += hist[b]; } }
   __syncthreads();
   for (int e = t; e < n; e += PRE_THREADS) {
-    int k = (int)state[(size_t)e * PIH_STATE_WORDS + PIH_S_NCONTACT];
-    k = k < 0 ? 0 : (k > 63 ? 63 : k);
-    const int r = atomicAdd(&base[63 - k], 1);
+    const int r = atomicAdd(&base[contact_bin(state[(size_t)e * PIH_STATE_WORDS + PIH_S_NCONTACT])], 1);
     order[r] = e;
   }
 }
@@ -135,10 +136,10 @@ __global__ void __launch_bounds__(64, 2) pih_step_kernel(Params P, float* __rest
   if (lane < 5 && obs) obs[env * 5 + lane] = o[0] * (lane == 0) + o[1] * (lane == 1) + o[2] * (lane == 2) + o[3] * (lane == 3) + o[4] * (lane == 4);
   if (lane == 0) {
     if (reward) reward[env] = r; if (done) done[env] = d;
-    if (F.bnext) {                                           // a slot in the next launch's dispatch order: bin 0 = most contacts
-      int k = (int)sh.S[PIH_S_NCONTACT]; k = k < 0 ? 0 : (k > 63 ? 63 : k);
-      const int rnk = atomicAdd(F.bnext + (63 - k), 1);
-      if (rnk < F.n) F.bnext[64 + (size_t)(63 - k) * F.n + rnk] = env;
+    if (F.bnext) {                                           // a slot in the next launch's dispatch order
+      const int bin = contact_bin(sh.S[PIH_S_NCONTACT]);
+      const int rnk = atomicAdd(F.bnext + bin, 1);
+      if (rnk < F.n) F.bnext[64 + (size_t)bin * F.n + rnk] = env;
     }
   }
 }
@@ -146,9 +147,9 @@ __global__ void __launch_bounds__(64, 2) pih_step_kernel(Params P, float* __rest
 // first fill of a bin buffer (pih_create): the same counting sort, from the state records
 __global__ void __launch_bounds__(256) pih_bins_init_kernel(const float* __restrict__ state, int* __restrict__ bins, int n) {
   for (int e = blockIdx.x * 256 + threadIdx.x; e < n; e += gridDim.x * 256) {
-    int k = (int)state[(size_t)e * PIH_STATE_WORDS + PIH_S_NCONTACT]; k = k < 0 ? 0 : (k > 63 ? 63 : k);
-    const int rnk = atomicAdd(bins + (63 - k), 1);
-    bins[64 + (size_t)(63 - k) * n + rnk] = e;
+    const int bin = contact_bin(state[(size_t)e * PIH_STATE_WORDS + PIH_S_NCONTACT]);
+    const int rnk = atomicAdd(bins + bin, 1);
+    bins[64 + (size_t)bin * n + rnk] = e;
   }
 }
 
@@ -353,8 +354,8 @@ __global__ void __launch_bounds__(64, 1) pih_fly_step_kernel(Params P, float* __
   const int env = QUAD ? blk * 16 + (int)(threadIdx.x >> 2) : blk * 64 + (int)threadIdx.x;
   if (env >= n) return;
   const bool writer = !QUAD || (threadIdx.x & 3) == 0;      // (the four lanes of a quad hold identical results)
-  // config.debug = 2: start / end of the wavefront on the chip-wide 100 MHz clock and where it ran (debug words 940 .. 947 of the wave's
-  // first env; tools/fly_trace.py) -- never read by the kernel
+  // config.debug = 2: start / end of the wavefront on the chip-wide 100 MHz clock and where it ran (debug words PIH_DBG_T_START .. of the
+  // wave's first env; tools/fly_trace.py) -- never read by the kernel
   const bool stamp = dbg && P.debug == 2 && threadIdx.x == 0;
   long long ts0 = 0;
   if (stamp) ts0 = (long long)__builtin_amdgcn_s_memrealtime();
@@ -388,9 +389,7 @@ __global__ void __launch_bounds__(64, 1) pih_fly_step_kernel(Params P, float* __
   if (stamp) {
     const long long ts1 = (long long)__builtin_amdgcn_s_memrealtime();
     float* o2 = dbg + (size_t)env * PIH_DEBUG_WORDS;
-    o2[940] = (float)(ts0 & 0xFFFF); o2[941] = (float)((ts0 >> 16) & 0xFFFF); o2[942] = (float)((ts0 >> 32) & 0xFFFF);
-    o2[943] = (float)(ts1 & 0xFFFF); o2[944] = (float)((ts1 >> 16) & 0xFFFF); o2[945] = (float)((ts1 >> 32) & 0xFFFF);
-    o2[946] = (float)(__builtin_amdgcn_s_getreg((15 << 11) | 4) & 0xFFFF); o2[947] = (float)__builtin_amdgcn_s_getreg((3 << 11) | 20);
+    debug_store_time(o2, PIH_DBG_T_START, ts0); debug_store_time(o2, PIH_DBG_T_END, ts1); debug_store_hw_id(o2);
   }
 }
 
@@ -498,17 +497,6 @@ struct DevGuard {
 };
 #define PIH_ENTER(h) DevGuard _guard((h)->device); if (_guard.err != hipSuccess) return fail(h, "select the handle's device", _guard.err)
 
-static Params make_params(const pih_config* c) {
-  Params P;
-  P.dt = c->dt; P.resid = c->residual_threshold; P.erp = c->erp; P.warm = c->warmstart; P.margin = c->contact_margin;
-  P.slop = c->linear_slop; P.ikdamp = c->ik_damping; P.ikres = c->ik_residual; P.dv = c->dv; P.iters = c->solver_iters;
-  P.ikiters = c->ik_iters; P.mode = c->mode; P.maxsteps = c->max_episode_steps; P.autoreset = c->auto_reset;
-  P.selfcol = c->enable_self_collision; P.armcol = c->enable_arm_collision; P.debug = c->debug; P.env0 = c->env_index0; P.seed = c->seed; P.pgsmode = c->solver_path; P.attachball = c->attach_ball; P.noprio = (c->schedule & 4) != 0; P.nospec = (c->schedule & 64) != 0;
-  P.checkstride = c->exit_check_stride < 1 ? 1 : c->exit_check_stride;
-  P.object = c->object_id;
-  return P;
-}
-
 // fold finished event triples into the running sums (called when the pool is full and by pih_timing)
 static int drain_events(pih_handle* h) {
   for (size_t i = 0; i < h->ev_used; i++) {
@@ -524,13 +512,7 @@ static int drain_events(pih_handle* h) {
 
 extern "C" {
 
-void pih_default_config(pih_config* c) {
-  memset(c, 0, sizeof *c);
-  c->n_envs = 1; c->env_index0 = 0; c->mode = 0; c->solver_iters = 50; c->ik_iters = 20; c->max_episode_steps = 2227;
-  c->auto_reset = 0; c->enable_self_collision = 1; c->enable_arm_collision = 3; c->task_id = PIH_TASK_PEG_IN_HOLE; c->debug = 0; c->schedule = 1; c->exit_check_stride = 16; c->seed = 0; c->dt = 1.0f / 240.0f; c->residual_threshold = 1e-7f;
-  c->erp = 0.2f; c->warmstart = 0.85f; c->contact_margin = 0.005f; c->linear_slop = 1e-5f; c->ik_damping = 0.5f; c->ik_residual = 1e-4f;
-  c->dv = 2.0f / 240.0f;
-}
+void pih_default_config(pih_config* c) { config_defaults(c); }
 int pih_abi_version(void) { return PIH_ABI_VERSION; }
 int pih_task_dims(int task_id, int32_t out[3]) {
   if (!out) return -2;
@@ -655,7 +637,7 @@ int pih_create(const pih_config* cfg, const float* offsets_host, pih_handle** ou
   hipError_t e = hipGetDeviceCount(&ndev);
   if (e != hipSuccess || ndev == 0) { g_err = "pih_create: no HIP device (this library has no CPU path)"; return -3; }
   pih_handle* h = new pih_handle;
-  h->cfg = *cfg; h->P = make_params(cfg);
+  h->cfg = *cfg; h->P = params_from_config(cfg);
   h->fly = cfg->task_id == PIH_TASK_RANDOM_FLY; h->words = h->fly ? PIH_FLY_STATE_WORDS : PIH_STATE_WORDS;
   float* offd = nullptr;
   int rc = -1;
@@ -769,15 +751,16 @@ int pih_get_state(pih_handle* h, int field, void* out_dev, void* stream) {
   PIH_ENTER(h);
   hipStream_t s = (hipStream_t)stream;
   const int n = h->cfg.n_envs;
+  if (field == PIH_FIELD_DEBUG) {                              // both tasks: env-major, layout PIH_DBG_* of include/pih.h
+    if (!h->dbg) { h->err = "pih_get_state: debug buffer not enabled (config.debug = 0)"; return -4; }
+    HIPCHK(h, hipMemcpyAsync(out_dev, h->dbg, (size_t)n * PIH_DEBUG_WORDS * sizeof(float), hipMemcpyDeviceToDevice, s)); return 0;
+  }
   if (h->fly) {
     int w0 = 0, nw = 0;
     switch (field) {
       case PIH_FIELD_STATE: w0 = 0; nw = PIH_FLY_STATE_WORDS; break;
       case PIH_FIELD_CONTACT_FORCE: w0 = PIH_F_CFORCE; nw = 1; break;
       case PIH_FIELD_EE_POS: w0 = PIH_F_EE; nw = 3; break;
-      case PIH_FIELD_DEBUG:
-        if (!h->dbg) { h->err = "pih_get_state: debug buffer not enabled (config.debug = 0)"; return -4; }
-        HIPCHK(h, hipMemcpyAsync(out_dev, h->dbg, (size_t)n * PIH_DEBUG_WORDS * sizeof(float), hipMemcpyDeviceToDevice, s)); return 0;
       default: h->err = "pih_get_state: field not available for the random-fly task"; return -2;
     }
     hipLaunchKernelGGL(pih_soa_to_aos_kernel, dim3((n * nw + 255) / 256), dim3(256), 0, s, h->state, (float*)out_dev, n, PIH_FLY_STATE_WORDS, w0, nw);
@@ -789,9 +772,6 @@ int pih_get_state(pih_handle* h, int field, void* out_dev, void* stream) {
     case PIH_FIELD_TIP_POSE: hipLaunchKernelGGL(pih_gather_kernel, dim3((n * 7 + 255) / 256), dim3(256), 0, s, h->state, (float*)out_dev, n, (int)PIH_S_TIP, 7); break;
     case PIH_FIELD_CONTACT_FORCE: hipLaunchKernelGGL(pih_gather_kernel, dim3((n + 255) / 256), dim3(256), 0, s, h->state, (float*)out_dev, n, (int)PIH_S_CFORCE, 1); break;
     case PIH_FIELD_EE_POS: hipLaunchKernelGGL(pih_gather_kernel, dim3((n * 3 + 255) / 256), dim3(256), 0, s, h->state, (float*)out_dev, n, (int)PIH_S_EE, 3); break;
-    case PIH_FIELD_DEBUG:
-      if (!h->dbg) { h->err = "pih_get_state: debug buffer not enabled (config.debug = 0)"; return -4; }
-      HIPCHK(h, hipMemcpyAsync(out_dev, h->dbg, (size_t)n * PIH_DEBUG_WORDS * sizeof(float), hipMemcpyDeviceToDevice, s)); return 0;
     default: h->err = "pih_get_state: unknown field"; return -2;
   }
   HIPCHK(h, hipGetLastError());

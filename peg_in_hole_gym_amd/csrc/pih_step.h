@@ -124,11 +124,11 @@ PIH_HD void step_env(W& w, Shared& sh, const Params& P, const Ovf& ov, int env, 
     w.par(ND, [&](int d) { sh.u[d] += dt * sh.udot[d]; });
     w.phase(3);
     if (dbg && P.debug) {
-      w.par(ND, [&](int d) { dbg[d] = sh.udot[d]; });
+      w.par(ND, [&](int d) { dbg[PIH_DBG_UDOT + d] = sh.udot[d]; });
       w.par(sh.nc, [&](int c) {
-        real* o = dbg + 40 + 12 * c;
+        real* o = dbg + PIH_DBG_CONTACT + PIH_DBG_CONTACT_STRIDE * c;
         o[0] = (real)sh.c_la[c]; o[1] = (real)sh.c_lb[c]; o[2] = sh.c_p[c][0]; o[3] = sh.c_p[c][1]; o[4] = sh.c_p[c][2];
-        o[5] = sh.c_n[c][0]; o[6] = sh.c_n[c][1]; o[7] = sh.c_n[c][2]; o[8] = sh.c_depth[c]; o[9] = sh.c_mu[c]; o[10] = (real)sh.c_key[c];
+        o[5] = sh.c_n[c][0]; o[6] = sh.c_n[c][1]; o[7] = sh.c_n[c][2]; o[8] = sh.c_depth[c]; o[9] = sh.c_mu[c]; o[PIH_DBG_CONTACT_KEY] = (real)sh.c_key[c];
       });
     }
     MotorW mw;
@@ -166,13 +166,13 @@ PIH_HD void step_env(W& w, Shared& sh, const Params& P, const Ovf& ov, int env, 
       S[PIH_S_CACHE_LAMBDA + c] = live ? sh.r_lam[3 * c] : (real)0;
     });
     if (dbg && P.debug) {
-      w.par(sh.nc, [&](int c) { dbg[40 + 12 * c + 11] = sh.r_lam[3 * c]; });
-      w.par(3 * sh.nc, [&](int r) { dbg[640 + r] = crec_of(sh, ov, r / 3)[11 + 4 * (r % 3)]; });
+      w.par(sh.nc, [&](int c) { dbg[PIH_DBG_CONTACT + PIH_DBG_CONTACT_STRIDE * c + PIH_DBG_CONTACT_LAMBDA] = sh.r_lam[3 * c]; });
+      w.par(3 * sh.nc, [&](int r) { dbg[PIH_DBG_DINV + r] = crec_of(sh, ov, r / 3)[11 + 4 * (r % 3)]; });
     }
     S[PIH_S_CACHE_N] = (real)sh.nc;
     S[PIH_S_CFORCE] = cf / dt; S[PIH_S_NCONTACT] = (real)sh.nc; S[PIH_S_PGS_ITERS] = (real)iters;
     S[PIH_S_STEPS] += 1;
-    if (dbg && P.debug) { dbg[38] = (real)sh.nc; dbg[39] = (real)iters; }
+    if (dbg && P.debug) { dbg[PIH_DBG_NCONTACT] = (real)sh.nc; dbg[PIH_DBG_PGS_ITERS] = (real)iters; }
     w.sync();
     w.phase(6);
     fk_all(w, sh);

@@ -10,21 +10,21 @@
 
 namespace pih {
 
+// Debug words PIH_DBG_T_START .. PIH_DBG_XCC_ID (config.debug = 2; tools/sched_trace.py, tools/fly_trace.py): a time of the chip-wide 100 MHz
+// clock (s_memrealtime) as three 16-bit pieces, each exact in fp32, and where the wavefront ran (HW_ID, XCC_ID).  Never read by a kernel.
+PIH_HD void debug_store_time(real* dbg, int at, long long t) { dbg[at] = (real)(t & 0xFFFF); dbg[at + 1] = (real)((t >> 16) & 0xFFFF); dbg[at + 2] = (real)((t >> 32) & 0xFFFF); }
+PIH_HD void debug_store_hw_id(real* dbg) { dbg[PIH_DBG_HW_ID] = (real)(__builtin_amdgcn_s_getreg((15 << 11) | 4) & 0xFFFF); dbg[PIH_DBG_XCC_ID] = (real)__builtin_amdgcn_s_getreg((3 << 11) | 20); }
+
 struct Wave {
   int l;
   int counter;
   static constexpr bool controller_inline = false;          // the controller runs in its own wavefronts (fused launch) or in pih_pre_kernel
   real* dbg = nullptr; int dbgmode = 0; long long t0 = 0, t1 = 0;   // diagnostic shader-clock stamps (config.debug == 2; never read by the kernel)
-  PIH_HD void stamp(int k) { if (dbg && dbgmode == 2) { long long t = __builtin_readcyclecounter(); if (l == 0) dbg[900 + k] = (real)(t - t0); t0 = t; } }   // sub-phases
-  // debug words 940..949: start / end of the env's wave on the chip-wide 100 MHz clock (s_memrealtime; three 16-bit pieces each), HW_ID, XCC_ID: the
-  // launch's dispatch timeline (tools/sched_trace.py)
-  PIH_HD void trace(int at, long long t) {
-    if (l != 0) return;
-    dbg[at] = (real)(t & 0xFFFF); dbg[at + 1] = (real)((t >> 16) & 0xFFFF); dbg[at + 2] = (real)((t >> 32) & 0xFFFF);
-    if (at == 940) { dbg[946] = (real)(__builtin_amdgcn_s_getreg((15 << 11) | 4) & 0xFFFF); dbg[947] = (real)__builtin_amdgcn_s_getreg((3 << 11) | 20); }
-  }
-  PIH_HD void phase_begin() { if (dbg && dbgmode == 2) { t1 = __builtin_readcyclecounter(); trace(940, (long long)__builtin_amdgcn_s_memrealtime()); } }
-  PIH_HD void phase(int k) { if (dbg && dbgmode == 2) { long long t = __builtin_readcyclecounter(); if (l == 0) dbg[900 + k] = (real)(t - t1); t1 = t; if (k == 7) trace(943, (long long)__builtin_amdgcn_s_memrealtime()); } }
+  PIH_HD void stamp(int k) { if (dbg && dbgmode == 2) { long long t = __builtin_readcyclecounter(); if (l == 0) dbg[PIH_DBG_CYCLES + k] = (real)(t - t0); t0 = t; } }   // sub-phases
+  // start / end of the env's wave and where it ran: the launch's dispatch timeline
+  PIH_HD void trace(int at, long long t) { if (l != 0) return; debug_store_time(dbg, at, t); if (at == PIH_DBG_T_START) debug_store_hw_id(dbg); }
+  PIH_HD void phase_begin() { if (dbg && dbgmode == 2) { t1 = __builtin_readcyclecounter(); trace(PIH_DBG_T_START, (long long)__builtin_amdgcn_s_memrealtime()); } }
+  PIH_HD void phase(int k) { if (dbg && dbgmode == 2) { long long t = __builtin_readcyclecounter(); if (l == 0) dbg[PIH_DBG_CYCLES + k] = (real)(t - t1); t1 = t; if (k == 7) trace(PIH_DBG_T_END, (long long)__builtin_amdgcn_s_memrealtime()); } }
   PIH_HD int lane() const { return l; }
   // issue priority of this wavefront among the waves of its SIMD (s_setprio 0..3).  A launch of n envs ends when its heaviest
   // env ends, and that env shares its SIMD with a light one for most of its life: the heavy wave goes first at every issue slot.

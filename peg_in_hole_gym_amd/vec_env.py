@@ -119,9 +119,9 @@ class PihVecEnv:
     # --- checkpoint / resume: everything a handle owns is its per-env state record -- the 98 physical words incl. the
     # RNG draw counters and step counters, the derived outputs, the warm-start contact cache -- plus the base seed; the config rides
     # along so that a checkpoint is only loaded into a handle that simulates the same thing.
-    _CFG_KEYS = ("n_envs", "env_index0", "mode", "task_id", "object_id", "solver_iters", "ik_iters", "max_episode_steps", "auto_reset",
-                 "enable_self_collision", "enable_arm_collision", "solver_path", "attach_ball", "exit_check_stride", "dt", "residual_threshold",
-                 "erp", "warmstart", "contact_margin", "linear_slop", "ik_damping", "ik_residual", "dv")
+    # Every field of pih_config has to agree but these: `schedule` and `debug` do not change results, `seed` is checked on its own,
+    # `reserved_f` is unused.  (A new field is compared unless it is excluded here.)
+    _CFG_KEYS = tuple(f for f, _ in _lib.PihConfig._fields_ if f not in ("schedule", "debug", "seed", "reserved_f"))
 
     def state_dict(self):
         """-> {'state': float32 [n, state_words] (host copy), 'seed': int, 'config': {...}, 'abi_version': int}"""
@@ -212,14 +212,16 @@ class PihVecEnv:
         self.L.pih_set_timing(self.h, int(enable))
 
     def timing(self, reset=True):
-        """(average ms per step = controller/sort launch + physics launch, number of timed steps)"""
+        """(average ms per step = the two numbers of timing2 added, number of timed steps)"""
         ms = C.c_double(0)
         n = C.c_int64(0)
         self._chk(self.L.pih_timing(self.h, int(reset), C.byref(ms), C.byref(n)), "pih_timing")
         return ms.value, n.value
 
     def timing2(self, reset=True):
-        """(average ms of pih_pre_kernel, average ms of pih_step_kernel, number of timed steps), HIP events on the launch stream"""
+        """(average ms before the step kernel, average ms of the step kernel, number of timed steps), HIP events on the launch stream.  The
+        first number is pih_pre_kernel (controller + dispatch order) in the two-launch peg-in-hole step (schedule + 8); under the fused launch
+        the controller wavefronts are part of the step kernel and it is only the gap between two event records, close to 0."""
         a = C.c_double(0); b = C.c_double(0); n = C.c_int64(0)
         self._chk(self.L.pih_timing2(self.h, int(reset), C.byref(a), C.byref(b), C.byref(n)), "pih_timing2")
         return a.value, b.value, n.value

@@ -21,14 +21,8 @@ struct Emul {
   std::vector<real> dbg;     // n * 1024
 };
 
-static Params make_params(const pih_config* c) {
-  Params P;
-  P.dt = (real)c->dt; P.resid = (real)c->residual_threshold; P.erp = (real)c->erp; P.warm = (real)c->warmstart;
-  P.margin = (real)c->contact_margin; P.slop = (real)c->linear_slop; P.ikdamp = (real)c->ik_damping; P.ikres = (real)c->ik_residual;
-  P.dv = (real)c->dv; P.iters = c->solver_iters; P.ikiters = c->ik_iters; P.mode = c->mode; P.maxsteps = c->max_episode_steps;
-  P.autoreset = c->auto_reset; P.selfcol = c->enable_self_collision; P.armcol = c->enable_arm_collision; P.debug = c->debug; P.env0 = c->env_index0; P.seed = c->seed; P.pgsmode = c->solver_path; P.attachball = c->attach_ball; P.noprio = 1; P.nospec = (c->schedule & 64) != 0; P.checkstride = c->exit_check_stride < 1 ? 1 : c->exit_check_stride; P.object = c->object_id;
-  return P;
-}
+// the product's pih_config -> Params mapping; the one difference: the host build has no issue priority to raise
+static Params host_params(const pih_config* c) { Params P = params_from_config(c); P.noprio = 1; return P; }
 
 // ---- quad-per-env IK (pih_ikq.h): the four lanes of a quad are four host threads; every cross-lane primitive is
 // publish -> barrier -> read -> barrier, i.e. the lockstep semantics of a DPP quad_perm read
@@ -49,7 +43,7 @@ struct QuadHost {
 };
 struct FlyQuadHost : QuadHost { static constexpr bool QUAD = true; int wave_max(int x) const { return x; } int wave_or(int x) const { return x; } bool wave_any(bool x) const { return x; } };
 template <class C> static void ikq_host(const pih_config* c, const double* q0, const double* tpos, const double* tquat, double* qout, double* ee_out) {
-  const Params P = make_params(c);
+  const Params P = host_params(c);
   QuadShared sh;
   Q4 tq; tq.x = (real)tquat[0]; tq.y = (real)tquat[1]; tq.z = (real)tquat[2]; tq.w = (real)tquat[3];
   const V3 tp = mk((real)tpos[0], (real)tpos[1], (real)tpos[2]);
@@ -70,12 +64,13 @@ template <class C> static void ikq_host(const pih_config* c, const double* q0, c
 }
 
 extern "C" {
+void emul_default_config(pih_config* c) { config_defaults(c); }     // the library defaults (pih_default_config)
 int emul_real_bytes() { return (int)sizeof(real); }
 int emul_shared_bytes() { return (int)sizeof(Shared); }
 // double-precision overrides of the float config fields (so the f64 build is not limited by float dt etc.)
 void* emul_create(const pih_config* c, const double* offsets, double dt) {
   Emul* e = new Emul;
-  e->P = make_params(c); e->n = c->n_envs;
+  e->P = host_params(c); e->n = c->n_envs;
   if (dt > 0) e->P.dt = (real)dt;
   if (c->mode == 0 && c->dv == 0) e->P.dv = (real)(2.0 / 240.0);
   e->state.assign((size_t)e->n * PIH_STATE_WORDS, 0); e->dbg.assign((size_t)e->n * PIH_DEBUG_WORDS, 0);
@@ -113,7 +108,7 @@ void emul_get_state(void* h, double* out) { Emul* e = (Emul*)h; for (size_t i = 
 void emul_set_state(void* h, const double* in) { Emul* e = (Emul*)h; for (size_t i = 0; i < e->state.size(); i++) e->state[i] = (real)in[i]; }
 void emul_get_debug(void* h, double* out) { Emul* e = (Emul*)h; for (size_t i = 0; i < e->dbg.size(); i++) out[i] = (double)e->dbg[i]; }
 void emul_ik(const pih_config* c, const double* q0, const double* tpos, const double* tquat, double* qout) {
-  Params P = make_params(c); Serial w; real ikT[7][12];
+  Params P = host_params(c); Serial w; real ikT[7][12];
   real q[9], qo[7]; for (int i = 0; i < 9; i++) q[i] = (real)q0[i];
   Q4 tq; tq.x = (real)tquat[0]; tq.y = (real)tquat[1]; tq.z = (real)tquat[2]; tq.w = (real)tquat[3];
   ik_chain<PandaChain>(w, ikT, P, q, mk((real)tpos[0], (real)tpos[1], (real)tpos[2]), tq, qo);
@@ -121,7 +116,7 @@ void emul_ik(const pih_config* c, const double* q0, const double* tpos, const do
   qout[7] = q0[7]; qout[8] = q0[8];
 }
 void emul_ik_ur5(const pih_config* c, const double* q0, const double* tpos, const double* tquat, double* qout) {
-  real ikT[6][12]; Params P = make_params(c); Serial w;
+  real ikT[6][12]; Params P = host_params(c); Serial w;
   real q[6], qo[6]; for (int i = 0; i < 6; i++) q[i] = (real)q0[i];
   Q4 tq; tq.x = (real)tquat[0]; tq.y = (real)tquat[1]; tq.z = (real)tquat[2]; tq.w = (real)tquat[3];
   ik_chain<Ur5Chain>(w, ikT, P, q, mk((real)tpos[0], (real)tpos[1], (real)tpos[2]), tq, qo);
@@ -139,7 +134,7 @@ void emul_ikq_ur5(const pih_config* c, const double* q0, const double* tpos, con
 struct EmulFly { Params P; int n; std::vector<real> state, dbg; };
 void* emul_fly_create(const pih_config* c, const double* offsets, double dt) {
   EmulFly* e = new EmulFly;
-  e->P = make_params(c); e->n = c->n_envs;
+  e->P = host_params(c); e->n = c->n_envs;
   if (dt > 0) e->P.dt = (real)dt;
   e->state.assign((size_t)e->n * PIH_FLY_STATE_WORDS, 0); e->dbg.assign((size_t)e->n * PIH_DEBUG_WORDS, 0);
   for (int i = 0; i < e->n; i++) {

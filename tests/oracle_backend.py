@@ -3,6 +3,7 @@ logic can be tested in this GPU-less container.  Never imported by the product."
 import numpy as np
 
 from oracle import oracle as O
+from peg_in_hole_gym_amd import _lib
 
 
 class OracleBackend:
@@ -23,7 +24,7 @@ class OracleBackend:
         self.o.reseed(seed)
 
     def invalid(self):
-        return self.o.get_state()[:, 39 if self.task_id == 1 else 112] != 0
+        return self.o.get_state()[:, _lib.F_INVALID if self.task_id == 1 else _lib.S_INVALID] != 0
 
     def step(self, actions):
         a = np.asarray(actions, dtype=np.float64).reshape(self.n, self.adim)
@@ -59,7 +60,7 @@ class OracleBackend:
         return self.o.render(width, height, shaded=shaded)
 
     def grasp_labels(self, size=300):
-        ang = self.o.get_state()[:, 111]
+        ang = self.o.get_state()[:, _lib.S_GRASP_ANGLE]
         outs = [O.grasp_labels(a, size) for a in ang]
         return np.stack([x[0] for x in outs]), np.stack([x[1] for x in outs])
 

@@ -5,6 +5,7 @@ sensitivity the GPU will have.  The real parity tests (through the C ABI, on the
 import numpy as np
 import pytest
 
+from peg_in_hole_gym_amd import _lib
 from tests.emul import emul as E
 
 REST = np.array([0, -0.215, -np.pi / 3, -2.57, 0, 2.356, 2.356, 0, 0])
@@ -48,7 +49,7 @@ def test_one_step_equivalence_f64(oracle_mod):
         oo, ro, do = o.step(a); oe, re, de = e.step(a)
         so = o.get_state(); se = e.get_state()
         ud = np.array([o.debug_udot(i) for i in range(N)])
-        assert np.abs(ud - e.get_debug()[:, :38]).max() <= 1e-6 * (1 + np.abs(ud).max())
+        assert np.abs(ud - e.get_debug()[:, _lib.DBG_UDOT:_lib.DBG_UDOT + 38]).max() <= 1e-6 * (1 + np.abs(ud).max())
         # rounding-level agreement (median far below); the bound leaves room for steps with a loaded mu = 10 end-link contact,
         # where pyramid-friction PGS amplifies rounding differences
         assert np.abs(so[:, POS] - se[:, POS]).max() < 1e-6 and np.median(np.abs(so[:, POS] - se[:, POS])) < 1e-12
@@ -203,12 +204,12 @@ def test_many_contacts_spill_rows(oracle_mod, prec):
         dbg = e.get_debug()
         for i in range(N):
             oc = o.debug_contacts(i); k = len(oc)
-            gc = dbg[i, 40:40 + 12 * k].reshape(k, 12)
-            np.testing.assert_array_equal(oc[:, 10], gc[:, 10])
+            gc = dbg[i, _lib.DBG_CONTACT:_lib.DBG_CONTACT + _lib.DBG_CONTACT_STRIDE * k].reshape(k, _lib.DBG_CONTACT_STRIDE)
+            np.testing.assert_array_equal(oc[:, 10], gc[:, _lib.DBG_CONTACT_KEY])
             st = stiff_finger_contact(oc); stiff.append(st)
             if not st:
                 seen[k] += 1
-            lerr.append(np.abs(oc[:, 11] - gc[:, 11]).max() / (1e-3 + np.abs(oc[:, 11]).max()))
+            lerr.append(np.abs(oc[:, 11] - gc[:, _lib.DBG_CONTACT_LAMBDA]).max() / (1e-3 + np.abs(oc[:, 11]).max()))
         perr.append(np.abs(so[:, POS] - se[:, POS]).max(1))
         cf = o.contact_force(); ferr.append(np.abs(se[:, 105] - cf) / (1 + np.abs(cf)))
     perr = np.concatenate(perr); ferr = np.concatenate(ferr); lerr = np.array(lerr); stiff = np.array(stiff)

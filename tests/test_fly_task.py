@@ -6,6 +6,7 @@ import os
 import numpy as np
 import pytest
 
+from peg_in_hole_gym_amd import _lib
 from tests.emul import emul as E
 
 DT = 1.0 / 120.0      # README.md:38 args=['Banana', 1/120.]
@@ -180,7 +181,7 @@ def test_arm_stops_at_the_table(oracle_mod):
             seen += 1
             d = e.get_debug()[0]
             for k in range(10, 15):
-                g = d[16 + 10 * k:16 + 10 * k + 10]
+                g = d[_lib.DBG_FLY_CAND + _lib.DBG_FLY_CAND_STRIDE * k:_lib.DBG_FLY_CAND + _lib.DBG_FLY_CAND_STRIDE * (k + 1)]
                 assert g[0] == c[k, 0]
                 if c[k, 0]:
                     assert g[1] == c[k, 1] == k - 9                                  # slot 2 NS + a holds arm link 1 + a
@@ -231,10 +232,10 @@ def test_arm_object_contact_transfers_momentum(oracle_mod):
         if c[:5, 0].any():
             k = int(np.argmax(c[:5, 0]))
             assert c[k, 1] in (1, 2, 3) and c[k, 9] > 0
-            g = d[16 + 10 * k:16 + 10 * k + 10]
+            g = d[_lib.DBG_FLY_CAND + _lib.DBG_FLY_CAND_STRIDE * k:_lib.DBG_FLY_CAND + _lib.DBG_FLY_CAND_STRIDE * (k + 1)]
             assert g[0] == 1 and g[1] == c[k, 1]
             np.testing.assert_allclose(g[2:9], c[k, 2:9], atol=1e-9)
-            np.testing.assert_allclose(d[200 + int(g[9])], c[k, 9], rtol=1e-6)
+            np.testing.assert_allclose(d[_lib.DBG_FLY_LAMBDA + int(g[9])], c[k, 9], rtol=1e-6)
             st = o.get_state()[0]
             assert st[O.F_OVLIN + 1] > -4.0 + 0.5       # the approach velocity was (partly) removed by the arm
             hit = True
@@ -295,7 +296,7 @@ def test_fly_exit_cadence_host_build_matches_same_cadence_oracle(oracle_mod):
         a = rng.uniform(-1, 1, (n, 6))
         s = B.get_state(); A.set_state(s); e.set_state(s)
         A.step(a); _, _, dn = B.step(a); e.step(a)
-        it = e.get_debug()[:, 13].astype(int)
+        it = e.get_debug()[:, _lib.DBG_FLY_PGS_ITERS].astype(int)
         live = dn == 0
         np.testing.assert_array_equal(it[live], B.pgs_iters()[live])
         assert np.abs(e.get_state()[live][:, :31] - B.get_state()[live][:, :31]).max() < 5e-8      # (the fp64 bound of the one-step test above)
@@ -324,7 +325,7 @@ def test_fly_quad_layout_host_build(oracle_mod, prec):
         sa, sb, so = a.get_state(), b.get_state(), o.get_state()
         np.testing.assert_array_equal(da, db); np.testing.assert_array_equal(ra, rb); np.testing.assert_array_equal(sa[:, 44], sb[:, 44])
         live = (do == 0) & (da == 0)
-        ia, ib = a.get_debug()[:, 13], b.get_debug()[:, 13]
+        ia, ib = a.get_debug()[:, _lib.DBG_FLY_PGS_ITERS], b.get_debug()[:, _lib.DBG_FLY_PGS_ITERS]
         its += int((ia[live] != ib[live]).sum())
         ncs += int(sb[:, 44].sum())
         err_l.append(np.abs(sa[live][:, :31] - sb[live][:, :31]).max(initial=0)); err_o.append(np.abs(so[live][:, :31] - sb[live][:, :31]).max(initial=0))
@@ -354,7 +355,7 @@ def test_fly_quad_layout_more_contacts_than_register_records(oracle_mod):
         sa, sb, so = a.get_state(), b.get_state(), o.get_state()
         np.testing.assert_array_equal(sa[:, 44], sb[:, 44]); np.testing.assert_array_equal(sa[:, 44], so[:, 44])
         big += int((sb[:, 44] > 8).sum())
-        np.testing.assert_array_equal(a.get_debug()[:, 13], b.get_debug()[:, 13])
+        np.testing.assert_array_equal(a.get_debug()[:, _lib.DBG_FLY_PGS_ITERS], b.get_debug()[:, _lib.DBG_FLY_PGS_ITERS])
         assert np.abs(sa[:, :31] - sb[:, :31]).max() < 1e-9 and np.abs(so[:, :31] - sb[:, :31]).max() < 1e-6
         assert np.abs(sa[:, 43] - sb[:, 43]).max() < 1e-6 * (1 + np.abs(sa[:, 43]).max())         # the summed normal force
     assert big >= 30
@@ -383,13 +384,13 @@ def test_fly_limit_rows_speculation_is_exact(oracle_mod):
         o.step(act); a.step(act); _, _, _, bad = b.step_quad(act)
         assert bad == 0
         da, db = a.get_debug(), b.get_debug()
-        np.testing.assert_array_equal(da[:, 14], db[:, 14]); np.testing.assert_array_equal(da[:, 13], db[:, 13])
+        np.testing.assert_array_equal(da[:, _lib.DBG_FLY_LIMIT_ROWS], db[:, _lib.DBG_FLY_LIMIT_ROWS]); np.testing.assert_array_equal(da[:, _lib.DBG_FLY_PGS_ITERS], db[:, _lib.DBG_FLY_PGS_ITERS])
         if t == 0:
-            assert (da[:4, 14] == 1).all() and (da[4:8, 14] == 2).all() and (da[8:, 14] == 0).all()
-        seen |= set(da[:, 14].astype(int).tolist())
+            assert (da[:4, _lib.DBG_FLY_LIMIT_ROWS] == 1).all() and (da[4:8, _lib.DBG_FLY_LIMIT_ROWS] == 2).all() and (da[8:, _lib.DBG_FLY_LIMIT_ROWS] == 0).all()
+        seen |= set(da[:, _lib.DBG_FLY_LIMIT_ROWS].astype(int).tolist())
         sa, sb, so = a.get_state(), b.get_state(), o.get_state()
         assert np.abs(sa[:, :31] - so[:, :31]).max() < 1e-9 * 100 and np.abs(sb[:, :31] - so[:, :31]).max() < 1e-9 * 100     # (velocities up to 100 rad/s)
-        np.testing.assert_array_equal(a.get_debug()[:, 13], o.pgs_iters())
+        np.testing.assert_array_equal(a.get_debug()[:, _lib.DBG_FLY_PGS_ITERS], o.pgs_iters())
         s = so
     assert seen == {0, 1, 2}
     # the limit did hold: no joint beyond its limit by more than the one-step overshoot the ERP removes

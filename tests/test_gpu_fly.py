@@ -4,6 +4,8 @@ per lane, pih_fly.h) through the C ABI against the fp64 oracle on the same seede
 import numpy as np
 import pytest
 
+from peg_in_hole_gym_amd import _lib
+
 pytestmark = pytest.mark.gpu
 DT = 1.0 / 120.0
 
@@ -226,7 +228,7 @@ def test_fly_quad_layout_against_lane_layout(n):
         live = same & (da == 0)
         errs.append((sa[live][:, PV] - sb[live][:, PV]).abs().max(1).values.cpu())
         if kw["debug"]:
-            its += int((a.debug()[live][:, 13] != b.debug()[live][:, 13]).sum())
+            its += int((a.debug()[live][:, _lib.DBG_FLY_PGS_ITERS] != b.debug()[live][:, _lib.DBG_FLY_PGS_ITERS]).sum())
     e = torch.cat(errs).numpy()
     print("   quad vs lane layout n=%d: %d env-steps, %d contacts, %d threshold flips, %d iteration counts differ; one-step pose difference p50 / p99.9 / max %.2e / %.2e / %.2e" % (
         n, len(e), ncs, flips, its, np.percentile(e, 50), np.percentile(e, 99.9), e.max()))
@@ -289,8 +291,8 @@ def test_fly_limit_rows_speculation_is_exact(torch_mod, oracle_mod, sched):
         o.step(act); g.step(torch.tensor(act, dtype=torch.float32))
         d = g.debug().cpu().numpy(); so = o.get_state(); sg = g.state().cpu().numpy().astype(np.float64)
         if t == 0:
-            assert (d[:per, 14] == 1).all() and (d[per:2 * per, 14] == 2).all() and (d[2 * per:, 14] == 0).all(), d[:, 14]
-        assert (d[:, 13] == o.pgs_iters()).mean() > 0.97
+            assert (d[:per, _lib.DBG_FLY_LIMIT_ROWS] == 1).all() and (d[per:2 * per, _lib.DBG_FLY_LIMIT_ROWS] == 2).all() and (d[2 * per:, _lib.DBG_FLY_LIMIT_ROWS] == 0).all(), d[:, _lib.DBG_FLY_LIMIT_ROWS]
+        assert (d[:, _lib.DBG_FLY_PGS_ITERS] == o.pgs_iters()).mean() > 0.97
         assert np.abs(sg[:, :6] - so[:, :6]).max() < 2e-4 and np.abs(sg[:, 6:12] - so[:, 6:12]).max() < 2e-2       # (velocities up to 100 rad/s in float)
         s = so
     assert (s[:, :6] <= np.pi + 0.05).all() and (s[:, :6] >= -np.pi - 0.05).all()
@@ -324,7 +326,7 @@ def test_fly_defaults_exit_test_and_cadence(torch_mod, oracle_mod):
         live = same & (dnB == 0)
         e_all = np.maximum(np.abs(so[:, PW] - sg[:, PW]).max(1), DT * np.abs(so[:, VW] - sg[:, VW]).max(1))
         led.after(B, a, np.where(live, e_all, 0.0))
-        gi = g.debug().cpu().numpy()[:, 13].astype(int)
+        gi = g.debug().cpu().numpy()[:, _lib.DBG_FLY_PGS_ITERS].astype(int)
         dA.append(np.where(live, gi - A.pgs_iters(), 0)); dB.append(np.where(live, gi - B.pgs_iters(), 0)); itB.append(B.pgs_iters().copy())
     dA, dB, itB = map(np.concatenate, (dA, dB, itB))
     led.finish("fly defaults (exit test live, cadence 16) N=%d" % N, p50=2e-6, p99=2e-5, exempt_share=0.02, check_force=False)

@@ -4,6 +4,7 @@ scenarios; chaotic phases are compared one step at a time from a resynchronised 
 import numpy as np
 import pytest
 
+from peg_in_hole_gym_amd import _lib
 from tests import parity_util as P
 
 pytestmark = pytest.mark.gpu
@@ -82,7 +83,7 @@ def test_one_step_parity_resynchronised(torch_mod, oracle_mod):
         so = o.get_state(); sg = g.state().cpu().numpy().astype(np.float64)
         ud = np.array([o.debug_udot(i) for i in range(N)])
         dbg = g.debug().cpu().numpy()
-        assert (np.abs(ud - dbg[:, :38]).max(1) <= 1e-3 * (1 + np.abs(ud).max(1))).all()     # free acceleration, fp32
+        assert (np.abs(ud - dbg[:, _lib.DBG_UDOT:_lib.DBG_UDOT + 38]).max(1) <= 1e-3 * (1 + np.abs(ud).max(1))).all()     # free acceleration, fp32
         np.testing.assert_array_equal(o.ncontacts(), sg[:, 106].astype(int))               # same contact sets
         np.testing.assert_array_equal(dg.cpu().numpy(), do)
         np.testing.assert_allclose(og.cpu().numpy()[:, 2:], oo[:, 2:], atol=1e-4)          # ee position
@@ -157,13 +158,13 @@ def test_spill_path_many_contacts(torch_mod, oracle_mod):
         dbg = g.debug().cpu().numpy().astype(np.float64)
         for e in range(N):
             oc = o.debug_contacts(e); k = len(oc)
-            gc = dbg[e, 40:40 + 12 * k].reshape(k, 12)
-            np.testing.assert_array_equal(oc[:, 10], gc[:, 10])                      # same contact keys, same order
+            gc = dbg[e, _lib.DBG_CONTACT:_lib.DBG_CONTACT + _lib.DBG_CONTACT_STRIDE * k].reshape(k, _lib.DBG_CONTACT_STRIDE)
+            np.testing.assert_array_equal(oc[:, 10], gc[:, _lib.DBG_CONTACT_KEY])                      # same contact keys, same order
             np.testing.assert_array_equal(oc[:, 0:2], gc[:, 0:2])                    # same link pairs
             np.testing.assert_allclose(oc[:, 2:9], gc[:, 2:9], atol=1e-4)            # point, normal, depth (fp32 kinematics of a 1.3 m chain)
             seen[k] += 1
             arm_spilled += int(((oc[20:, 0] < 9) | ((oc[20:, 1] >= 0) & (oc[20:, 1] < 9))).sum())
-            lerr.append(np.abs(oc[:, 11] - gc[:, 11]).max() / (1e-3 + np.abs(oc[:, 11]).max()) if k else 0.0)
+            lerr.append(np.abs(oc[:, 11] - gc[:, _lib.DBG_CONTACT_LAMBDA]).max() / (1e-3 + np.abs(oc[:, 11]).max()) if k else 0.0)
         perr.append(np.abs(so[:, POS] - sg[:, POS]).max(1))
         cf = o.contact_force(); ferr.append(np.abs(sg[:, 105] - cf) / (1 + np.abs(cf)))
         led.after(o, a, perr[-1], ferr[-1])

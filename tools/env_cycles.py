@@ -3,7 +3,9 @@ usage: python tools/env_cycles.py [n_envs]      Not a benchmark (the stamps cost
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
+from peg_in_hole_gym_amd import _lib
 from peg_in_hole_gym_amd.vec_env import PihVecEnv
+CYC = _lib.DBG_CYCLES            # + k: cycles of phase k (0 .. 7; 5 = PGS)
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 4096
 sched = int(sys.argv[2]) if len(sys.argv) > 2 else 1
 for path in (0, 1):
@@ -14,8 +16,8 @@ for path in (0, 1):
         env.step(torch.rand(n, 4, device="cuda", generator=gen) * 2 - 1)
         if t >= 400 and t % 5 == 0:
             d = env.debug()
-            tot.append(d[:, 900:908].sum(1)); pgs.append(d[:, 905]); cnt.append(env.state()[:, 106]); phs.append(d[:, 900:908].clone())
-            i = int(tot[-1].argmax()); smax.append(float(tot[-1][i])); sarg.append(int(cnt[-1][i])); sph.append(d[i, 900:908].tolist())
+            tot.append(d[:, CYC:CYC + 8].sum(1)); pgs.append(d[:, CYC + 5]); cnt.append(env.state()[:, _lib.S_NCONTACT]); phs.append(d[:, CYC:CYC + 8].clone())
+            i = int(tot[-1].argmax()); smax.append(float(tot[-1][i])); sarg.append(int(cnt[-1][i])); sph.append(d[i, CYC:CYC + 8].tolist())
     tot = torch.cat(tot); pgs = torch.cat(pgs); cnt = torch.cat(cnt); phs = torch.cat(phs)
     q = lambda x, p: float(torch.quantile(x.float(), p))
     print("solver_path %d: per-env cycles mean %.0f p50 %.0f p90 %.0f p99 %.0f max %.0f | PGS mean %.0f | mean contacts %.2f | sum/2048 slots %.0f" % (

@@ -1,6 +1,7 @@
 import sys, os
 sys.path.insert(0, os.getcwd())
 import torch
+from peg_in_hole_gym_amd import _lib
 from peg_in_hole_gym_amd.vec_env import PihVecEnv
 n = 1024
 res = {}
@@ -12,7 +13,7 @@ for iters in (25, 50, 100):
         env.step(torch.rand(n, 4, device="cuda", generator=gen) * 2 - 1)
         if t >= 400 and t % 5 == 0:
             d = env.debug(); st = env.state()
-            pg.append(d[:, 905]); cn.append(st[:, 106]); vr.append(st[:, 114])
+            pg.append(d[:, _lib.DBG_CYCLES + 5]); cn.append(st[:, _lib.S_NCONTACT]); vr.append(st[:, _lib.S_SOLVER])
     pg = torch.cat(pg); cn = torch.cat(cn); vr = torch.cat(vr)
     for v in (1, 2, 5):
         for lo, hi in ((0, 4), (5, 7), (8, 10), (11, 14), (15, 19), (20, 32)):

@@ -3,6 +3,7 @@ wavefront started and ended (shader clock), on which XCD / CU / SIMD.  usage: py
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
+from peg_in_hole_gym_amd import _lib
 from peg_in_hole_gym_amd.vec_env import PihVecEnv
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 4096
 sched = int(sys.argv[2]) if len(sys.argv) > 2 else 1
@@ -12,16 +13,15 @@ for t in range(420):
     env.step(torch.rand(n, 4, device="cuda", generator=gen) * 2 - 1)
 dump = {}
 for rep in range(3):
-    prev_cnt = env.state()[:, 106].cpu().clone(); prev_var = env.state()[:, 114].cpu().clone()
+    prev_cnt = env.state()[:, _lib.S_NCONTACT].cpu().clone(); prev_var = env.state()[:, _lib.S_SOLVER].cpu().clone()
     env.step(torch.rand(n, 4, device="cuda", generator=gen) * 2 - 1)
     d = env.debug().double().cpu()
-    cnt = env.state()[:, 106].cpu()
-    t0 = d[:, 940] + d[:, 941] * 65536 + d[:, 942] * 65536 ** 2
-    t1 = d[:, 943] + d[:, 944] * 65536 + d[:, 945] * 65536 ** 2
-    hw = d[:, 946].long(); xcc = d[:, 947].long()
+    cnt = env.state()[:, _lib.S_NCONTACT].cpu()
+    t0, t1 = (d[:, w] + d[:, w + 1] * 65536 + d[:, w + 2] * 65536 ** 2 for w in (_lib.DBG_T_START, _lib.DBG_T_END))
+    hw = d[:, _lib.DBG_HW_ID].long(); xcc = d[:, _lib.DBG_XCC_ID].long()
     simd = (hw >> 4) & 3; cu = (hw >> 8) & 15; sh = (hw >> 12) & 1; se = (hw >> 13) & 7
     base = t0.min(); t0 = (t0 - base) * 0.01; t1 = (t1 - base) * 0.01       # 100 MHz ticks -> microseconds
-    dump["dur%d" % rep] = (t1 - t0).numpy(); dump["cnt%d" % rep] = cnt.numpy(); dump["prev_cnt%d" % rep] = prev_cnt.numpy(); dump["prev_var%d" % rep] = prev_var.numpy(); dump["var%d" % rep] = env.state()[:, 114].cpu().numpy()
+    dump["dur%d" % rep] = (t1 - t0).numpy(); dump["cnt%d" % rep] = cnt.numpy(); dump["prev_cnt%d" % rep] = prev_cnt.numpy(); dump["prev_var%d" % rep] = prev_var.numpy(); dump["var%d" % rep] = env.state()[:, _lib.S_SOLVER].cpu().numpy()
     dump["t0_%d" % rep] = t0.numpy(); dump["t1_%d" % rep] = t1.numpy()
     span = float(t1.max()); dur = t1 - t0
     print("launch %d: span %.1f us; sum of wave durations / span = %.0f waves in flight on average (2048 slots); env durations mean %.0f max %.0f" % (

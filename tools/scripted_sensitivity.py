@@ -5,6 +5,7 @@ with reward = 1 at the end of the episode.  A large swing marks the constant as 
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
+from peg_in_hole_gym_amd import _lib
 from peg_in_hole_gym_amd.vec_env import PihVecEnv
 
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 4096
@@ -16,8 +17,8 @@ def run(**kw):
     for k in range(7):
         obs, rew, done = env.step_n(318)
     st = env.state()
-    q = st[:, 0:7]
-    return float(rew.mean()), int(st[:, 112].sum())
+    q = st[:, _lib.S_QARM:_lib.S_QARM + 7]
+    return float(rew.mean()), int(st[:, _lib.S_INVALID].sum())
 
 
 base = run()

@@ -3,6 +3,7 @@ episode, 6-row weld (default) vs the round-1 ball joint.  usage: python tools/sc
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
+from peg_in_hole_gym_amd import _lib
 from peg_in_hole_gym_amd.vec_env import PihVecEnv
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 4096
 for ball in (0, 1):
@@ -13,4 +14,4 @@ for ball in (0, 1):
         best = torch.maximum(best, rew)
     st = env.state()
     print("attach_ball %d: %d envs, reward = 1 at the end of the episode: %.3f ; at any of the 7 sampled instants: %.3f ; finite %s ; invalid %d" % (
-        ball, n, float(rew.mean()), float(best.mean()), bool(torch.isfinite(st[:, :98]).all()), int(st[:, 112].sum())))
+        ball, n, float(rew.mean()), float(best.mean()), bool(torch.isfinite(st[:, :98]).all()), int(st[:, _lib.S_INVALID].sum())))

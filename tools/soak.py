@@ -4,6 +4,7 @@ same seed; reports non-finite resets, contact statistics, episode counts and whe
 import sys, os, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
+from peg_in_hole_gym_amd import _lib
 from peg_in_hole_gym_amd.vec_env import PihVecEnv
 
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 4096
@@ -11,7 +12,7 @@ K = int(sys.argv[2]) if len(sys.argv) > 2 else 20000
 mode = sys.argv[3] if len(sys.argv) > 3 else "action"          # action | scripted | fly (the random-fly task: quad layout, fused launch)
 fly = mode == "fly"
 kw = dict(mode=1, dv=0.05) if mode == "scripted" else (dict(task_id=1, dt=1 / 120.0, contact_margin=0.02) if fly else {})
-NACT = 6 if fly else 4; W_NC, W_F, W_BAD = (44, 43, 38) if fly else (106, 105, 97)      # state words: contact count, contact force, non-finite resets
+NACT = 6 if fly else 4; W_NC, W_F, W_BAD = (_lib.F_NCONTACT, _lib.F_CFORCE, _lib.F_SPARE) if fly else (_lib.S_NCONTACT, _lib.S_CFORCE, _lib.S_SPARE)      # state words: contact count, contact force, non-finite resets
 
 
 def run():

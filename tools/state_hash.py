@@ -4,6 +4,7 @@ the same lines -- the check used when an optimisation only re-schedules instruct
 import sys, os, hashlib
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
+from peg_in_hole_gym_amd import _lib
 from peg_in_hole_gym_amd.vec_env import PihVecEnv
 
 
@@ -17,7 +18,7 @@ def run(name, n, steps, adim, **kw):
             st = env.state()
             h.update(st.cpu().numpy().tobytes()); h.update(obs.cpu().numpy().tobytes())
             if adim == 4:
-                variants += torch.bincount(st[:, 114].long().cpu(), minlength=6)
+                variants += torch.bincount(st[:, _lib.S_SOLVER].long().cpu(), minlength=6)
     print("%-28s %s  solver variants %s" % (name, h.hexdigest()[:32], variants.tolist()))
 
 
