@@ -32,7 +32,6 @@ constexpr int CMAX = 48;      // contacts per env
 constexpr int CAMAX = 12;     // of which may involve the arm (same cap as the oracle's PIHO_CAMAX)
 constexpr int CL = 20;        // contacts whose solver data live in LDS; contacts CL..CMAX-1 spill to a global scratch
 constexpr int NROWC = 3 * CMAX;
-constexpr int CREC = 32;      // words per packed contact record
 constexpr int WPS = 39;       // LDS row stride of a contact response row: entry d = DOF d (9 arm + 29 pipe), word 38 = 0 (read by idle lanes)
 constexpr int WMS = 31;       // row stride of the staged pipe-motor response rows (29 used)
 constexpr int NMOT = 32;      // 9 arm + 23 pipe joint motors
@@ -143,12 +142,45 @@ inline Params params_from_config(const pih_config* c) {
 // dof index of link L: arm link i -> i ; pipe root (link 9) -> 9..14 (lin xyz, ang xyz) ; pipe link L>=10 -> L+5
 PIH_HD int link_dof(int L) { return L < ANL ? L : (L == ANL ? 9 : L + 5); }
 
-// Packed per-contact solver record (CREC = 32 words, 128-bit aligned so the PGS loop reads it with b128 broadcasts):
-//  0-2 p | 3 lower bound of the normal row (0, attach: -BIG) | 4 floor of the friction bound (0, attach: +BIG) | 5 mu | 6 - | 7 -
-//  8-10 n | 11 dinv_n | 12-14 t1 | 15 dinv_t1 | 16-18 t2 | 19 dinv_t2
-//  20-22 rhs (n,t1,t2) | 23 G[t1][n] | 24 G[t2][n] | 25 G[t2][t1] | 26-28 dvp_n, then multipliers | 29-31 dvp_t1, then sqrt(resid)*dinv
-// (dvp_k = relative velocity change at the contact point per unit impulse along direction k; G[a][b] = dir_a . dvp_b
-//  are the cross terms that make the in-block (n, t1, t2) update exact Gauss-Seidel)
+constexpr int CREC = 32;      // words per packed contact record
+// Packed per-contact solver record (CREC = 32 words, 128-bit aligned so the PGS loop reads it with b128 broadcasts).  Written by build_rows,
+// read by the three solvers of pih_wave.h (and the host solver of tests/emul); k = 0, 1, 2 is the row's direction n, t1, t2.
+enum : int {
+  CR_P = 0,            // 0-2   contact point (angular rows of the attach weld: the rotation-vector error)
+  CR_LB = 3,           // 3     lower bound of the normal row (0; attach rows: -BIG)
+  CR_FLOOR = 4,        // 4     floor of the friction bound max(mu * lambda_n, floor) (0; attach rows: +BIG, so all three rows are bilateral)
+  CR_MU = 5,           // 5     friction coefficient (< 0: attach rows)
+  CR_ANG = 6,          // 6     1 = angular row (attach weld), 0 = translational
+  CR_PAD = 7,          // 7     0, never read
+  CR_DIR0 = 8,         // 8-10, 12-14, 16-18   direction k at CR_DIR0 + CR_KSTRIDE * k
+  CR_DINV0 = 11,       // 11, 15, 19           1 / (J W) of row k at CR_DINV0 + CR_KSTRIDE * k
+  CR_KSTRIDE = 4,
+  CR_RHS = 20,         // 20-22 right-hand side of row k
+  CR_G = 23,           // 23-25 cross terms G[t1][n], G[t2][n], G[t2][t1] (G[a][b] = dir_a . dvp_b: they make the in-block (n, t1, t2) update exact Gauss-Seidel)
+  CR_LAM = 26,         // 26-28 multipliers of row k (DOF-space solver; the row-space solvers keep theirs in sh.r_lam) ...
+  CR_DVP_N = CR_LAM,   //       ... and until the cross terms are formed dvp_n: relative velocity change at the contact point per unit impulse along n
+  CR_THRESH = 29,      // 29-31 early-exit threshold sqrt(resid) * dinv of row k ...
+  CR_DVP_T1 = CR_THRESH,  //       ... and until the cross terms are formed dvp_t1
+};
+static_assert(CR_THRESH + 3 == CREC && CR_DINV0 == CR_DIR0 + 3 && CR_DIR0 + 3 * CR_KSTRIDE == CR_RHS && CR_DVP_T1 == CR_DVP_N + 3, "contact record layout");
+static_assert(CR_P % 4 == 0 && CR_DIR0 % 4 == 0 && CR_KSTRIDE == 4 && CR_RHS % 4 == 0 && CREC % 4 == 0, "pgs() reads the record as eight real4: (p, lb), (dir k, dinv k) and (rhs, G) each are one 16-byte group");
+// Packed motor / limit rows (16-byte records => one broadcast ds_read_b128 per row in the PGS loop)
+enum : int {
+  MR_DINV = 0,         // 1 / (J W)
+  MR_RHS = 1,          // right-hand side (vt - u) / (J W) ...
+  MR_VT = MR_RHS,      // ... before build_rows: the motor's target velocity (controller_rows)
+  MR_LAM = MR_RHS,     // ... after the row-space solvers: the row's multiplier (arm rows: motor + lower - upper limit)
+  MR_THRESH = 2,       // sqrt(resid) / (J W): early-exit threshold on |d lambda|
+  MR_IMP = 3,          // max impulse
+  MR_WORDS = 4,
+};
+enum : int {
+  LR_LO = 0,           // right-hand side of the lower-limit row of arm joint j (LR_LO + side)
+  LR_HI = 1,           // ... of the upper-limit row
+  LR_JW = 2,           // J W of the joint's motor row
+  LR_JWDINV = 3,       // (J W) dinv, filled in by the row-space solvers (1 up to rounding)
+  LR_WORDS = 4,
+};
 
 // LDS is time-multiplexed: the kinematics / ABA scratch (arena A) is dead once the free velocity update is done, the
 // solver scratch (arena B) is dead once the PGS result has been folded into the velocities.
@@ -181,11 +213,9 @@ struct Shared {
   real c_p[CMAX][3], c_n[CMAX][3], c_depth[CMAX], c_mu[CMAX];
   int nc, nca;
   real r_lam[NROWC];
-  // packed motor / limit rows (16-byte records => one broadcast ds_read_b128 per row in the PGS loop):
-  //   mrec[m] = {1/(J W), rhs, sqrt(resid)/(J W) (early-exit threshold on |d lambda|), max impulse} ; before build_rows [1] holds the target velocity
-  //   lrec[j] = {rhs lower, rhs upper, J W of arm joint j, -}
-  alignas(16) real mrec[NMOT][4];
-  alignas(16) real lrec[9][4];
+  // packed motor / limit rows: words MR_* / LR_* above
+  alignas(16) real mrec[NMOT][MR_WORDS];
+  alignas(16) real lrec[9][LR_WORDS];
   union { ArenaA a; ArenaB b; };
 };
 // global spill area of one env: response rows and records of contacts CL..CMAX-1
@@ -196,7 +226,8 @@ constexpr int OVF_WORDS = OVF_MW_OFF + OVF_MW_WORDS;
 constexpr int OVF_PAD_WORDS = 256;   // slack behind the LAST env's scratch: pgs_rows2's column ring reads (never uses) up to 12 columns past the column area
 struct Ovf { real* base; };
 PIH_HD real* wp_row(Shared& sh, const Ovf& ov, int row) { return row < 3 * CL ? sh.b.Wp[row] : ov.base + (size_t)(row - 3 * CL) * WPS; }
-PIH_HD real* crec_of(Shared& sh, const Ovf& ov, int c) { return c < CL ? sh.b.crec[c] : ov.base + OVF_W_WORDS + (size_t)(c - CL) * CREC; }
+PIH_HD real* crec_spilled(const Ovf& ov, int c) { return ov.base + OVF_W_WORDS + (size_t)(c - CL) * CREC; }      // record of a contact c >= CL
+PIH_HD real* crec_of(Shared& sh, const Ovf& ov, int c) { return c < CL ? sh.b.crec[c] : crec_spilled(ov, c); }
 PIH_HD real* wmp_row(Shared& sh, int j) { return &sh.b.Wp[0][0] + WSTAGE + j * WMS; }
 PIH_HD real* wma_row(Shared& sh, int j) { return &sh.b.Wp[0][0] + WSTAGE + WMA_OFF + j * 9; }
 
@@ -512,17 +543,17 @@ template <class W> PIH_HD void controller_rows(W& w, Shared& sh, const Params& P
     const bool closed = st >= 3 && st < 7;
     posctl_f = 1; kp_f = (real)0.1; imp_f = (closed ? (real)20000 : (real)20) * P.dt;
   }
-  // part 0: all motor rows, before build_rows (which turns word 1 into the row's right-hand side (vt - u) / (J W)).
+  // part 0: all motor rows, before build_rows (which turns MR_VT into the row's right-hand side MR_RHS (vt - u) / (J W)).
   // part 1: only the rows that do not depend on the controller (the 23 pipe motors: target 0, max impulse 1), before build_rows;
-  // part 2: the 9 arm rows AFTER build_rows (called with defer_arm: it left their word 1 alone): the same expression, evaluated once the
+  // part 2: the 9 arm rows AFTER build_rows (called with defer_arm: it left their MR_VT alone): the same expression, evaluated once the
   //         controller's targets are there -- in the fused launch the wait for the controller wavefront then sits behind the response rows.
   w.par(NMOT, [&](int m) {
     if ((part == 1 && m < 9) || (part == 2 && m >= 9)) return;
     real vt = 0, imp = 1;
     if (m < 7) { if (posctl_arm) { vt = kp_arm * (S[PIH_S_TARGET + m] - S[PIH_S_QARM + m]) / P.dt; imp = imp_arm; } }
     else if (m < 9) { if (posctl_f) { vt = kp_f * (S[PIH_S_TARGET + m] - S[PIH_S_QARM + m]) / P.dt; imp = imp_f; } }
-    sh.mrec[m][1] = part == 2 ? (vt - sh.u[m]) * sh.mrec[m][0] : vt;      // (arm DOF m = motor row m; sh.u is untouched between build_rows and here)
-    sh.mrec[m][3] = imp;
+    sh.mrec[m][MR_RHS] = part == 2 ? (vt - sh.u[m]) * sh.mrec[m][MR_DINV] : vt;      // (arm DOF m = motor row m; sh.u is untouched between build_rows and here)
+    sh.mrec[m][MR_IMP] = imp;
   });
 }
 
@@ -964,9 +995,9 @@ template <class W> PIH_HD void build_rows(W& w, Shared& sh, const Params& P, con
       const real di = (real)1 / jw;
       if (ismotor) {
         const int d = link_dof(jm);
-        sh.mrec[g][0] = di; sh.mrec[g][2] = (real)sqrt(P.resid) * di;
-        if (!(defer_arm && g < 9)) sh.mrec[g][1] = (sh.mrec[g][1] - sh.u[d]) * di;      // (deferred arm rows: controller_rows part 2)
-        if (g < 9) sh.lrec[g][2] = jw;
+        sh.mrec[g][MR_DINV] = di; sh.mrec[g][MR_THRESH] = (real)sqrt(P.resid) * di;
+        if (!(defer_arm && g < 9)) sh.mrec[g][MR_RHS] = (sh.mrec[g][MR_VT] - sh.u[d]) * di;      // (deferred arm rows: controller_rows part 2)
+        if (g < 9) sh.lrec[g][LR_JW] = jw;
       } else {
         real* R = crec_of(sh, ov, c);
         V3 vr = ang ? ld3(sh.VW[la]) : point_vel(sh, la, p);
@@ -982,11 +1013,11 @@ template <class W> PIH_HD void build_rows(W& w, Shared& sh, const Params& P, con
           int ncache = (int)sh.S[PIH_S_CACHE_N]; real key = (real)sh.c_key[c];
           for (int q = 0; q < ncache; q++) if (sh.S[PIH_S_CACHE_KEY + q] == key) { lam = P.warm * sh.S[PIH_S_CACHE_LAMBDA + q]; break; }
           const bool bil = sh.c_mu[c] < 0;
-          R[0] = p.x; R[1] = p.y; R[2] = p.z; R[3] = bil ? -PIH_BIG : (real)0; R[4] = bil ? PIH_BIG : (real)0; R[5] = sh.c_mu[c]; R[6] = ang ? (real)1 : (real)0; R[7] = 0;
+          R[CR_P] = p.x; R[CR_P + 1] = p.y; R[CR_P + 2] = p.z; R[CR_LB] = bil ? -PIH_BIG : (real)0; R[CR_FLOOR] = bil ? PIH_BIG : (real)0; R[CR_MU] = sh.c_mu[c]; R[CR_ANG] = ang ? (real)1 : (real)0; R[CR_PAD] = 0;
         } else rhs = ((ang ? -P.erp * dot(p, dir) / dt : (real)0) - ju) * di;
-        R[8 + 4 * k] = dir.x; R[9 + 4 * k] = dir.y; R[10 + 4 * k] = dir.z; R[11 + 4 * k] = di;
-        R[20 + k] = rhs;
-        if (k < 2) { R[26 + 3 * k] = dvp.x; R[27 + 3 * k] = dvp.y; R[28 + 3 * k] = dvp.z; }
+        R[CR_DIR0 + CR_KSTRIDE * k] = dir.x; R[CR_DIR0 + CR_KSTRIDE * k + 1] = dir.y; R[CR_DIR0 + CR_KSTRIDE * k + 2] = dir.z; R[CR_DINV0 + CR_KSTRIDE * k] = di;
+        R[CR_RHS + k] = rhs;
+        if (k < 2) { R[CR_DVP_N + 3 * k] = dvp.x; R[CR_DVP_N + 3 * k + 1] = dvp.y; R[CR_DVP_N + 3 * k + 2] = dvp.z; }      // (k = 1: CR_DVP_T1)
         sh.r_lam[row] = lam;
       }
     });
@@ -997,7 +1028,7 @@ template <class W> PIH_HD void build_rows(W& w, Shared& sh, const Params& P, con
         real pen = side == 0 ? q - L_LO[L] : L_HI[L] - q;
         real vb = pen > 0 ? -pen / dt : -P.erp * pen / dt;
         real sg = side == 0 ? (real)1 : (real)-1;
-        sh.lrec[L][side] = (vb - sg * sh.u[L]) * sh.mrec[L][0];
+        sh.lrec[L][LR_LO + side] = (vb - sg * sh.u[L]) * sh.mrec[L][MR_DINV];
       });
       // pull the motor rows out of the staging words before the contact rows of the second pass overwrite them
       pull_motor_rows(w, sh, mw);
@@ -1006,10 +1037,10 @@ template <class W> PIH_HD void build_rows(W& w, Shared& sh, const Params& P, con
   // cross terms of each contact block (lane = contact)
   w.par(sh.nc, [&](int c) {
     real* R = crec_of(sh, ov, c);
-    V3 t1 = ld3(R + 12), t2 = ld3(R + 16), dn = ld3(R + 26), d1 = ld3(R + 29);
-    R[23] = dot(t1, dn); R[24] = dot(t2, dn); R[25] = dot(t2, d1);
-    R[26] = sh.r_lam[3 * c]; R[27] = 0; R[28] = 0;   // multipliers (n, t1, t2) live in the record from here on (GPU PGS)
-    { const real sr = (real)sqrt(P.resid); R[29] = sr * R[11]; R[30] = sr * R[15]; R[31] = sr * R[19]; }   // early-exit thresholds sqrt(resid) * dinv
+    V3 t1 = ld3(R + CR_DIR0 + CR_KSTRIDE), t2 = ld3(R + CR_DIR0 + CR_KSTRIDE * 2), dn = ld3(R + CR_DVP_N), d1 = ld3(R + CR_DVP_T1);
+    R[CR_G] = dot(t1, dn); R[CR_G + 1] = dot(t2, dn); R[CR_G + 2] = dot(t2, d1);
+    R[CR_LAM] = sh.r_lam[3 * c]; R[CR_LAM + 1] = 0; R[CR_LAM + 2] = 0;   // multipliers (n, t1, t2) live in the record from here on (GPU PGS)
+    { const real sr = (real)sqrt(P.resid); R[CR_THRESH] = sr * R[CR_DINV0]; R[CR_THRESH + 1] = sr * R[CR_DINV0 + CR_KSTRIDE]; R[CR_THRESH + 2] = sr * R[CR_DINV0 + CR_KSTRIDE * 2]; }   // early-exit thresholds sqrt(resid) * dinv
   });
 }
 

@@ -33,8 +33,21 @@ constexpr int NC = 2 * NS + NA;    // contact slots: sphere s vs its deepest arm
 constexpr int SW = PIH_FLY_STATE_WORDS;
 static_assert(PIH_DBG_FLY_UDOT + FND <= PIH_DBG_FLY_NCONTACT && PIH_DBG_FLY_CAND + PIH_DBG_FLY_CAND_STRIDE * NC <= PIH_DBG_FLY_LAMBDA &&
               PIH_DBG_FLY_LAMBDA + NC <= PIH_DBG_CYCLES, "debug words of the random-fly step (include/pih.h PIH_DBG_FLY_*) overlap");
-constexpr int CW = 24;             // words of one contact row record in lane memory
+constexpr int CW = 24;             // words of one contact row record in lane memory (arm-vs-table rows: no object part, FC_N .. FC_IRXN stay 0)
+enum : int {
+  FC_J = 0,       // 0-5   Jacobian entries of the 6 arm joints
+  FC_W = 6,       // 6-11  response entries of the 6 arm joints
+  FC_N = 12,      // 12-14 n: the object part of the row
+  FC_RXN = 15,    // 15-17 (p - o_obj) x n
+  FC_IRXN = 18,   // 18-20 I^-1 ((p - o_obj) x n)
+  FC_DINV = 21,   // 1 / (J W)
+  FC_RHS = 22,
+  FC_LAM = 23,    // the row's multiplier: the record's LAST word
+};
+static_assert(FC_W == FC_J + NJ && FC_N == FC_W + NJ && FC_LAM + 1 == CW, "contact row record of the lane layout");
 constexpr int KW = 8;              // words of one contact CANDIDATE of a slot (staged for the rolled row-build loop)
+enum : int { FK_TAG = 0 /* 0 = empty slot, else linkA + 2 */, FK_N = 1 /* 1-3 normal */, FK_P = 4 /* 4-6 point */, FK_DEPTH = 7 };
+static_assert(FK_DEPTH + 1 == KW, "contact candidate");
 constexpr int CAND0 = NC * CW;     // candidates follow the (compacted) row records
 constexpr int LANE_WORDS = NC * CW + NC * KW;
 // ONE ENV PER QUAD of lanes (round 4, `Q::QUAD`): everything up to the solver runs replicated in the four lanes (a wavefront issues the same
@@ -42,12 +55,20 @@ constexpr int LANE_WORDS = NC * CW + NC * KW;
 // of the 12-DOF velocity change (arm joints 0-2 | arm joints 3-5 | object linear | object angular) and, of every contact row, only its own
 // three Jacobian and three response entries.  A row's J . du is three multiply-adds plus a two-step quad all-reduce (DPP quad_perm: VALU
 // operand modifiers, no LDS), its update three multiply-adds: 12 VALU instructions and 9 LDS words per contact instead of 45 and 24.
-constexpr int CWQ = 9;             // words of a lane's share of one contact row: 0-2 J | 3-5 W | 6 dinv | 7 rhs | 8 lambda
+constexpr int CWQ = 9;             // words of a lane's share of one contact row
+enum : int {
+  FQ_J = 0,       // 0-2 the lane's three Jacobian entries
+  FQ_W = 3,       // 3-5 the lane's three response entries
+  FQ_DINV = 6,
+  FQ_RHS = 7,
+  FQ_LAM = 8,     // the row's multiplier: the share's LAST word (the register copy Rr of step_env leaves it out)
+};
+static_assert(FQ_W == FQ_J + 3 && FQ_DINV == FQ_W + 3 && FQ_LAM + 1 == CWQ, "a lane's share of a contact row record, quad layout");
 // quad layout: the candidates ALIAS the row area, 16 words up and with the records' stride: record c <= k lies in [9 c, 9 c + 9), below
 // candidate k at [16 + 9 k, 24 + 9 k) -- the compacted records never catch up with the candidates still to be read.  38 KB per wave.
 constexpr int CANDQ0 = 16, KWQ = CWQ;
 constexpr int LANE_WORDS_Q = CANDQ0 + NC * KWQ;
-static_assert(KW <= KWQ && CANDQ0 + KWQ > CWQ + KW - 1 && 6 * NJ <= LANE_WORDS_Q, "candidate k must not be overwritten by record k");
+static_assert(KW <= KWQ && CANDQ0 + KWQ > FQ_LAM + FK_DEPTH + 1 && 6 * NJ <= LANE_WORDS_Q, "candidate k must not be overwritten by record k");
 constexpr int KR = 8;              // quad layout: the records of the first KR contacts of an env stay in REGISTERS over the PGS iterations (72 per lane)
 struct NoQuad {                   // (the members are never called: they keep the discarded quad branches well-formed)
   static constexpr bool QUAD = false;
@@ -162,13 +183,7 @@ struct InlineIk {      // the step runs the IK itself, one env per lane (the hos
 #else
 #define PIH_FLY_PIN24(R) ((void)0)
 #endif
-static_assert(CW == 24, "PIH_FLY_PIN24 names the 24 words of a contact record");
-#ifndef PIH_PLATFORM_DEFINED
-#define PIH_FLY_PIN9(R) __asm__ volatile("" : "+v"(R[0]), "+v"(R[1]), "+v"(R[2]), "+v"(R[3]), "+v"(R[4]), "+v"(R[5]), "+v"(R[6]), "+v"(R[7]), "+v"(R[8]))
-#else
-#define PIH_FLY_PIN9(R) ((void)0)
-#endif
-static_assert(CWQ == 9, "PIH_FLY_PIN9 names the 9 words of a lane's share of a contact record");
+static_assert(FC_LAM == 23 && CW == 24, "PIH_FLY_PIN24 lists the 24 words FC_J .. FC_LAM of a contact record");
 
 // Diagnostic phase stamps (config.debug = 2, GPU only): shader-clock cycles since the previous stamp into debug word PIH_DBG_CYCLES + k of the env
 // (tools/fly_trace.py): 0 kinematics + inertias + collision candidates, 1 articulated-body sweeps, 2 motor response rows, 3 contact rows,
@@ -189,6 +204,7 @@ struct FlyStamp { FlyStamp(real*, bool) {} void operator()(int) {} };
 template <class Ctl = InlineIk, class Q = NoQuad, class Mem>
 PIH_HD void step_env(real* S, const Params& P, int env_global, const real* action, real* obs, real* reward, unsigned char* done, Mem mem, real* dbg, Ctl ctl = Ctl(), Q quad = Q()) {
   constexpr int RW = Q::QUAD ? CWQ : CW;          // words of a contact record in this lane's memory
+  constexpr int LAMW = Q::QUAD ? FQ_LAM : FC_LAM;   // ... and its multiplier word
   constexpr int CANDQ = Q::QUAD ? CANDQ0 : NC * RW;        // lane layout: candidates follow the (compacted) row records
   constexpr int KS = Q::QUAD ? KWQ : KW;                   // stride of the candidates
   const real dt = P.dt;
@@ -379,23 +395,23 @@ PIH_HD void step_env(real* S, const Params& P, int env_global, const real* actio
       else if (k < 2 * NS) { depth = sc[i].z - (real)PIH_TABLE_Z - srad[i]; valid = i < nsph && depth < P.margin; landed = landed || (i < nsph && depth < (real)0.002); la = -1; n = mk(0, 0, 1); p = mk(sc[i].x, sc[i].y, sc[i].z - srad[i] - (real)0.5 * depth); }
       else { depth = adepth[i]; valid = depth < P.margin; la = 1 + i; n = mk(0, 0, 1); p = apt[i]; }
       const int b = CANDQ + k * KS;
-      mem.at(b) = valid ? (real)(la + 2) : (real)0;
-      mem.at(b + 1) = n.x; mem.at(b + 2) = n.y; mem.at(b + 3) = n.z; mem.at(b + 4) = p.x; mem.at(b + 5) = p.y; mem.at(b + 6) = p.z; mem.at(b + 7) = depth;
+      mem.at(b + FK_TAG) = valid ? (real)(la + 2) : (real)0;
+      mem.at(b + FK_N) = n.x; mem.at(b + FK_N + 1) = n.y; mem.at(b + FK_N + 2) = n.z; mem.at(b + FK_P) = p.x; mem.at(b + FK_P + 1) = p.y; mem.at(b + FK_P + 2) = p.z; mem.at(b + FK_DEPTH) = depth;
     }
     // contact rows -> lane memory, compacted in slot order (arm-vs-table slots: linkA = the arm link, no object part: n, rxn, wo stay 0 and
     // the object's mass term is left out)
-    //   record: 0-5 J arm | 6-11 W arm | 12-14 n | 15-17 (p - o_obj) x n | 18-20 I^-1 ((p - o_obj) x n) | 21 dinv | 22 rhs | 23 lambda
+    // (record words: FC_* / FQ_* above)
     int nc = 0;
 #pragma nounroll
     for (int k = 0; k < NC; k++) {
       const bool armtab = k >= 2 * NS;
       const int kb = CANDQ + k * KS;
-      const real tag = mem.at(kb);
+      const real tag = mem.at(kb + FK_TAG);
       const bool valid = tag != (real)0;
       if (valid) {
         const int la = (int)tag - 2;
-        const V3 n = mk(mem.at(kb + 1), mem.at(kb + 2), mem.at(kb + 3)), p = mk(mem.at(kb + 4), mem.at(kb + 5), mem.at(kb + 6));
-        const real depth = mem.at(kb + 7);
+        const V3 n = mk(mem.at(kb + FK_N), mem.at(kb + FK_N + 1), mem.at(kb + FK_N + 2)), p = mk(mem.at(kb + FK_P), mem.at(kb + FK_P + 1), mem.at(kb + FK_P + 2));
+        const real depth = mem.at(kb + FK_DEPTH);
         real J[NJ], W[NJ];
         const real sg = armtab ? (real)1 : (real)-1;       // the normal points from the other body to the object / from the table to the arm
 #pragma unroll
@@ -421,13 +437,13 @@ PIH_HD void step_env(real* S, const Params& P, int env_global, const real* actio
           const real j3[3] = {s4 == 0 ? J[0] : s4 == 1 ? J[3] : s4 == 2 ? no.x : rxn.x, s4 == 0 ? J[1] : s4 == 1 ? J[4] : s4 == 2 ? no.y : rxn.y, s4 == 0 ? J[2] : s4 == 1 ? J[5] : s4 == 2 ? no.z : rxn.z};
           const real w3[3] = {s4 == 0 ? W[0] : s4 == 1 ? W[3] : s4 == 2 ? wl.x : wo.x, s4 == 0 ? W[1] : s4 == 1 ? W[4] : s4 == 2 ? wl.y : wo.y, s4 == 0 ? W[2] : s4 == 1 ? W[5] : s4 == 2 ? wl.z : wo.z};
 #pragma unroll
-          for (int t = 0; t < 3; t++) { mem.at(b + t) = j3[t]; mem.at(b + 3 + t) = w3[t]; }
-          mem.at(b + 6) = di; mem.at(b + 7) = (vb - ju) * di; mem.at(b + 8) = 0;
+          for (int t = 0; t < 3; t++) { mem.at(b + FQ_J + t) = j3[t]; mem.at(b + FQ_W + t) = w3[t]; }
+          mem.at(b + FQ_DINV) = di; mem.at(b + FQ_RHS) = (vb - ju) * di; mem.at(b + FQ_LAM) = 0;
         } else {
 #pragma unroll
-        for (int L = 0; L < NJ; L++) { mem.at(b + L) = J[L]; mem.at(b + 6 + L) = W[L]; }
-        mem.at(b + 12) = no.x; mem.at(b + 13) = no.y; mem.at(b + 14) = no.z; mem.at(b + 15) = rxn.x; mem.at(b + 16) = rxn.y; mem.at(b + 17) = rxn.z;
-        mem.at(b + 18) = wo.x; mem.at(b + 19) = wo.y; mem.at(b + 20) = wo.z; mem.at(b + 21) = di; mem.at(b + 22) = (vb - ju) * di; mem.at(b + 23) = 0;
+        for (int L = 0; L < NJ; L++) { mem.at(b + FC_J + L) = J[L]; mem.at(b + FC_W + L) = W[L]; }
+        mem.at(b + FC_N) = no.x; mem.at(b + FC_N + 1) = no.y; mem.at(b + FC_N + 2) = no.z; mem.at(b + FC_RXN) = rxn.x; mem.at(b + FC_RXN + 1) = rxn.y; mem.at(b + FC_RXN + 2) = rxn.z;
+        mem.at(b + FC_IRXN) = wo.x; mem.at(b + FC_IRXN + 1) = wo.y; mem.at(b + FC_IRXN + 2) = wo.z; mem.at(b + FC_DINV) = di; mem.at(b + FC_RHS) = (vb - ju) * di; mem.at(b + FC_LAM) = 0;
         }
         if (dbg && P.debug) { real* d = dbg + PIH_DBG_FLY_CAND + PIH_DBG_FLY_CAND_STRIDE * k; d[0] = 1; d[1] = (real)la; d[2] = p.x; d[3] = p.y; d[4] = p.z; d[5] = n.x; d[6] = n.y; d[7] = n.z; d[8] = depth; d[9] = (real)nc; }
         nc++;
@@ -440,13 +456,13 @@ PIH_HD void step_env(real* S, const Params& P, int env_global, const real* actio
     // contact: such a row computes dl = 0), requested BEFORE the wait for the IK targets.  Through LDS a contact cost ~ 225 cycles per
     // iteration although it is 25 instructions: the ~ 200-cycle round trip of a batch of record reads was not covered by one contact's
     // arithmetic (gpurun_out/fly_trace_r04k.txt: 450 cycles per pair of contacts).  ncw: the largest contact count of the wavefront.
-    real Rr[KR][CWQ - 1], lamr[KR]; int ncw = 0;
+    real Rr[KR][FQ_LAM], lamr[KR]; int ncw = 0;      // (words FQ_J .. FQ_RHS; the multipliers in lamr)
     if constexpr (Q::QUAD) {
       ncw = quad.wave_max(nc);
 #pragma unroll
       for (int c = 0; c < KR; c++) {
 #pragma unroll
-        for (int i = 0; i < CWQ - 1; i++) { const real v = mem.at(c * CWQ + i); Rr[c][i] = c < nc ? v : (real)0; }
+        for (int i = 0; i < FQ_LAM; i++) { const real v = mem.at(c * CWQ + i); Rr[c][i] = c < nc ? v : (real)0; }
         lamr[c] = 0;
       }
     }
@@ -543,18 +559,18 @@ PIH_HD void step_env(real* S, const Params& P, int env_global, const real* actio
           PIH_FLY_PIN24(R);
           real jd = 0;
   #pragma unroll
-          for (int L = 0; L < NJ; L++) jd += R[L] * du[L];
-          const V3 n = mk(R[12], R[13], R[14]), rxn = mk(R[15], R[16], R[17]);
+          for (int L = 0; L < NJ; L++) jd += R[FC_J + L] * du[L];
+          const V3 n = mk(R[FC_N], R[FC_N + 1], R[FC_N + 2]), rxn = mk(R[FC_RXN], R[FC_RXN + 1], R[FC_RXN + 2]);
           jd += dot(n, mk(du[6], du[7], du[8])) + dot(rxn, mk(du[9], du[10], du[11]));
-          const real di = R[21], lam = R[23];
-          real dl = R[22] - jd * di;
+          const real di = R[FC_DINV], lam = R[FC_LAM];
+          real dl = R[FC_RHS] - jd * di;
           const real sum = max_(lam + dl, (real)0);
-          dl = sum - lam; mem.at(c * CW + 23) = sum;
+          dl = sum - lam; mem.at(c * CW + FC_LAM) = sum;
   #pragma unroll
-          for (int L = 0; L < NJ; L++) du[L] += R[6 + L] * dl;
+          for (int L = 0; L < NJ; L++) du[L] += R[FC_W + L] * dl;
           const real im = dl * omass_inv;
           du[6] += n.x * im; du[7] += n.y * im; du[8] += n.z * im;
-          du[9] += R[18] * dl; du[10] += R[19] * dl; du[11] += R[20] * dl;
+          du[9] += R[FC_IRXN] * dl; du[10] += R[FC_IRXN + 1] * dl; du[11] += R[FC_IRXN + 2] * dl;
           if (CHECK) { const real v = dl * dl - P.resid * di * di; worst = v > worst ? v : worst; }
         };
         static_assert((NC + 2) * CW <= LANE_WORDS, "the read-ahead of up to two records stays inside the lane's words");
@@ -586,14 +602,14 @@ PIH_HD void step_env(real* S, const Params& P, int env_global, const real* actio
         for (int c = 0; c < KR; c++) {
           if (c >= ncw) break;               // (wave-uniform: ONE taken branch per sweep, past the remaining register records)
           {
-            real jd = Rr[c][0] * du3[0] + Rr[c][1] * du3[1] + Rr[c][2] * du3[2];
+            real jd = Rr[c][FQ_J] * du3[0] + Rr[c][FQ_J + 1] * du3[1] + Rr[c][FQ_J + 2] * du3[2];
             jd += quad.xor1(jd); jd += quad.xor2(jd);
-            const real di = Rr[c][6];
-            real dl = Rr[c][7] - jd * di;
+            const real di = Rr[c][FQ_DINV];
+            real dl = Rr[c][FQ_RHS] - jd * di;
             const real sum = max_(lamr[c] + dl, (real)0);
             dl = sum - lamr[c]; lamr[c] = sum;
   #pragma unroll
-            for (int k = 0; k < 3; k++) du3[k] += Rr[c][3 + k] * dl;
+            for (int k = 0; k < 3; k++) du3[k] += Rr[c][FQ_W + k] * dl;
             if (CHECK) { const real v = dl * dl - P.resid * di * di; worst = v > worst ? v : worst; }
           }
         }
@@ -603,14 +619,14 @@ PIH_HD void step_env(real* S, const Params& P, int env_global, const real* actio
             real R[CWQ];
   #pragma unroll
             for (int i = 0; i < CWQ; i++) R[i] = mem.at(c * CWQ + i);
-            real jd = R[0] * du3[0] + R[1] * du3[1] + R[2] * du3[2];
+            real jd = R[FQ_J] * du3[0] + R[FQ_J + 1] * du3[1] + R[FQ_J + 2] * du3[2];
             jd += quad.xor1(jd); jd += quad.xor2(jd);
-            const real di = R[6], lam = R[8];
-            real dl = R[7] - jd * di;
+            const real di = R[FQ_DINV], lam = R[FQ_LAM];
+            real dl = R[FQ_RHS] - jd * di;
             const real sum = max_(lam + dl, (real)0);
-            dl = sum - lam; mem.at(c * CWQ + 8) = sum;
+            dl = sum - lam; mem.at(c * CWQ + FQ_LAM) = sum;
   #pragma unroll
-            for (int k = 0; k < 3; k++) du3[k] += R[3 + k] * dl;
+            for (int k = 0; k < 3; k++) du3[k] += R[FQ_W + k] * dl;
             if (CHECK) { const real v = dl * dl - P.resid * di * di; worst = v > worst ? v : worst; }
           }
         }
@@ -648,7 +664,7 @@ PIH_HD void step_env(real* S, const Params& P, int env_global, const real* actio
 #pragma unroll
         for (int c = 0; c < KR; c++) lamr[c] = 0;
       }
-      if (pass == 1) for (int c = 0; c < nc; c++) mem.at(c * RW + RW - 1) = 0;
+      if (pass == 1) for (int c = 0; c < nc; c++) mem.at(c * RW + LAMW) = 0;
       // iterations 1 .. 4 with the test, then groups of `checkstride`: stride - 1 without, one with; the last iteration always with (the
       // structure of pgs_iteration_loop, pih_wave.h: no per-iteration modulo -- as `(i - 4) % stride` it was a 40-instruction integer
       // division in front of every sweep)
@@ -666,17 +682,17 @@ PIH_HD void step_env(real* S, const Params& P, int env_global, const real* actio
     if (dbg && P.debug) dbg[PIH_DBG_FLY_LIMIT_ROWS] = redone ? (real)2 : (real)(limmask0 != 0);      // 1: limit rows of some joint from the start; 2: the solve was repeated with every limit row
     if constexpr (Q::QUAD) {
 #pragma unroll
-      for (int c = 0; c < KR; c++) if (c < nc) mem.at(c * CWQ + 8) = lamr[c];
+      for (int c = 0; c < KR; c++) if (c < nc) mem.at(c * CWQ + FQ_LAM) = lamr[c];
 #pragma unroll
       for (int k = 0; k < 3; k++) {
         du[k] = quad.template bcast<0>(du3[k]); du[3 + k] = quad.template bcast<1>(du3[k]); du[6 + k] = quad.template bcast<2>(du3[k]); du[9 + k] = quad.template bcast<3>(du3[k]);
       }
     }
     real cf = 0;
-    for (int c = 0; c < nc; c++) cf += mem.at(c * RW + RW - 1);
+    for (int c = 0; c < nc; c++) cf += mem.at(c * RW + LAMW);
     if (dbg && P.debug) {
       dbg[PIH_DBG_FLY_NCONTACT] = (real)nc; dbg[PIH_DBG_FLY_PGS_ITERS] = (real)it;
-      for (int c = 0; c < nc; c++) dbg[PIH_DBG_FLY_LAMBDA + c] = mem.at(c * RW + RW - 1);    // lambda_n of compacted contact c (the candidate records end below it)
+      for (int c = 0; c < nc; c++) dbg[PIH_DBG_FLY_LAMBDA + c] = mem.at(c * RW + LAMW);    // lambda_n of compacted contact c (the candidate records end below it)
     }
     stamp(5);
     // ---- integrate

@@ -167,7 +167,7 @@ PIH_HD void step_env(W& w, Shared& sh, const Params& P, const Ovf& ov, int env, 
     });
     if (dbg && P.debug) {
       w.par(sh.nc, [&](int c) { dbg[PIH_DBG_CONTACT + PIH_DBG_CONTACT_STRIDE * c + PIH_DBG_CONTACT_LAMBDA] = sh.r_lam[3 * c]; });
-      w.par(3 * sh.nc, [&](int r) { dbg[PIH_DBG_DINV + r] = crec_of(sh, ov, r / 3)[11 + 4 * (r % 3)]; });
+      w.par(3 * sh.nc, [&](int r) { dbg[PIH_DBG_DINV + r] = crec_of(sh, ov, r / 3)[CR_DINV0 + CR_KSTRIDE * (r % 3)]; });
     }
     S[PIH_S_CACHE_N] = (real)sh.nc;
     S[PIH_S_CFORCE] = cf / dt; S[PIH_S_NCONTACT] = (real)sh.nc; S[PIH_S_PGS_ITERS] = (real)iters;

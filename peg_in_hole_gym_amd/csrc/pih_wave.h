@@ -408,6 +408,10 @@ template <bool DOUBLED = true, class FC, class FN> PIH_HD int pgs_iteration_loop
   }
   return it;
 }
+// Word W (a CR_* / MR_* / LR_* name, pih_common.h) of a record held in registers as 16-byte groups: component W % 4 of group W / 4,
+// picked at compile time; rec4v: words W .. W + 2 as a vector
+template <int W> PIH_HD real rec4(const real4* q) { constexpr int c = W % 4; return c == 0 ? q[W / 4].x : c == 1 ? q[W / 4].y : c == 2 ? q[W / 4].z : q[W / 4].w; }
+template <int W> PIH_HD V3 rec4v(const real4* q) { return mk(rec4<W>(q), rec4<W + 1>(q), rec4<W + 2>(q)); }
 constexpr int FR = NMOT + 3 * MERGED_CONTACTS;
 PIH_HD int pgs_rows(Wave& w, Shared& sh, const Params& P) {
   const int nc = __builtin_amdgcn_readfirstlane(sh.nc);
@@ -421,7 +425,7 @@ PIH_HD int pgs_rows(Wave& w, Shared& sh, const Params& P) {
     const int row = ismotor ? 0 : lane - NMOT, c = row / 3, k = row - 3 * c;
     const bool live = !ismotor && c < nc;
     int la = -1, lb = -1; V3 p = mk(0, 0, 0), dir = mk(0, 0, 0); bool ang = false;
-    if (live) { la = sh.c_la[c]; lb = sh.c_lb[c]; const real* R = sh.b.crec[c]; p = ld3(R); dir = ld3(R + 8 + 4 * k); ang = R[6] != 0; }
+    if (live) { la = sh.c_la[c]; lb = sh.c_lb[c]; const real* R = sh.b.crec[c]; p = ld3(R + CR_P); dir = ld3(R + CR_DIR0 + CR_KSTRIDE * k); ang = R[CR_ANG] != 0; }
     const int md = lane < 9 ? lane : 15 + (lane - 9);
     // No contact involves the arm in 99.9 % of the env-steps of a random-action rollout (sh.nca, counted by collide): the nine arm
     // entries of every contact row's Jacobian and response row are then exact zeros, and both the entries and their products are
@@ -487,23 +491,23 @@ PIH_HD int pgs_rows(Wave& w, Shared& sh, const Params& P) {
   // share one lane): their lanes hold z = -dinv (J du).
   w.sync();
   real di = 0, rhs = 0, thr = PIH_BIG, lbv = 0, ubv = 0, cmu = 0, cfl = 0, lam0 = 0;
-  if (lane < 9) di = sh.mrec[lane][0];
-  else if (lane < NMOT) { di = sh.mrec[lane][0]; rhs = sh.mrec[lane][1]; thr = sh.mrec[lane][2]; ubv = sh.mrec[lane][3]; lbv = -ubv; }
+  if (lane < 9) di = sh.mrec[lane][MR_DINV];
+  else if (lane < NMOT) { di = sh.mrec[lane][MR_DINV]; rhs = sh.mrec[lane][MR_RHS]; thr = sh.mrec[lane][MR_THRESH]; ubv = sh.mrec[lane][MR_IMP]; lbv = -ubv; }
   else {
     const int row = lane - NMOT, c = row / 3, k = row - 3 * c;
     if (c < nc) {
       const real* R = sh.b.crec[c];
-      di = R[11 + 4 * k]; rhs = R[20 + k]; thr = R[29 + k]; cmu = R[5]; cfl = R[4];
-      if (k == 0) { lbv = R[3]; ubv = PIH_BIG; lam0 = sh.r_lam[3 * c]; }      // friction rows: bounds set per iteration from the normal multiplier
+      di = R[CR_DINV0 + CR_KSTRIDE * k]; rhs = R[CR_RHS + k]; thr = R[CR_THRESH + k]; cmu = R[CR_MU]; cfl = R[CR_FLOOR];
+      if (k == 0) { lbv = R[CR_LB]; ubv = PIH_BIG; lam0 = sh.r_lam[3 * c]; }      // friction rows: bounds set per iteration from the normal multiplier
     }
   }
-  // (sqrt(resid) * dinv of a contact row sits in words 29..31 of its record, the multipliers go back to sh.r_lam)
+  // (sqrt(resid) * dinv of a contact row sits in words CR_THRESH.. of its record, the multipliers go back to sh.r_lam)
 #pragma unroll
   for (int i = 0; i < FR; i++) { A[i] = (lane == i && lane >= 9 ? (real)1 : (real)0) - di * A[i]; }
   real* const Bn = A;
   unsigned angmask = 0;                    // contacts whose friction rows are always solved (mu < 0: the attach weld's rows)
 #pragma unroll
-  for (int c = 0; c < MERGED_CONTACTS; c++) if (c < nc && sh.b.crec[c][5] < 0) angmask |= 1u << c;
+  for (int c = 0; c < MERGED_CONTACTS; c++) if (c < nc && sh.b.crec[c][CR_MU] < 0) angmask |= 1u << c;
   angmask = (unsigned)__builtin_amdgcn_readfirstlane((int)angmask);
   // ---- the limit rows of arm joints 0..6 are exact no-ops for the whole solve when (a) the joint's motor row is never clamped --
   // an unclamped velocity motor sets the joint's velocity change to (target - current) whatever it was, because J W dinv = 1 -- and
@@ -517,20 +521,20 @@ PIH_HD int pgs_rows(Wave& w, Shared& sh, const Params& P) {
 #pragma unroll
     for (int j = 0; j < 7; j++) {
       const real q = sh.S[PIH_S_QARM + j], uj = sh.u[j];
-      const real vt = sh.mrec[j][1] * sh.lrec[j][2] + uj;                         // rhs / dinv + u = the motor's target velocity
+      const real vt = sh.mrec[j][MR_RHS] * sh.lrec[j][LR_JW] + uj;                         // rhs / dinv + u = the motor's target velocity
       const real plo = q - L_LO[j], phi = L_HI[j] - q;
       const real vlo = plo > 0 ? -plo / dt : -P.erp * plo / dt, vhi = phi > 0 ? -phi / dt : -P.erp * phi / dt;
       const real tol = (real)1e-4 * ((real)1 + absr(vt) + absr(uj) + absr(vlo) + absr(vhi));
       skip7 = skip7 && (vt - vlo > tol) && (-vhi - vt > tol);
     }
     // only with the huge impulse bound of the action-mode controller (1e5 dt): the scripted controller's 1200 dt does clamp
-    skip7 = skip7 && sh.mrec[0][3] >= (real)100;
+    skip7 = skip7 && sh.mrec[0][MR_IMP] >= (real)100;
     skip7 = __builtin_amdgcn_readfirstlane((int)skip7) != 0;
   }
-  real armlim = sh.mrec[0][3];
+  real armlim = sh.mrec[0][MR_IMP];
 #pragma unroll
-  for (int j = 1; j < 7; j++) armlim = sh.mrec[j][3] < armlim ? sh.mrec[j][3] : armlim;
-  if (lane < 9) sh.lrec[lane][3] = sh.lrec[lane][2] * sh.mrec[lane][0];          // (J W) dinv of the arm joint (1 up to rounding)
+  for (int j = 1; j < 7; j++) armlim = sh.mrec[j][MR_IMP] < armlim ? sh.mrec[j][MR_IMP] : armlim;
+  if (lane < 9) sh.lrec[lane][LR_JWDINV] = sh.lrec[lane][LR_JW] * sh.mrec[lane][MR_DINV];          // (J W) dinv of the arm joint (1 up to rounding)
   w.sync();
   // ---- multipliers: arm rows wave-uniform in VGPRs, every other row in its own lane
   real lam_a[9], lam_lo[9], lam_hi[9], lamr[NMOT];     // pipe motor rows: wave-uniform multipliers (lam[g] += step: one issue slot)
@@ -572,8 +576,8 @@ PIH_HD int pgs_rows(Wave& w, Shared& sh, const Params& P) {
         if (j < 9 && (PIH_OBJ_NJ * j) / 9 == jp) {   // arm joint block: motor, lower limit, upper limit; y = dinv (J du) of the joint
           const real4 ca = pa4[j % PF], cl = pl4[j % PF];
           if (j + PF < 9) { pa4[j % PF] = *reinterpret_cast<const real4*>(sh.mrec[j + PF]); pl4[j % PF] = *reinterpret_cast<const real4*>(sh.lrec[j + PF]); }
-          const real rh = ca.y, th = ca.z, lim = ca.w;
-          const real lor = cl.x, hir = cl.y, wd = cl.w;
+          const real rh = rec4<MR_RHS>(&ca), th = rec4<MR_THRESH>(&ca), lim = rec4<MR_IMP>(&ca);
+          const real lor = rec4<LR_LO>(&cl), hir = rec4<LR_HI>(&cl), wd = rec4<LR_JWDINV>(&cl);
           real y = -rdlane(za, j);
           real sum = lam_a[j] + (rh - y);
           sum = med3_(sum, -lim, lim);
@@ -638,10 +642,10 @@ PIH_HD int pgs_rows(Wave& w, Shared& sh, const Params& P) {
   if (!skip7) { solve(std::true_type{}); variant = 2; }
   else if (solve(std::false_type{})) { solve(std::true_type{}); variant = 4; }
   if (lane == 0) sh.S[PIH_S_SOLVER] = (real)variant;
-  // multipliers back to LDS: contacts -> r_lam, pipe motors -> word 1 of their (now unused) constant record
+  // multipliers back to LDS: contacts -> r_lam, pipe motors -> MR_LAM of their (now unused) constant record
   if (lane >= NMOT && lane < NMOT + 3 * nc) sh.r_lam[lane - NMOT] = lam;
 #pragma unroll
-  for (int g = 9; g < NMOT; g++) if (lane == 0) sh.mrec[g][1] = lamr[g];
+  for (int g = 9; g < NMOT; g++) if (lane == 0) sh.mrec[g][MR_LAM] = lamr[g];
   w.sync();
   {
     const int d = lane, dw = d < ND ? d : ND;
@@ -651,7 +655,7 @@ PIH_HD int pgs_rows(Wave& w, Shared& sh, const Params& P) {
       for (int j = 0; j < 9; j++) du += wma_row(sh, j)[d] * (lam_a[j] + lam_lo[j] - lam_hi[j]);
     } else if (d < ND) {
 #pragma unroll
-      for (int j = 0; j < PIH_OBJ_NJ; j++) du += wmp_row(sh, j)[d - 9] * sh.mrec[9 + j][1];
+      for (int j = 0; j < PIH_OBJ_NJ; j++) du += wmp_row(sh, j)[d - 9] * sh.mrec[9 + j][MR_LAM];
     }
 #pragma unroll
     for (int c = 0; c < MERGED_CONTACTS; c++)
@@ -686,14 +690,14 @@ PIH_HD int pgs_rows2(Wave& w, Shared& sh, const Params& P, const Ovf& ov, const 
   struct RowC { real di, rhs, thr, lb, ub, mu, fl, lam0; };
   auto rowconst = [&](int g) __attribute__((always_inline)) -> RowC {
     RowC r; r.di = 0; r.rhs = 0; r.thr = PIH_BIG; r.lb = 0; r.ub = 0; r.mu = 0; r.fl = 0; r.lam0 = 0;
-    if (g < 9) r.di = sh.mrec[g][0];
-    else if (g < NMOT) { r.di = sh.mrec[g][0]; r.rhs = sh.mrec[g][1]; r.thr = sh.mrec[g][2]; r.ub = sh.mrec[g][3]; r.lb = -r.ub; }
+    if (g < 9) r.di = sh.mrec[g][MR_DINV];
+    else if (g < NMOT) { r.di = sh.mrec[g][MR_DINV]; r.rhs = sh.mrec[g][MR_RHS]; r.thr = sh.mrec[g][MR_THRESH]; r.ub = sh.mrec[g][MR_IMP]; r.lb = -r.ub; }
     else {
       const int row = g - NMOT, c = row / 3, k = row - 3 * c;
       if (c < nc) {
-        const real* R = c < CL ? sh.b.crec[c] : ov.base + OVF_W_WORDS + (size_t)(c - CL) * CREC;
-        r.di = R[11 + 4 * k]; r.rhs = R[20 + k]; r.thr = R[29 + k]; r.mu = R[5]; r.fl = R[4];
-        if (k == 0) { r.lb = R[3]; r.ub = PIH_BIG; r.lam0 = sh.r_lam[3 * c]; }
+        const real* R = crec_of(sh, ov, c);
+        r.di = R[CR_DINV0 + CR_KSTRIDE * k]; r.rhs = R[CR_RHS + k]; r.thr = R[CR_THRESH + k]; r.mu = R[CR_MU]; r.fl = R[CR_FLOOR];
+        if (k == 0) { r.lb = R[CR_LB]; r.ub = PIH_BIG; r.lam0 = sh.r_lam[3 * c]; }
       }
     }
     return r;
@@ -736,8 +740,8 @@ PIH_HD int pgs_rows2(Wave& w, Shared& sh, const Params& P, const Ovf& ov, const 
       const int row = g - NMOT, c = row / 3, k = row - 3 * c;
       if (c >= nc) return;
       live = true; la = sh.c_la[c]; lb = sh.c_lb[c];
-      const real* R = c < CL ? sh.b.crec[c] : ov.base + OVF_W_WORDS + (size_t)(c - CL) * CREC;
-      p = ld3(R); dir = ld3(R + 8 + 4 * k); ang = R[6] != 0;
+      const real* R = crec_of(sh, ov, c);
+      p = ld3(R + CR_P); dir = ld3(R + CR_DIR0 + CR_KSTRIDE * k); ang = R[CR_ANG] != 0;
     };
     int la0, lb0, la1, lb1; V3 p0, d0, p1, d1; bool a0, a1, l0, l1;
     geom(lane, la0, lb0, p0, d0, a0, l0); geom(64 + lane, la1, lb1, p1, d1, a1, l1);
@@ -812,9 +816,9 @@ PIH_HD int pgs_rows2(Wave& w, Shared& sh, const Params& P, const Ovf& ov, const 
 #pragma unroll
   for (int q = NMOT; q < KREG; q++) if (q >= NMOT + 3 * nc) BB[q] = 0;
   unsigned angmask = 0;
-  for (int c = 0; c < nc; c++) { const real* R = c < CL ? sh.b.crec[c] : ov.base + OVF_W_WORDS + (size_t)(c - CL) * CREC; if (R[5] < 0) angmask |= 1u << c; }
+  for (int c = 0; c < nc; c++) { const real* R = crec_of(sh, ov, c); if (R[CR_MU] < 0) angmask |= 1u << c; }
   angmask = (unsigned)__builtin_amdgcn_readfirstlane((int)angmask);
-  if (lane < 9) sh.lrec[lane][3] = sh.lrec[lane][2] * sh.mrec[lane][0];          // (J W) dinv of the arm joint (1 up to rounding)
+  if (lane < 9) sh.lrec[lane][LR_JWDINV] = sh.lrec[lane][LR_JW] * sh.mrec[lane][MR_DINV];          // (J W) dinv of the arm joint (1 up to rounding)
   __threadfence_block();                                     // the streamed columns: written above, read back by the same lane
   w.sync();
   // ---- solve (every limit row in place)
@@ -852,8 +856,8 @@ PIH_HD int pgs_rows2(Wave& w, Shared& sh, const Params& P, const Ovf& ov, const 
       if (j < 9) {
         const real4 ca = pa4[j % PF], cl = pl4[j % PF];
         if (j + PF < 9) { pa4[j % PF] = *reinterpret_cast<const real4*>(sh.mrec[j + PF]); pl4[j % PF] = *reinterpret_cast<const real4*>(sh.lrec[j + PF]); }
-        const real rh = ca.y, th = ca.z, lim = ca.w;
-        const real lor = cl.x, hir = cl.y, wd = cl.w;
+        const real rh = rec4<MR_RHS>(&ca), th = rec4<MR_THRESH>(&ca), lim = rec4<MR_IMP>(&ca);
+        const real lor = rec4<LR_LO>(&cl), hir = rec4<LR_HI>(&cl), wd = rec4<LR_JWDINV>(&cl);
         real y = -rdlane(za, j);
         real sum = lam_a[j] + (rh - y);
         sum = med3_(sum, -lim, lim);
@@ -926,16 +930,16 @@ PIH_HD int pgs_rows2(Wave& w, Shared& sh, const Params& P, const Ovf& ov, const 
   // ---- multipliers back to LDS, DOF velocities du = sum_i W_i lambda_i
   if (lane >= NMOT && lane < NMOT + 3 * nc) sh.r_lam[lane - NMOT] = lam0;
   if (32 + lane < 3 * nc) sh.r_lam[32 + lane] = lam1;
-  if (lane >= 9 && lane < NMOT) sh.mrec[lane][1] = lam0;
+  if (lane >= 9 && lane < NMOT) sh.mrec[lane][MR_LAM] = lam0;
 #pragma unroll
-  for (int j = 0; j < 9; j++) if (lane == 0) sh.mrec[j][1] = lam_a[j] + lam_lo[j] - lam_hi[j];
+  for (int j = 0; j < 9; j++) if (lane == 0) sh.mrec[j][MR_LAM] = lam_a[j] + lam_lo[j] - lam_hi[j];
   w.sync();
   {
     const int d = lane, dw = d < ND ? d : ND;
     real du = 0;
 #pragma unroll
     for (int j = 0; j < PIH_OBJ_NJ; j++) {
-      du += Mg[j * 64] * (d < 9 ? (j < 9 ? sh.mrec[j][1] : (real)0) : sh.mrec[9 + j][1]);
+      du += Mg[j * 64] * (d < 9 ? (j < 9 ? sh.mrec[j][MR_LAM] : (real)0) : sh.mrec[9 + j][MR_LAM]);
     }
     // du += sum_r W_r[d] lambda_r: rows of contacts < CL from LDS, the others from the env's scratch -- two loops with known address
     // spaces, four reads in flight (one loop over the generic row pointer was a serialised round trip per row, flat loads to global
@@ -1023,8 +1027,8 @@ PIH_HD int pgs(Wave& w, Shared& sh, const Params& P, const Ovf& ov, const MotorW
       if (j < 9) {   // arm joint block: motor, lower limit, upper limit (wave-uniform chain)
         const real4 ca = pa4[j % PF], cl = pl4[j % PF];
         if (j + PF < 9) { pa4[j % PF] = *reinterpret_cast<const real4*>(sh.mrec[j + PF]); pl4[j % PF] = *reinterpret_cast<const real4*>(sh.lrec[j + PF]); }
-        const real di = ca.x, rhs = ca.y, thr = ca.z, lim = ca.w;
-        const real lor = cl.x, hir = cl.y, wjj = cl.z;
+        const real di = rec4<MR_DINV>(&ca), rhs = rec4<MR_RHS>(&ca), thr = rec4<MR_THRESH>(&ca), lim = rec4<MR_IMP>(&ca);
+        const real lor = rec4<LR_LO>(&cl), hir = rec4<LR_HI>(&cl), wjj = rec4<LR_JW>(&cl);
         real dj = rdlane(du, j);
         real sum = lam_a[j] + (rhs - dj * di);
         sum = med3_(sum, -lim, lim);
@@ -1041,7 +1045,7 @@ PIH_HD int pgs(Wave& w, Shared& sh, const Params& P, const Ovf& ov, const MotorW
         tot_a = dl + d2 - d3;
       }
       // pipe joint motor j (DOF 15 + j)
-      const real di = cm.x, rhs = cm.y, thr = cm.z, lim = cm.w;
+      const real di = rec4<MR_DINV>(&cm), rhs = rec4<MR_RHS>(&cm), thr = rec4<MR_THRESH>(&cm), lim = rec4<MR_IMP>(&cm);
       real dj = rdlane(du, 15 + j);
       real sum = lam_p[j] + (rhs - dj * di);
       sum = med3_(sum, -lim, lim);
@@ -1066,38 +1070,38 @@ PIH_HD int pgs(Wave& w, Shared& sh, const Params& P, const Ovf& ov, const MotorW
     auto block = [&](int c, unsigned sgw, const CRec& r, real* R, bool in_lds) __attribute__((always_inline)) {
       // (the angular rows of the attach weld -- at most one such contact, scripted mode only, index ang_c -- take the DOF's axis
       //  itself as Jacobian column instead of axis x lever arm: one scalar compare per contact)
-      // q0 = p.xyz, lo_n | q1 = hi_floor, mu, -, - | q2 = n, dinv_n | q3 = t1, dinv_t1 | q4 = t2, dinv_t2
-      // q5 = rhs n,t1,t2, G[t1][n] | q6 = G[t2][n], G[t2][t1], lam_n, lam_t1 | q7 = lam_t2, ...
-      // (lo_n = 0 / -BIG and hi_floor = 0 / +BIG make the attach rows bilateral without a select)
+      // (the record's words by name, rec4<CR_*>: pih_common.h; CR_LB = 0 / -BIG and CR_FLOOR = 0 / +BIG make the attach rows bilateral
+      //  without a select)
+      const real4* const q = r.q;
       const real w0 = r.w0, w1 = r.w1, w2 = r.w2;
-      const V3 pr = mk(r.q[0].x - g.o.x, r.q[0].y - g.o.y, r.q[0].z - g.o.z);
-      const real mu = r.q[1].y;
+      const V3 pr = mk(rec4<CR_P>(q) - g.o.x, rec4<CR_P + 1>(q) - g.o.y, rec4<CR_P + 2>(q) - g.o.z);
+      const real mu = rec4<CR_MU>(q);
       const real sdu = (real)(int)__builtin_amdgcn_sbfe(sgw, 2u * (unsigned)(c & 15), 2u) * du;
       V3 cv = mk(__builtin_fmaf(ae.y, pr.z, __builtin_fmaf(-ae.z, pr.y, mp.x)), __builtin_fmaf(ae.z, pr.x, __builtin_fmaf(-ae.x, pr.z, mp.y)), __builtin_fmaf(ae.x, pr.y, __builtin_fmaf(-ae.y, pr.x, mp.z)));
       if (__builtin_expect(c == ang_cs, 0)) cv = ae;
-      real jd0 = sdu * dot(mk(r.q[2].x, r.q[2].y, r.q[2].z), cv), jd1 = sdu * dot(mk(r.q[3].x, r.q[3].y, r.q[3].z), cv), jd2 = sdu * dot(mk(r.q[4].x, r.q[4].y, r.q[4].z), cv);
+      real jd0 = sdu * dot(rec4v<CR_DIR0>(q), cv), jd1 = sdu * dot(rec4v<CR_DIR0 + CR_KSTRIDE>(q), cv), jd2 = sdu * dot(rec4v<CR_DIR0 + CR_KSTRIDE * 2>(q), cv);
       // materialise the products: otherwise fast-math folds the multiply into the first reduction step as mul + mov_dpp + fmac
       // (3 instructions per value) instead of mul + v_add_f32_dpp (2)
       __asm__ volatile("" : "+v"(jd0), "+v"(jd1), "+v"(jd2));
       row16_sum3(jd0, jd1, jd2);
       rows012_total3(jd0, jd1, jd2);          // valid in lanes 32..47 from here; the scalar chain below runs in plain VGPRs
-      const real l0 = r.q[6].z, l1 = r.q[6].w, l2 = r.q[7].x;
-      const real di0 = r.q[2].w, di1 = r.q[3].w, di2 = r.q[4].w;
-      real s0 = l0 + (r.q[5].x - jd0 * di0);
-      s0 = max_(s0, r.q[0].w);
+      const real l0 = rec4<CR_LAM>(q), l1 = rec4<CR_LAM + 1>(q), l2 = rec4<CR_LAM + 2>(q);
+      const real di0 = rec4<CR_DINV0>(q), di1 = rec4<CR_DINV0 + CR_KSTRIDE>(q), di2 = rec4<CR_DINV0 + CR_KSTRIDE * 2>(q);
+      real s0 = l0 + (rec4<CR_RHS>(q) - jd0 * di0);
+      s0 = max_(s0, rec4<CR_LB>(q));
       real dl0 = s0 - l0;
-      if (CHECK) busy |= __ballot(absr(dl0) > r.q[7].y);
+      if (CHECK) busy |= __ballot(absr(dl0) > rec4<CR_THRESH>(q));
       real dl1 = 0, dl2 = 0, s1 = l1, s2 = l2;
       if (rdlane(s0, 32) > 0 || rdlane(mu, 32) < 0) {   // wave-uniform branch (Bullet skips the friction rows of an unloaded contact)
-        real hi = max_(mu * s0, r.q[1].x);
-        jd1 += r.q[5].w * dl0;
-        s1 = l1 + (r.q[5].y - jd1 * di1); s1 = med3_(s1, -hi, hi); dl1 = s1 - l1;
-        if (CHECK) busy |= __ballot(absr(dl1) > r.q[7].z);
-        jd2 += r.q[6].x * dl0 + r.q[6].y * dl1;
-        s2 = l2 + (r.q[5].z - jd2 * di2); s2 = med3_(s2, -hi, hi); dl2 = s2 - l2;
-        if (CHECK) busy |= __ballot(absr(dl2) > r.q[7].w);
+        real hi = max_(mu * s0, rec4<CR_FLOOR>(q));
+        jd1 += rec4<CR_G>(q) * dl0;
+        s1 = l1 + (rec4<CR_RHS + 1>(q) - jd1 * di1); s1 = med3_(s1, -hi, hi); dl1 = s1 - l1;
+        if (CHECK) busy |= __ballot(absr(dl1) > rec4<CR_THRESH + 1>(q));
+        jd2 += rec4<CR_G + 1>(q) * dl0 + rec4<CR_G + 2>(q) * dl1;
+        s2 = l2 + (rec4<CR_RHS + 2>(q) - jd2 * di2); s2 = med3_(s2, -hi, hi); dl2 = s2 - l2;
+        if (CHECK) busy |= __ballot(absr(dl2) > rec4<CR_THRESH + 2>(q));
       }
-      if (d == 32) { R[26] = s0; R[27] = s1; R[28] = s2; }
+      if (d == 32) { R[CR_LAM] = s0; R[CR_LAM + 1] = s1; R[CR_LAM + 2] = s2; }
       if (!in_lds) __threadfence_block();     // spilled records live in global memory: make lane 32's store visible to the wave
       du += w0 * rdlane(dl0, 32) + w1 * rdlane(dl1, 32) + w2 * rdlane(dl2, 32);
     };
@@ -1120,18 +1124,17 @@ PIH_HD int pgs(Wave& w, Shared& sh, const Params& P, const Ovf& ov, const MotorW
     if (nc > CL) {
       // the spilled contacts (global scratch) with the same one-ahead ping-pong: an env that gets here is one of the heaviest of
       // the launch, i.e. the one the launch ends up waiting for, and an unprefetched global load per contact is its latency
-      auto rec_of = [&](int c) { return ov.base + OVF_W_WORDS + (size_t)(c - CL) * CREC; };
       auto row_of = [&](int c) { return ov.base + (size_t)(3 * (c - CL)) * WPS; };
-      CRec ra = fetch(rec_of(CL), row_of(CL));
+      CRec ra = fetch(crec_spilled(ov, CL), row_of(CL));
       int c = CL;
       for (;;) {
         const int c1 = c + 1 < nc ? c + 1 : c;
-        CRec rb = fetch(rec_of(c1), row_of(c1));
-        block(c, c < 32 ? sg1 : sg2, ra, rec_of(c), false);
+        CRec rb = fetch(crec_spilled(ov, c1), row_of(c1));
+        block(c, c < 32 ? sg1 : sg2, ra, crec_spilled(ov, c), false);
         if (++c >= nc) break;
         const int c2 = c + 1 < nc ? c + 1 : c;
-        ra = fetch(rec_of(c2), row_of(c2));
-        block(c, c < 32 ? sg1 : sg2, rb, rec_of(c), false);
+        ra = fetch(crec_spilled(ov, c2), row_of(c2));
+        block(c, c < 32 ? sg1 : sg2, rb, crec_spilled(ov, c), false);
         if (++c >= nc) break;
       }
     }
@@ -1139,7 +1142,7 @@ PIH_HD int pgs(Wave& w, Shared& sh, const Params& P, const Ovf& ov, const MotorW
   };
   const int it = pgs_iteration_loop(P.iters, P.checkstride, [&]() __attribute__((always_inline)) { return iterate(std::true_type{}); }, [&]() __attribute__((always_inline)) { return iterate(std::false_type{}); });
   w.sync();
-  if (d < nc) { const real* R = d < CL ? sh.b.crec[d] : ov.base + OVF_W_WORDS + (size_t)(d - CL) * CREC; sh.r_lam[3 * d] = R[26]; sh.r_lam[3 * d + 1] = R[27]; sh.r_lam[3 * d + 2] = R[28]; }
+  if (d < nc) { const real* R = crec_of(sh, ov, d); sh.r_lam[3 * d] = R[CR_LAM]; sh.r_lam[3 * d + 1] = R[CR_LAM + 1]; sh.r_lam[3 * d + 2] = R[CR_LAM + 2]; }
   if (d < ND) sh.u[d] += du;
   w.sync();
   return it;

@@ -180,33 +180,33 @@ PIH_HD int pgs(Wave& w, Shared& sh, const Params& P, const Ovf& ov, const MotorW
     auto track = [&](real dl, real di) { real v = dl * dl - P.resid * di * di; if (v > worst) worst = v; };
     for (int m = 0; m < NMOT; m++) {
       int d = m < 9 ? m : 15 + (m - 9);
-      real dl = sh.mrec[m][1] - du[d] * sh.mrec[m][0], sum = mlam[m] + dl, lim = sh.mrec[m][3];
+      real dl = sh.mrec[m][MR_RHS] - du[d] * sh.mrec[m][MR_DINV], sum = mlam[m] + dl, lim = sh.mrec[m][MR_IMP];
       if (sum < -lim) { dl = -lim - mlam[m]; sum = -lim; } else if (sum > lim) { dl = lim - mlam[m]; sum = lim; }
       mlam[m] = sum;
       if (m < 9) for (int k = 0; k < 9; k++) du[k] += w.hWma[m][k] * dl; else for (int k = 0; k < 29; k++) du[9 + k] += w.hWmp[m - 9][k] * dl;
-      track(dl, sh.mrec[m][0]);
+      track(dl, sh.mrec[m][MR_DINV]);
       if (m < 9) for (int side = 0; side < 2; side++) {   // the joint's lower / upper limit rows follow its motor row
         int k = 2 * m + side; real sg = side ? (real)-1 : (real)1;
-        real dl2 = sh.lrec[m][side] - sg * du[m] * sh.mrec[m][0], sum2 = llam[k] + dl2;
+        real dl2 = sh.lrec[m][LR_LO + side] - sg * du[m] * sh.mrec[m][MR_DINV], sum2 = llam[k] + dl2;
         if (sum2 < 0) { dl2 = -llam[k]; sum2 = 0; }
         llam[k] = sum2;
         for (int j = 0; j < 9; j++) du[j] += sg * w.hWma[m][j] * dl2;
-        track(dl2, sh.mrec[m][0]);
+        track(dl2, sh.mrec[m][MR_DINV]);
       }
     }
     for (int c = 0; c < nc; c++) {
       const real* R = crec_of(sh, ov, c);
-      V3 p = ld3(R);
+      V3 p = ld3(R + CR_P);
       for (int k = 0; k < 3; k++) {
         int row = 3 * c + k;
         real lo = 0, hi = PIH_BIG;
-        if (R[5] < 0) lo = -PIH_BIG;                                   // bilateral (attach) rows
-        else if (k > 0) { real tot = sh.r_lam[3 * c]; if (!(tot > 0)) continue; hi = R[5] * tot; lo = -hi; }
-        V3 dir = ld3(R + 8 + 4 * k);
+        if (R[CR_MU] < 0) lo = -PIH_BIG;                                   // bilateral (attach) rows
+        else if (k > 0) { real tot = sh.r_lam[3 * c]; if (!(tot > 0)) continue; hi = R[CR_MU] * tot; lo = -hi; }
+        V3 dir = ld3(R + CR_DIR0 + CR_KSTRIDE * k);
         real jd = 0;
-        for (int d = 0; d < ND; d++) jd += jac_entry(geo[d], sh.c_la[c], sh.c_lb[c], p, dir, R[6] != 0) * du[d];
-        real di = R[11 + 4 * k];
-        real dl = R[20 + k] - jd * di, sum = sh.r_lam[row] + dl;
+        for (int d = 0; d < ND; d++) jd += jac_entry(geo[d], sh.c_la[c], sh.c_lb[c], p, dir, R[CR_ANG] != 0) * du[d];
+        real di = R[CR_DINV0 + CR_KSTRIDE * k];
+        real dl = R[CR_RHS + k] - jd * di, sum = sh.r_lam[row] + dl;
         if (sum < lo) { dl = lo - sh.r_lam[row]; sum = lo; } else if (sum > hi) { dl = hi - sh.r_lam[row]; sum = hi; }
         sh.r_lam[row] = sum;
         for (int d = 0; d < ND; d++) du[d] += Wrow(row, d) * dl;

@@ -43,12 +43,12 @@ class OracleBackend:
         if self.task_id == 1:
             return self.o.get_state()
         s = np.zeros((self.n, 256))
-        s[:, :128] = self.o.get_state()
+        s[:, :O.STATE_WORDS] = self.o.get_state()
         return s
 
     def ee_position(self):
         st = self.o.get_state()
-        return np.array([O.fk_arm(st[i, 0:9], 9)[0] + self.offsets[i] for i in range(self.n)])
+        return np.array([O.fk_arm(st[i, _lib.S_QARM : _lib.S_QDARM], 9)[0] + self.offsets[i] for i in range(self.n)])
 
     def tip_pose(self):
         return self.o.tip_pose()

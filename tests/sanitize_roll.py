@@ -9,6 +9,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from oracle import oracle as O            # noqa: E402
+from peg_in_hole_gym_amd import _lib  # noqa: E402
 from tests.emul import emul as E          # noqa: E402
 from tests.scenarios import coil_pipe_flat  # noqa: E402
 
@@ -28,8 +29,8 @@ n = 4
 o, e = sims(n, seed=3, auto_reset=1, max_episode_steps=150)
 for t in range(2 * steps):
     a = rng.uniform(-1, 1, (n, 4)); o.step(a); e.step(a)
-assert np.isfinite(o.get_state()).all() and np.isfinite(e.get_state()[:, :128]).all()
-print("action mode: %d steps x %d envs, contacts max %d / %d" % (2 * steps, n, o.ncontacts().max(), int(e.get_state()[:, 106].max())))
+assert np.isfinite(o.get_state()).all() and np.isfinite(e.get_state()[:, :O.STATE_WORDS]).all()
+print("action mode: %d steps x %d envs, contacts max %d / %d" % (2 * steps, n, o.ncontacts().max(), int(e.get_state()[:, _lib.S_NCONTACT].max())))
 
 # 2. pipes coiled flat on the table under a hovering arm: 25 table + up to ~17 self contacts (two rows per lane, DOF space beyond 32
 #    contacts, global-scratch spill beyond 20), then the scripted gripper coming down on the coil (weld / finger rows)
@@ -40,11 +41,11 @@ cmax = 0
 for kw, act, k in ((dict(seed=2), np.tile([p0[0], p0[1], p0[2], 0.0], (n, 1)), steps), (dict(seed=2, mode=1, dv=0.05), np.zeros((n, 4)), steps + 100)):
     o, e = sims(n, **kw)
     o.set_state(s8.copy())
-    se = e.get_state(); se[:, :98] = s8[:, :98]; se[:, 128] = 0; e.set_state(se)
+    se = e.get_state(); se[:, :_lib.S_TIP] = s8[:, :_lib.S_TIP]; se[:, _lib.S_CACHE_N] = 0; e.set_state(se)
     for t in range(k):
         o.step(act); e.step(act)
-        cmax = max(cmax, int(o.ncontacts().max()), int(e.get_state()[:, 106].max()))
-    assert np.isfinite(o.get_state()).all() and np.isfinite(e.get_state()[:, :128]).all()
+        cmax = max(cmax, int(o.ncontacts().max()), int(e.get_state()[:, _lib.S_NCONTACT].max()))
+    assert np.isfinite(o.get_state()).all() and np.isfinite(e.get_state()[:, :O.STATE_WORDS]).all()
 assert cmax > 32, cmax
 print("coiled pipe (hover + scripted gripper): up to %d contacts" % cmax)
 

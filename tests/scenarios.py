@@ -1,19 +1,21 @@
 """Shared constructed scenarios for the parity tests (test infrastructure)."""
 import numpy as np
 
+from peg_in_hole_gym_amd import _lib
+
 
 def coil_pipe_flat(s):
     """Lay every env's pipe flat on the table as a planar spiral (only the z-axis joints are bent, tighter for higher env
     indices): all 25 vertex spheres touch the table and the inner turns touch each other, so a step sees 25..~42 contacts,
     i.e. the > 20 (global-scratch spill) and > 32 (third sign word) contact paths of the HIP PGS.  `s`: oracle state
-    [n, >= 98] (modified in place and returned)."""
+    [n, >= S_TIP] (modified in place and returned)."""
     n = s.shape[0]
     for e in range(n):
-        s[e, 31:54] = 0
-        s[e, 31:54:2] = np.linspace(1.5, 0.5, 12) * (0.8 + 0.05 * (e % 8))
-        s[e, 20] = -0.04 + 1e-4
-        s[e, 25:31] = 0
-        s[e, 54:77] = 0
+        s[e, _lib.S_QJ : _lib.S_QDJ] = 0
+        s[e, _lib.S_QJ : _lib.S_QDJ : 2] = np.linspace(1.5, 0.5, 12) * (0.8 + 0.05 * (e % 8))
+        s[e, _lib.S_POS + 2] = -0.04 + 1e-4
+        s[e, _lib.S_VLIN : _lib.S_QJ] = 0
+        s[e, _lib.S_QDJ : _lib.S_TARGET] = 0
     return s
 
 

@@ -4,6 +4,7 @@ import numpy as np
 import pytest
 
 import peg_in_hole_gym_amd as pih
+from peg_in_hole_gym_amd import _lib
 from peg_in_hole_gym_amd.envs import BaseEnv, BaseEnvMp, TASK_LIST
 from peg_in_hole_gym_amd.envs.utils import (MPMultiAgentActionSpace, MultiAgentActionSpace, env_offsets, vel_constraint)
 from tests.oracle_backend import factory
@@ -98,14 +99,14 @@ def test_hard_reset_draws_a_new_scene_like_the_reference():
     scenes = []
     for _ in range(3):
         env.reset(hard_reset=True)
-        scenes.append(env._backend.state()[:, 18:20].copy())          # pipe base xy
+        scenes.append(env._backend.state()[:, _lib.S_POS : _lib.S_POS + 2].copy())          # pipe base xy
     assert not np.allclose(scenes[0], scenes[1]) and not np.allclose(scenes[1], scenes[2]) and not np.allclose(scenes[0], scenes[2])
     env.reset()                                                        # soft reset: a new scene as well
-    assert not np.allclose(env._backend.state()[:, 18:20], scenes[2])
+    assert not np.allclose(env._backend.state()[:, _lib.S_POS : _lib.S_POS + 2], scenes[2])
     # explicit replay is a separate, deliberate call: reseed -> the next reset restarts that seed's sequence
     env._backend.reseed(3); env.reset(hard_reset=True)
     first = BaseEnvMp(client=None, task="peg-in-hole", mp_num=2, sub_num=1, backend_factory=factory, seed=3)
-    np.testing.assert_array_equal(env._backend.state()[:, :98], first._backend.state()[:, :98])
+    np.testing.assert_array_equal(env._backend.state()[:, :_lib.S_TIP], first._backend.state()[:, :_lib.S_TIP])
 
 
 def test_type_errors_inside_a_backend_reset_propagate():

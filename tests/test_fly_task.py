@@ -149,9 +149,9 @@ def test_per_lane_algorithm_matches_oracle(oracle_mod, prec, obj):
         oo, ro, do = o.step(a); oe, re, de = e.step(a)
         so, se = o.get_state(), e.get_state()
         np.testing.assert_array_equal(do, de); np.testing.assert_array_equal(ro, re)
-        np.testing.assert_array_equal(so[:, 44], se[:, 44])
-        ncs += int(so[:, 44].sum())
-        perr.append(np.abs(so[:, :31] - se[:, :31]).max())
+        np.testing.assert_array_equal(so[:, _lib.F_NCONTACT], se[:, _lib.F_NCONTACT])
+        ncs += int(so[:, _lib.F_NCONTACT].sum())
+        perr.append(np.abs(so[:, :_lib.F_DONE] - se[:, :_lib.F_DONE]).max())
         np.testing.assert_allclose(oo, oe, atol=1e-9 if prec == "f64" else 2e-4)
     print(prec, "max one-step state error %.2e, contact env-steps %d" % (max(perr), ncs))
     assert ncs > 300
@@ -186,7 +186,7 @@ def test_arm_stops_at_the_table(oracle_mod):
                 if c[k, 0]:
                     assert g[1] == c[k, 1] == k - 9                                  # slot 2 NS + a holds arm link 1 + a
                     np.testing.assert_allclose(g[2:9], c[k, 2:9], atol=1e-9)
-        np.testing.assert_allclose(e.get_state()[0, :31], o.get_state()[0, :31], atol=5e-8)
+        np.testing.assert_allclose(e.get_state()[0, :_lib.F_DONE], o.get_state()[0, :_lib.F_DONE], atol=5e-8)
     st = o.get_state()[0]
     assert seen > 100 and st[O.F_CFORCE] > 1.0
     # lowest capsule end of the distal links: resting on the table top within the slop / one step of ERP
@@ -299,7 +299,7 @@ def test_fly_exit_cadence_host_build_matches_same_cadence_oracle(oracle_mod):
         it = e.get_debug()[:, _lib.DBG_FLY_PGS_ITERS].astype(int)
         live = dn == 0
         np.testing.assert_array_equal(it[live], B.pgs_iters()[live])
-        assert np.abs(e.get_state()[live][:, :31] - B.get_state()[live][:, :31]).max() < 5e-8      # (the fp64 bound of the one-step test above)
+        assert np.abs(e.get_state()[live][:, :_lib.F_DONE] - B.get_state()[live][:, :_lib.F_DONE]).max() < 5e-8      # (the fp64 bound of the one-step test above)
         dA.append((it - A.pgs_iters())[live]); early += int((B.pgs_iters()[live] < 50).sum())
     dA = np.concatenate(dA)
     assert early > 500 and dA.min() >= 0 and dA.max() <= 46 and (dA > 0).any()
@@ -323,12 +323,12 @@ def test_fly_quad_layout_host_build(oracle_mod, prec):
         oo, ro, do = o.step(act); oa, ra, da = a.step(act); ob, rb, db, bad = b.step_quad(act)
         assert bad == 0
         sa, sb, so = a.get_state(), b.get_state(), o.get_state()
-        np.testing.assert_array_equal(da, db); np.testing.assert_array_equal(ra, rb); np.testing.assert_array_equal(sa[:, 44], sb[:, 44])
+        np.testing.assert_array_equal(da, db); np.testing.assert_array_equal(ra, rb); np.testing.assert_array_equal(sa[:, _lib.F_NCONTACT], sb[:, _lib.F_NCONTACT])
         live = (do == 0) & (da == 0)
         ia, ib = a.get_debug()[:, _lib.DBG_FLY_PGS_ITERS], b.get_debug()[:, _lib.DBG_FLY_PGS_ITERS]
         its += int((ia[live] != ib[live]).sum())
-        ncs += int(sb[:, 44].sum())
-        err_l.append(np.abs(sa[live][:, :31] - sb[live][:, :31]).max(initial=0)); err_o.append(np.abs(so[live][:, :31] - sb[live][:, :31]).max(initial=0))
+        ncs += int(sb[:, _lib.F_NCONTACT].sum())
+        err_l.append(np.abs(sa[live][:, :_lib.F_DONE] - sb[live][:, :_lib.F_DONE]).max(initial=0)); err_o.append(np.abs(so[live][:, :_lib.F_DONE] - sb[live][:, :_lib.F_DONE]).max(initial=0))
         np.testing.assert_allclose(oa, ob, atol=1e-9 if prec == "f64" else 2e-4)
     print(prec, "quad vs lane layout max %.2e, quad vs oracle max %.2e median %.2e; contact env-steps %d; iteration counts differing %d" % (max(err_l), max(err_o), np.median(err_o), ncs, its))
     assert ncs > 100
@@ -353,11 +353,11 @@ def test_fly_quad_layout_more_contacts_than_register_records(oracle_mod):
         o.step(act); a.step(act); _, _, _, bad = b.step_quad(act)
         assert bad == 0
         sa, sb, so = a.get_state(), b.get_state(), o.get_state()
-        np.testing.assert_array_equal(sa[:, 44], sb[:, 44]); np.testing.assert_array_equal(sa[:, 44], so[:, 44])
-        big += int((sb[:, 44] > 8).sum())
+        np.testing.assert_array_equal(sa[:, _lib.F_NCONTACT], sb[:, _lib.F_NCONTACT]); np.testing.assert_array_equal(sa[:, _lib.F_NCONTACT], so[:, _lib.F_NCONTACT])
+        big += int((sb[:, _lib.F_NCONTACT] > 8).sum())
         np.testing.assert_array_equal(a.get_debug()[:, _lib.DBG_FLY_PGS_ITERS], b.get_debug()[:, _lib.DBG_FLY_PGS_ITERS])
-        assert np.abs(sa[:, :31] - sb[:, :31]).max() < 1e-9 and np.abs(so[:, :31] - sb[:, :31]).max() < 1e-6
-        assert np.abs(sa[:, 43] - sb[:, 43]).max() < 1e-6 * (1 + np.abs(sa[:, 43]).max())         # the summed normal force
+        assert np.abs(sa[:, :_lib.F_DONE] - sb[:, :_lib.F_DONE]).max() < 1e-9 and np.abs(so[:, :_lib.F_DONE] - sb[:, :_lib.F_DONE]).max() < 1e-6
+        assert np.abs(sa[:, _lib.F_CFORCE] - sb[:, _lib.F_CFORCE]).max() < 1e-6 * (1 + np.abs(sa[:, _lib.F_CFORCE]).max())         # the summed normal force
     assert big >= 30
 
 
@@ -375,7 +375,7 @@ def test_fly_limit_rows_speculation_is_exact(oracle_mod):
     for e in range(n):
         j = e % 6
         if e < 4:   s[e, j] = hi[j] - 0.2; s[e, 6 + j] = 3.0                     # (a) inside the band, moving into the limit
-        elif e < 8: s[e, 2] = lo[2] + 0.26 + 0.01 * (e - 4); s[e, 8] = -60.0           # (b) the elbow outside the band, reaches the limit within the step
+        elif e < 8: s[e, _lib.F_Q + 2] = lo[2] + 0.26 + 0.01 * (e - 4); s[e, _lib.F_QD + 2] = -60.0           # (b) the elbow outside the band, reaches the limit within the step
         else:       s[e, 6 + j] = 5.0                                            # (c) at the rest pose
     seen = set()
     for t in range(4):
@@ -389,9 +389,9 @@ def test_fly_limit_rows_speculation_is_exact(oracle_mod):
             assert (da[:4, _lib.DBG_FLY_LIMIT_ROWS] == 1).all() and (da[4:8, _lib.DBG_FLY_LIMIT_ROWS] == 2).all() and (da[8:, _lib.DBG_FLY_LIMIT_ROWS] == 0).all()
         seen |= set(da[:, _lib.DBG_FLY_LIMIT_ROWS].astype(int).tolist())
         sa, sb, so = a.get_state(), b.get_state(), o.get_state()
-        assert np.abs(sa[:, :31] - so[:, :31]).max() < 1e-9 * 100 and np.abs(sb[:, :31] - so[:, :31]).max() < 1e-9 * 100     # (velocities up to 100 rad/s)
+        assert np.abs(sa[:, :_lib.F_DONE] - so[:, :_lib.F_DONE]).max() < 1e-9 * 100 and np.abs(sb[:, :_lib.F_DONE] - so[:, :_lib.F_DONE]).max() < 1e-9 * 100     # (velocities up to 100 rad/s)
         np.testing.assert_array_equal(a.get_debug()[:, _lib.DBG_FLY_PGS_ITERS], o.pgs_iters())
         s = so
     assert seen == {0, 1, 2}
     # the limit did hold: no joint beyond its limit by more than the one-step overshoot the ERP removes
-    assert (s[:8, :6] <= hi + 0.05).all() and (s[:8, :6] >= lo - 0.05).all()
+    assert (s[:8, :_lib.F_QD] <= hi + 0.05).all() and (s[:8, :_lib.F_QD] >= lo - 0.05).all()

@@ -4,6 +4,8 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from peg_in_hole_gym_amd import _lib
+
 pytestmark = pytest.mark.gpu
 
 
@@ -28,14 +30,14 @@ def test_masked_reset_and_state_roundtrip(torch_mod):
     for _ in range(20):
         g.step(a)
     s1 = g.state().clone()
-    assert not torch.equal(s0[:, :86], s1[:, :86])
+    assert not torch.equal(s0[:, :_lib.S_FSM], s1[:, :_lib.S_FSM])
     mask = torch.zeros(n, dtype=torch.uint8, device="cuda"); mask[::3] = 1
     g.reset(mask)
     s2 = g.state()
     keep = mask == 0
     assert torch.equal(s2[keep], s1[keep])                                   # untouched envs keep their state bit for bit
-    assert (s2[mask == 1][:, 93] == 0).all() and (s2[mask == 1][:, 20] == 0.11).all()   # reset envs: step counter 0, spawn height
-    assert (s2[mask == 1][:, 92] > s1[mask == 1][:, 92]).all()               # RNG counter advanced: a NEW random scene
+    assert (s2[mask == 1][:, _lib.S_STEPS] == 0).all() and (s2[mask == 1][:, _lib.S_POS + 2] == 0.11).all()   # reset envs: step counter 0, spawn height
+    assert (s2[mask == 1][:, _lib.S_RNG] > s1[mask == 1][:, _lib.S_RNG]).all()               # RNG counter advanced: a NEW random scene
     g.set_state(s1)
     assert torch.equal(g.state(), s1)
 
@@ -53,20 +55,20 @@ def test_hard_reset_reseed_and_two_handles(torch_mod):
         a.step(act); b.step(act)                     # interleaved launches on two handles
     assert torch.equal(a.state(), b.state())
     a.reset()                                         # soft reset: a NEW scene (counter continues)
-    assert not torch.equal(a.state()[:, 18:20], first[:, 18:20])
+    assert not torch.equal(a.state()[:, _lib.S_POS : _lib.S_POS + 2], first[:, _lib.S_POS : _lib.S_POS + 2])
     second = a.state().clone()
     a.reset(hard_reset=True)                          # hard reset: again a NEW scene (an unmodified training loop sees fresh scenes)
     third = a.state().clone()
-    assert not torch.equal(third[:, 18:20], first[:, 18:20]) and not torch.equal(third[:, 18:20], second[:, 18:20])
-    assert (third[:, 92] > second[:, 92]).all()       # the draw counter kept advancing
+    assert not torch.equal(third[:, _lib.S_POS : _lib.S_POS + 2], first[:, _lib.S_POS : _lib.S_POS + 2]) and not torch.equal(third[:, _lib.S_POS : _lib.S_POS + 2], second[:, _lib.S_POS : _lib.S_POS + 2])
+    assert (third[:, _lib.S_RNG] > second[:, _lib.S_RNG]).all()       # the draw counter kept advancing
     a.reset(hard_reset=True, seed=4)                  # explicit replay: the seed's first scene again, bit for bit
-    assert torch.equal(a.state()[:, :98], first[:, :98])
+    assert torch.equal(a.state()[:, :_lib.S_TIP], first[:, :_lib.S_TIP])
     a.reset()
-    assert torch.equal(a.state()[:, :98], second[:, :98])      # ... and the same sequence after it
+    assert torch.equal(a.state()[:, :_lib.S_TIP], second[:, :_lib.S_TIP])      # ... and the same sequence after it
     a.reseed(77); a.reset(hard_reset=True)            # pih_reseed: new base seed, the next reset starts its sequence
     c = _gpu(n, seed=77)
-    assert torch.equal(a.state()[:, :98], c.state()[:, :98]) and not torch.equal(a.state()[:, 18:20], first[:, 18:20])
-    assert torch.equal(b.state()[:, 93], torch.full((n,), 5.0, device="cuda"))     # b was never touched by a's resets
+    assert torch.equal(a.state()[:, :_lib.S_TIP], c.state()[:, :_lib.S_TIP]) and not torch.equal(a.state()[:, _lib.S_POS : _lib.S_POS + 2], first[:, _lib.S_POS : _lib.S_POS + 2])
+    assert torch.equal(b.state()[:, _lib.S_STEPS], torch.full((n,), 5.0, device="cuda"))     # b was never touched by a's resets
 
 
 def test_non_finite_env_is_frozen_and_flagged(torch_mod):
@@ -75,17 +77,17 @@ def test_non_finite_env_is_frozen_and_flagged(torch_mod):
     torch = torch_mod
     n = 8
     g = _gpu(n, seed=1)
-    s = g.state().clone(); s[2, 18] = float("nan"); s[5, 31] = float("nan"); g.set_state(s)
+    s = g.state().clone(); s[2, _lib.S_POS] = float("nan"); s[5, _lib.S_QJ] = float("nan"); g.set_state(s)
     a = torch.zeros(n, 4, device="cuda")
     _, _, done = g.step(a)
     st = g.state()
     assert done.cpu().tolist() == [0, 0, 1, 0, 0, 1, 0, 0]
     assert torch.isfinite(st).all() and g.invalid().cpu().tolist() == [False, False, True, False, False, True, False, False]
-    assert (st[[2, 5], 97] == 1).all() and (st[[2, 5], 88] == 1).all()
+    assert (st[[2, 5], _lib.S_SPARE] == 1).all() and (st[[2, 5], _lib.S_DONE] == 1).all()
     frozen = st[[2, 5]].clone()
     for _ in range(3):
         _, _, done = g.step(a)
-    assert torch.equal(g.state()[[2, 5], :98], frozen[:, :98]) and done[[2, 5]].all()
+    assert torch.equal(g.state()[[2, 5], :_lib.S_TIP], frozen[:, :_lib.S_TIP]) and done[[2, 5]].all()
     g.reset()
     assert not g.invalid().any()
 
@@ -103,7 +105,6 @@ def test_step_n_equals_repeated_step(torch_mod):
 
 
 def test_error_paths(torch_mod):
-    from peg_in_hole_gym_amd import _lib
     L = _lib.load()
     g = _gpu(4)
     assert L.pih_step(g.h, None, None, None, None, None) != 0               # action mode needs actions
@@ -131,8 +132,8 @@ def test_timing_api_and_obs_fields(torch_mod):
     assert g.timing()[1] == 1100
     torch.cuda.synchronize()
     st = g.state()
-    assert torch.allclose(obs[:, 2:5], g.ee_position()) and torch.allclose(obs[:, 0:2], st[:, 7:9])
-    assert torch.equal(g.tip_pose(), st[:, 98:105]) and torch.equal(g.contact_force(), st[:, 105])
+    assert torch.allclose(obs[:, 2:5], g.ee_position()) and torch.allclose(obs[:, 0:2], st[:, _lib.S_QARM + 7 : _lib.S_QDARM])
+    assert torch.equal(g.tip_pose(), st[:, _lib.S_TIP : _lib.S_CFORCE]) and torch.equal(g.contact_force(), st[:, _lib.S_CFORCE])
     assert ((rew == 0) | (rew == 1)).all() and ((done == 0) | (done == 1)).all()
 
 
@@ -182,7 +183,7 @@ def test_results_do_not_depend_on_batch_size_or_dispatch_order(torch_mod):
         oa, ra, da = a.step(acts[t]); ob, rb, db = b.step(acts[t, :37].contiguous()); oc, rc, dc = c.step(acts[t])
         assert torch.equal(oa[:37], ob) and torch.equal(da[:37], db) and torch.equal(oa, oc)
     assert torch.equal(a.state()[:37], b.state()) and torch.equal(a.state(), c.state())
-    assert int(a.state()[:, 93].max()) <= 40                                   # episodes were cut and auto-reset at 40 steps
+    assert int(a.state()[:, _lib.S_STEPS].max()) <= 40                                   # episodes were cut and auto-reset at 40 steps
 
 
 def test_scripted_facade_on_gpu(torch_mod):
@@ -230,7 +231,6 @@ def test_state_dict_round_trip_resumes_bit_for_bit(torch_mod, tmp_path):
     bit for bit, including the scenes later auto-resets draw (RNG counters are part of the record); a checkpoint of another config or
     seed is refused."""
     torch = torch_mod
-    from peg_in_hole_gym_amd import _lib
     from peg_in_hole_gym_amd.vec_env import PihVecEnv
     n = 70
     kw = dict(seed=6, auto_reset=1, max_episode_steps=30)
@@ -261,7 +261,6 @@ def test_new_seed_needs_a_full_reset(torch_mod):
     """pih_reset(seed != 0) / a pending pih_reseed with a MASK would leave the unmasked envs on another seed's stream ->
     rejected (-2) and nothing changes; the unmasked form works as before."""
     torch = torch_mod
-    from peg_in_hole_gym_amd import _lib
     n = 9
     g = _gpu(n, seed=4)
     s0 = g.state().clone()
@@ -273,10 +272,10 @@ def test_new_seed_needs_a_full_reset(torch_mod):
     with pytest.raises(_lib.PihError, match="reset of all envs"):
         g.reset(mask)
     g.reset()                                                  # consumes the pending reseed: seed 5's first scene
-    assert torch.equal(g.state()[:, :98], _gpu(n, seed=5).state()[:, :98])
-    before = g.state()[:, 92].clone()
+    assert torch.equal(g.state()[:, :_lib.S_TIP], _gpu(n, seed=5).state()[:, :_lib.S_TIP])
+    before = g.state()[:, _lib.S_RNG].clone()
     g.reset(mask)                                              # masked resets are fine again afterwards: the masked envs draw on, the others rest
-    after = g.state()[:, 92]
+    after = g.state()[:, _lib.S_RNG]
     assert (after[mask == 1] > before[mask == 1]).all() and torch.equal(after[mask == 0], before[mask == 0])
 
 
@@ -290,7 +289,7 @@ def test_roctx_ranges_do_not_disturb_the_step(torch_mod):
         a.step(act); b.step(act)
     a.reset(); b.reset()
     a.step(act); b.step(act)
-    assert torch.equal(a.state()[:, :128], b.state()[:, :128])
+    assert torch.equal(a.state()[:, :_lib.S_CACHE_N], b.state()[:, :_lib.S_CACHE_N])
 
 
 @pytest.mark.parametrize("mode,n,steps", [(0, 2500, 150), (1, 2500, 150), (0, 16384, 40)])
@@ -311,4 +310,4 @@ def test_fused_launch_equals_the_two_launch_step(torch_mod, mode, n, steps):
             assert torch.equal(x, y) and torch.equal(x, z), "step %d" % t
     assert torch.equal(a.state(), b.state()) and torch.equal(a.state(), c.state())
     a.set_timing(1); a.step(act); a.timing2()                 # timing2 also reports a controller time-out of the fused launch (-5): none
-    assert int(a.state()[:, 106].max().item()) > (10 if steps >= 100 else 3)
+    assert int(a.state()[:, _lib.S_NCONTACT].max().item()) > (10 if steps >= 100 else 3)

@@ -17,6 +17,8 @@ import sys
 import numpy as np
 import pytest
 
+from peg_in_hole_gym_amd import _lib
+
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -48,9 +50,9 @@ def test_eight_blocks_of_2048_equal_one_handle_of_16384():
     # everything an env owns: 98 physical words, derived outputs, warm-start cache (bitwise; NaN-free by the finite check)
     assert torch.isfinite(sb).all()
     assert torch.equal(sb, sp)
-    assert int(sb[:, 106].max().item()) > 10          # (heavy envs took the two-rows-per-lane solver with its per-env scratch)
+    assert int(sb[:, _lib.S_NCONTACT].max().item()) > 10          # (heavy envs took the two-rows-per-lane solver with its per-env scratch)
     print("config 3 partition: 8 x 2048 == 1 x 16384 bit for bit over %d steps (%d env-steps, every env re-drawn once at step 40), contacts mean %.1f max %d" % (
-        steps, steps * total, float(sb[:, 106].mean().item()), int(sb[:, 106].max().item())))
+        steps, steps * total, float(sb[:, _lib.S_NCONTACT].mean().item()), int(sb[:, _lib.S_NCONTACT].max().item())))
 
 
 _RCCL_WORKER = r"""

@@ -31,17 +31,17 @@ def test_fly_reset_and_state_roundtrip(torch_mod, oracle_mod):
     assert sg.shape == (n, 48)
     np.testing.assert_allclose(sg, o.get_state(), atol=2e-6)
     assert g.obs.shape == (n, 6)
-    np.testing.assert_allclose(g.ee_position().cpu().numpy(), sg[:, 40:43], atol=0)
-    s2 = torch.tensor(sg) + 0.0; s2[:, 18] += 0.25
+    np.testing.assert_allclose(g.ee_position().cpu().numpy(), sg[:, _lib.F_EE : _lib.F_CFORCE], atol=0)
+    s2 = torch.tensor(sg) + 0.0; s2[:, _lib.F_OPOS] += 0.25
     g.set_state(s2)
     assert torch.equal(g.state().cpu(), s2)                        # env-major <-> structure-of-arrays transposition is exact
     mask = torch.zeros(n, dtype=torch.uint8); mask[::4] = 1
     g.reset(mask)
     s3 = g.state().cpu()
-    assert torch.equal(s3[mask == 0], s2[mask == 0]) and (s3[mask == 1][:, 33] > s2[mask == 1][:, 33]).all()
+    assert torch.equal(s3[mask == 0], s2[mask == 0]) and (s3[mask == 1][:, _lib.F_RNG] > s2[mask == 1][:, _lib.F_RNG]).all()
     g.reset(hard_reset=True)
     s4 = g.state().cpu()
-    assert not torch.equal(s4[:, 18:21], torch.tensor(sg)[:, 18:21]) and (s4[:, 33] > s3[:, 33]).all()   # hard reset: a NEW scene (draw counter advances)
+    assert not torch.equal(s4[:, _lib.F_OPOS : _lib.F_OQUAT], torch.tensor(sg)[:, _lib.F_OPOS : _lib.F_OQUAT]) and (s4[:, _lib.F_RNG] > s3[:, _lib.F_RNG]).all()   # hard reset: a NEW scene (draw counter advances)
     g.reset(hard_reset=True, seed=int(g.cfg.seed))
     np.testing.assert_array_equal(g.state().cpu().numpy(), sg)   # explicit replay (seed != 0): the seed's first scene bit for bit
 
@@ -70,18 +70,18 @@ def test_fly_one_step_parity_resynchronised(torch_mod, oracle_mod, N, steps, obj
         so = o.get_state(); sg = g.state().cpu().numpy().astype(np.float64)
         # an env whose object passes within float rounding of a contact / catch / landing threshold, or whose sphere is equally deep
         # in two neighbouring capsules, takes a different discrete branch than the oracle: counted, bounded, and left out of the stats
-        same = (do == dg.cpu().numpy()) & (so[:, 44] == sg[:, 44]) & (ro == rg.cpu().numpy())
+        same = (do == dg.cpu().numpy()) & (so[:, _lib.F_NCONTACT] == sg[:, _lib.F_NCONTACT]) & (ro == rg.cpu().numpy())
         mism += int((~same).sum())
-        ncs += int(so[:, 44].sum()); nrew += int(ro.sum())
+        ncs += int(so[:, _lib.F_NCONTACT].sum()); nrew += int(ro.sum())
         perr.append(np.abs(so[same][:, [*range(0, 6), *range(18, 25)]] - sg[same][:, [*range(0, 6), *range(18, 25)]]).max(1))
-        verr.append(np.abs(so[same][:, [*range(6, 12), *range(25, 31)]] - sg[same][:, [*range(6, 12), *range(25, 31)]]).max(1))
-        ferr.append(np.abs(so[same][:, 43] - sg[same][:, 43]) / (1 + np.abs(so[same][:, 43])))
+        verr.append(np.abs(so[same][:, [*range(_lib.F_QD, _lib.F_TARGET), *range(_lib.F_OVLIN, _lib.F_DONE)]] - sg[same][:, [*range(_lib.F_QD, _lib.F_TARGET), *range(_lib.F_OVLIN, _lib.F_DONE)]]).max(1))
+        ferr.append(np.abs(so[same][:, _lib.F_CFORCE] - sg[same][:, _lib.F_CFORCE]) / (1 + np.abs(so[same][:, _lib.F_CFORCE])))
         # every env-step that took the oracle's branch and did not finish (a finished env is reset inside the step) goes into the ledger:
         # error = position words, and the velocity error over one dt
-        PW = [*range(0, 6), *range(18, 25)]; VW = [*range(6, 12), *range(25, 31)]
+        PW = [*range(_lib.F_Q, _lib.F_QD), *range(_lib.F_OPOS, _lib.F_OVLIN)]; VW = [*range(_lib.F_QD, _lib.F_TARGET), *range(_lib.F_OVLIN, _lib.F_DONE)]
         live = same & (do == 0)
         e_all = np.maximum(np.abs(so[:, PW] - sg[:, PW]).max(1), DT * np.abs(so[:, VW] - sg[:, VW]).max(1))
-        led.after(o, a, np.where(live, e_all, 0.0), np.where(live, np.abs(so[:, 43] - sg[:, 43]) / (1 + np.abs(so[:, 43])), 0.0))
+        led.after(o, a, np.where(live, e_all, 0.0), np.where(live, np.abs(so[:, _lib.F_CFORCE] - sg[:, _lib.F_CFORCE]) / (1 + np.abs(so[:, _lib.F_CFORCE])), 0.0))
         oerr = np.abs(og.cpu().numpy() - oo).max(1)
         assert oerr[same & (e_all < 1e-4)].max() < 2e-4            # the observation follows the state
     led.finish("fly one-step resynchronised N=%d object %d" % (N, obj), p50=2e-6, p99=2e-5, exempt_share=0.02)
@@ -118,8 +118,8 @@ def test_fly_free_flight_trajectory_and_arm_tracking(torch_mod, oracle_mod):
     sg = g.state().cpu().numpy()
     print("fly trajectory parity: obs max diff %.2e over 300 steps" % md)
     assert md < 1e-3
-    np.testing.assert_allclose(sg[:, 18:21], np.tile(p, (N, 1)), atol=2e-3)        # closed-form damped flight (fp32 accumulation over 300 steps at z ~ 40)
-    np.testing.assert_allclose(sg[:, 25:28], np.tile(v, (N, 1)), atol=2e-4)
+    np.testing.assert_allclose(sg[:, _lib.F_OPOS : _lib.F_OQUAT], np.tile(p, (N, 1)), atol=2e-3)        # closed-form damped flight (fp32 accumulation over 300 steps at z ~ 40)
+    np.testing.assert_allclose(sg[:, _lib.F_OVLIN : _lib.F_OVANG], np.tile(v, (N, 1)), atol=2e-4)
 
 
 def test_fly_full_size_properties(torch_mod):
@@ -139,10 +139,10 @@ def test_fly_full_size_properties(torch_mod):
         st = g.state()
         outs.append(st.clone())
         assert torch.isfinite(st).all() and torch.isfinite(obs).all()
-        assert torch.allclose(st[:, 21:25].norm(dim=1), torch.ones(N, device="cuda"), atol=1e-4)
-        assert (st[:, 0:6].abs() <= 3.14159265359 + 0.05).all()
-        assert ndone > 2 * N and st[:, 38].sum().item() == 0          # every env finished > 2 episodes; no non-finite resets
-        assert (st[:, 32] < 300).all()
+        assert torch.allclose(st[:, _lib.F_OQUAT : _lib.F_OVLIN].norm(dim=1), torch.ones(N, device="cuda"), atol=1e-4)
+        assert (st[:, _lib.F_Q : _lib.F_QD].abs() <= 3.14159265359 + 0.05).all()
+        assert ndone > 2 * N and st[:, _lib.F_SPARE].sum().item() == 0          # every env finished > 2 episodes; no non-finite resets
+        assert (st[:, _lib.F_STEPS] < 300).all()
     assert torch.equal(outs[0], outs[1])
     gen = torch.Generator(device="cuda").manual_seed(5)
     acts = torch.rand(40, 130, 6, device="cuda", generator=gen) * 2 - 1
@@ -223,8 +223,8 @@ def test_fly_quad_layout_against_lane_layout(n):
         b.set_state(a.state())
         oa, ra, da = [x.clone() for x in a.step(act)]; ob, rb, db = b.step(act)
         sa, sb = a.state(), b.state()
-        same = (da == db) & (ra == rb) & (sa[:, 44] == sb[:, 44])
-        flips += int((~same).sum()); ncs += int(sa[:, 44].sum())
+        same = (da == db) & (ra == rb) & (sa[:, _lib.F_NCONTACT] == sb[:, _lib.F_NCONTACT])
+        flips += int((~same).sum()); ncs += int(sa[:, _lib.F_NCONTACT].sum())
         live = same & (da == 0)
         errs.append((sa[live][:, PV] - sb[live][:, PV]).abs().max(1).values.cpu())
         if kw["debug"]:
@@ -254,10 +254,10 @@ def test_fly_quad_layout_more_contacts_than_register_records(torch_mod, oracle_m
         o.set_state(s); a.set_state(torch.tensor(s, dtype=torch.float32)); b.set_state(torch.tensor(s, dtype=torch.float32))
         o.step(act); a.step(torch.tensor(act, dtype=torch.float32)); b.step(torch.tensor(act, dtype=torch.float32))
         sa = a.state().cpu().numpy().astype(np.float64); sb = b.state().cpu().numpy().astype(np.float64); so = o.get_state()
-        same = (sa[:, 44] == so[:, 44]) & (sb[:, 44] == so[:, 44])
+        same = (sa[:, _lib.F_NCONTACT] == so[:, _lib.F_NCONTACT]) & (sb[:, _lib.F_NCONTACT] == so[:, _lib.F_NCONTACT])
         assert (~same).sum() <= 2                               # (a contact within float rounding of the margin)
-        big += int((sa[:, 44] > 8).sum())
-        eo.append(np.abs(sa[same][:, :31] - so[same][:, :31]).max(1)); el.append(np.abs(sa[same][:, :31] - sb[same][:, :31]).max(1))
+        big += int((sa[:, _lib.F_NCONTACT] > 8).sum())
+        eo.append(np.abs(sa[same][:, :_lib.F_DONE] - so[same][:, :_lib.F_DONE]).max(1)); el.append(np.abs(sa[same][:, :_lib.F_DONE] - sb[same][:, :_lib.F_DONE]).max(1))
         s = so
     eo, el = np.concatenate(eo), np.concatenate(el)
     print("   many-contact states: %d env-steps with > 8 contacts; quad layout vs oracle p50 / p99 / max %.2e / %.2e / %.2e; vs lane layout %.2e / %.2e / %.2e" % (
@@ -283,7 +283,7 @@ def test_fly_limit_rows_speculation_is_exact(torch_mod, oracle_mod, sched):
     for e in range(n):
         j = e % 6
         if e < per:        s[e, j] = np.pi - 0.2; s[e, 6 + j] = 3.0
-        elif e < 2 * per and e % 4 == 0: s[e, 2] = -np.pi + 0.26 + 0.01 * (e % 3); s[e, 8] = -60.0
+        elif e < 2 * per and e % 4 == 0: s[e, _lib.F_Q + 2] = -np.pi + 0.26 + 0.01 * (e % 3); s[e, _lib.F_QD + 2] = -60.0
         elif e >= 2 * per: s[e, 6 + j] = 5.0
     act = np.zeros((n, 6)); act[:, :3] = [0.3, 0.1, 0.4]
     for t in range(3):
@@ -293,9 +293,9 @@ def test_fly_limit_rows_speculation_is_exact(torch_mod, oracle_mod, sched):
         if t == 0:
             assert (d[:per, _lib.DBG_FLY_LIMIT_ROWS] == 1).all() and (d[per:2 * per, _lib.DBG_FLY_LIMIT_ROWS] == 2).all() and (d[2 * per:, _lib.DBG_FLY_LIMIT_ROWS] == 0).all(), d[:, _lib.DBG_FLY_LIMIT_ROWS]
         assert (d[:, _lib.DBG_FLY_PGS_ITERS] == o.pgs_iters()).mean() > 0.97
-        assert np.abs(sg[:, :6] - so[:, :6]).max() < 2e-4 and np.abs(sg[:, 6:12] - so[:, 6:12]).max() < 2e-2       # (velocities up to 100 rad/s in float)
+        assert np.abs(sg[:, :_lib.F_QD] - so[:, :_lib.F_QD]).max() < 2e-4 and np.abs(sg[:, _lib.F_QD : _lib.F_TARGET] - so[:, _lib.F_QD : _lib.F_TARGET]).max() < 2e-2       # (velocities up to 100 rad/s in float)
         s = so
-    assert (s[:, :6] <= np.pi + 0.05).all() and (s[:, :6] >= -np.pi - 0.05).all()
+    assert (s[:, :_lib.F_QD] <= np.pi + 0.05).all() and (s[:, :_lib.F_QD] >= -np.pi - 0.05).all()
 
 
 def test_fly_defaults_exit_test_and_cadence(torch_mod, oracle_mod):
@@ -314,7 +314,7 @@ def test_fly_defaults_exit_test_and_cadence(torch_mod, oracle_mod):
     pk = dict(kw); pk["auto_reset"] = 0; pk["exit_check_stride"] = 16
     led = P.ConditionedParity(oracle_mod, task="random-fly", slots=256, **pk)
     rng = np.random.default_rng(3)
-    PW = [*range(0, 6), *range(18, 25)]; VW = [*range(6, 12), *range(25, 31)]
+    PW = [*range(_lib.F_Q, _lib.F_QD), *range(_lib.F_OPOS, _lib.F_OVLIN)]; VW = [*range(_lib.F_QD, _lib.F_TARGET), *range(_lib.F_OVLIN, _lib.F_DONE)]
     dA, dB, itB = [], [], []
     for t in range(steps):
         a = rng.uniform(-1, 1, (N, 6))
@@ -322,7 +322,7 @@ def test_fly_defaults_exit_test_and_cadence(torch_mod, oracle_mod):
         A.step(a); _, rB, dnB = B.step(a)
         _, rg, dg = g.step(torch.tensor(a, dtype=torch.float32))
         so = B.get_state(); sg = g.state().cpu().numpy().astype(np.float64)
-        same = (dnB == dg.cpu().numpy()) & (so[:, 44] == sg[:, 44]) & (rB == rg.cpu().numpy())
+        same = (dnB == dg.cpu().numpy()) & (so[:, _lib.F_NCONTACT] == sg[:, _lib.F_NCONTACT]) & (rB == rg.cpu().numpy())
         live = same & (dnB == 0)
         e_all = np.maximum(np.abs(so[:, PW] - sg[:, PW]).max(1), DT * np.abs(so[:, VW] - sg[:, VW]).max(1))
         led.after(B, a, np.where(live, e_all, 0.0))

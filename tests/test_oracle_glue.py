@@ -1,6 +1,8 @@
 """Oracle vs the golden vectors produced by the reference's own pure-Python glue (tests/golden/make_glue_golden.py)."""
 import numpy as np
 
+from peg_in_hole_gym_amd import _lib
+
 
 def test_vel_constraint(golden, oracle_mod):
     for c in golden["vel_constraint"]:
@@ -49,16 +51,16 @@ def test_reset_matches_reference_structure(golden, oracle_mod):
     o = oracle_mod.Oracle(256)
     s = o.get_state()
     from oracle.oracle import Config  # noqa: F401
-    assert np.all((s[:, 18] >= -0.2) & (s[:, 18] <= 0.2)) and np.all((s[:, 19] >= -0.6) & (s[:, 19] <= -0.4)) and np.all(s[:, 20] == 0.11)
-    qj = s[:, 31:54]
+    assert np.all((s[:, _lib.S_POS] >= -0.2) & (s[:, _lib.S_POS] <= 0.2)) and np.all((s[:, _lib.S_POS + 1] >= -0.6) & (s[:, _lib.S_POS + 1] <= -0.4)) and np.all(s[:, _lib.S_POS + 2] == 0.11)
+    qj = s[:, _lib.S_QJ : _lib.S_QDJ]
     assert np.all((qj >= 0) & (qj <= np.pi / 3))
     nz = (qj != 0).sum(1)
     assert nz.min() >= 4 and nz.max() <= 23          # k in [5,24] draws over 24 indices, index 0 is the fixed joint
-    assert set(np.unique(s[:, 89])) <= {0.0, 23.0} and len(np.unique(s[:, 89])) == 2
-    assert np.all(np.abs(s[:, 90]) <= 0.03)
-    np.testing.assert_allclose(s[:, 0:9], np.tile([0, -0.215, -np.pi / 3, -2.57, 0, 2.356, 2.356, 0, 0], (256, 1)))
+    assert set(np.unique(s[:, _lib.S_GRASP])) <= {0.0, 23.0} and len(np.unique(s[:, _lib.S_GRASP])) == 2
+    assert np.all(np.abs(s[:, _lib.S_RANDY]) <= 0.03)
+    np.testing.assert_allclose(s[:, _lib.S_QARM : _lib.S_QDARM], np.tile([0, -0.215, -np.pi / 3, -2.57, 0, 2.356, 2.356, 0, 0], (256, 1)))
     # per-env streams differ, and the same seed reproduces
-    assert len(np.unique(s[:, 18])) == 256
+    assert len(np.unique(s[:, _lib.S_POS])) == 256
     np.testing.assert_array_equal(oracle_mod.Oracle(256).get_state(), s)
 
 

@@ -7,6 +7,8 @@ value per object, optionally shaded with the ambient + diffuse terms of TinyRend
 import numpy as np
 import pytest
 
+from peg_in_hole_gym_amd import _lib
+
 NEAR, FAR = 0.001, 1000.0
 TABLE_Z = -0.05
 
@@ -21,9 +23,9 @@ def test_depth_of_bare_table_is_the_closed_form(oracle_mod):
     for _ in range(540):                          # gripper hovering above the grasp point, pointing straight down
         o.step(np.zeros((1, 4)))
     s = o.get_state()
-    s[0, 18] = 5.0                                # move the pipe out of view
+    s[0, _lib.S_POS] = 5.0                                # move the pipe out of view
     o.set_state(s)
-    ee = O.fk_arm(s[0, 0:9], 9)[0]
+    ee = O.fk_arm(s[0, _lib.S_QARM : _lib.S_QDARM], 9)[0]
     img = o.render(40, 30)[0]
     assert img.shape == (30, 40, 4)
     # a plane perpendicular to the view axis has ONE depth-buffer value: gl_depth(eye.z - table.z); the finger pads sit
@@ -33,10 +35,10 @@ def test_depth_of_bare_table_is_the_closed_form(oracle_mod):
     # near-plane clipping: at the rest pose the fingers are closed and the eye (the grasp target) lies ON the faces of both
     # pads; their hits at ray parameter ~0 are in front of the near plane and must not be drawn (they gave depth << 0)
     o2 = O.Oracle(1)
-    s2 = o2.get_state(); s2[0, 18] = 5.0; o2.set_state(s2)
+    s2 = o2.get_state(); s2[0, _lib.S_POS] = 5.0; o2.set_state(s2)
     img2 = o2.render(40, 30)[0]
     assert (img2[:, :, 0] > 0.9).all() and (img2[:, :, 0] <= 1.0).all()
-    ee2 = O.fk_arm(s2[0, 0:9], 9)[0]
+    ee2 = O.fk_arm(s2[0, _lib.S_QARM : _lib.S_QDARM], 9)[0]
     assert np.allclose(img2[:, :, 0], gl_depth(ee2[2] - TABLE_Z), atol=1e-12) and (img2[:, :, 1] == 153.0).all()
 
 
@@ -48,7 +50,7 @@ def test_pipe_silhouette_and_depth_bounds(oracle_mod):
     s = o.get_state()
     img = o.render(120, 120)
     for e in range(2):
-        ee = O.fk_arm(s[e, 0:9], 9)[0]
+        ee = O.fk_arm(s[e, _lib.S_QARM : _lib.S_QDARM], 9)[0]
         pipe = img[e, :, :, 1] == 232.0
         assert pipe.sum() > 200                                   # the hovering gripper looks down at the pipe
         z = NEAR * FAR / (FAR - img[e, :, :, 0] * (FAR - NEAR))   # linearised eye depth
@@ -108,7 +110,7 @@ def test_hip_shaded_render_matches_oracle():
     g = PihVecEnv(n, mode=1, dv=0.05, seed=4)
     g.step_n(540)
     o = O.Oracle(n, mode=1, dv=0.05, seed=4)
-    o.set_state(g.state().cpu().numpy()[:, :128].astype(np.float64))
+    o.set_state(g.state().cpu().numpy()[:, :O.STATE_WORDS].astype(np.float64))
     a = g.render(200, 160, shaded=True).cpu().numpy(); b = o.render(200, 160, shaded=True)
     af = g.render(200, 160).cpu().numpy(); bf = o.render(200, 160)
     assert np.array_equal(a[..., 0], af[..., 0])                                 # shading does not touch the depth buffer
@@ -129,7 +131,7 @@ def test_hip_render_matches_oracle():
     g.step_n(540)
     st = g.state().cpu().numpy()
     o = O.Oracle(n, mode=1, dv=0.05, seed=4)
-    o.set_state(st[:, :128].astype(np.float64))
+    o.set_state(st[:, :O.STATE_WORDS].astype(np.float64))
     for (W, H) in ((300, 300), (97, 61)):
         a = g.render(W, H).cpu().numpy()
         b = o.render(W, H)
@@ -143,7 +145,7 @@ def test_hip_render_matches_oracle():
         assert (a[..., 1] == 232.0).any()
     # rest pose (fingers closed: the eye lies on the pad faces, their t ~ 0 hits are clipped by the near plane)
     g0 = PihVecEnv(3, seed=7); o0 = O.Oracle(3, seed=7)
-    o0.set_state(g0.state().cpu().numpy()[:, :128].astype(np.float64))
+    o0.set_state(g0.state().cpu().numpy()[:, :O.STATE_WORDS].astype(np.float64))
     a0 = g0.render(64, 48).cpu().numpy(); b0 = o0.render(64, 48)
     assert (a0[..., 0] > 0.9).all() and (a0[..., 0] <= 1.0).all()
     assert (a0[..., 1] == b0[..., 1]).mean() > 0.997 and np.abs(a0[..., 0] - b0[..., 0])[a0[..., 1] == b0[..., 1]].max() < 2e-6
@@ -154,7 +156,7 @@ def test_hip_render_matches_oracle():
     g.step_n(1)
     lab, meta = g.grasp_labels(300)
     lab = lab.cpu().numpy(); meta = meta.cpu().numpy()
-    ang = g.state()[:, 111].cpu().numpy().astype(np.float64)
+    ang = g.state()[:, _lib.S_GRASP_ANGLE].cpu().numpy().astype(np.float64)
     assert (ang != 0).all()
     for e in range(n):
         lo, mo = O.grasp_labels(ang[e], 300)

@@ -15,6 +15,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
 from tests.emul import emul as E  # noqa: E402
+from peg_in_hole_gym_amd import _lib  # noqa: E402
 
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 96
 pre = int(sys.argv[2]) if len(sys.argv) > 2 else 400
@@ -35,7 +36,7 @@ L.emul_flops_reset()
 contacts = []
 for t in range(steps):
     c.step(rng.uniform(-1, 1, (n, 4)))
-    contacts.append(c.get_state()[:, 106].mean())
+    contacts.append(c.get_state()[:, _lib.S_NCONTACT].mean())
 ph = (C.c_ulonglong * 96)(); tot = (C.c_ulonglong * 6)()
 L.emul_flops_get(ph, tot)
 ph = np.array(ph[:], dtype=np.float64).reshape(16, 6); tot = np.array(tot[:], dtype=np.float64)

@@ -26,7 +26,7 @@ for name, sched in (("quad, limit rows speculated", 1), ("quad, every limit row"
     # B: arm poses lying on the table (0 .. 5 arm contacts)
     rng = np.random.default_rng(0)
     sb = s.clone().cpu().numpy()
-    sb[:, 0] = rng.uniform(-3, 3, n); sb[:, 1] = rng.uniform(-0.3, 0.3, n); sb[:, 2] = rng.uniform(-0.5, 0.5, n)
+    sb[:, _lib.F_Q] = rng.uniform(-3, 3, n); sb[:, _lib.F_Q + 1] = rng.uniform(-0.3, 0.3, n); sb[:, _lib.F_Q + 2] = rng.uniform(-0.5, 0.5, n)
     for k in (3, 4, 5):
         sb[:, k] = rng.uniform(-3, 3, n)
     env.set_state(torch.tensor(sb, dtype=torch.float32)); env.step(act); torch.cuda.synchronize()

@@ -20,9 +20,10 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from oracle import oracle as O            # noqa: E402  (test infrastructure)
+from peg_in_hole_gym_amd import _lib  # noqa: E402
 
 AMP, K, MAGS = 30.0, 4, (1e-6, 1e-5)
-POS = [*range(0, 9), *range(18, 25), *range(31, 54)]
+POS = [*range(_lib.S_QARM, _lib.S_QDARM), *range(_lib.S_POS, _lib.S_VLIN), *range(_lib.S_QJ, _lib.S_QDJ)]
 
 
 def features(o, prev_cnt):
@@ -68,7 +69,7 @@ def rollout(N, steps, variant, seed=5, collect=True):
                 feats.setdefault(k, np.zeros((steps, N), dtype=bool))[t] = v
         for mag in MAGS:
             for _ in range(K):
-                s = s0.copy(); s[:, :77] *= 1 + mag * prng.uniform(-1, 1, (N, 77))
+                s = s0.copy(); s[:, :_lib.S_TARGET] *= 1 + mag * prng.uniform(-1, 1, (N, _lib.S_TARGET))
                 P.set_state(s); P.set_warm_cache(c0); P.step(a)
                 amp[t] = np.maximum(amp[t], np.abs(P.get_state()[:, POS] - sa[:, POS]).max(1) / mag)
     return amp > AMP, feats, move

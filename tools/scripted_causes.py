@@ -39,7 +39,7 @@ for t in range(2226):
 grasp = snap["s3"]["st"][:, _lib.S_GRASP]
 near = {k: np.linalg.norm(v["tip"] - hole, axis=1) < 0.05 for k, v in snap.items()}
 ee_at_hole = np.linalg.norm(snap["s6"]["ee"] - hole, axis=1) < 0.02
-q6 = snap["s6"]["st"][:, 0:7]
+q6 = snap["s6"]["st"][:, _lib.S_QARM : _lib.S_QARM + 7]
 at_limit = np.minimum(q6 - LO, HI - q6).min(1) < 0.02
 cause = np.full(N, "ok", dtype=object)
 cause[~near["s8"]] = "retreat"

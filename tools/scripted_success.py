@@ -14,4 +14,4 @@ for ball in (0, 1):
         best = torch.maximum(best, rew)
     st = env.state()
     print("attach_ball %d: %d envs, reward = 1 at the end of the episode: %.3f ; at any of the 7 sampled instants: %.3f ; finite %s ; invalid %d" % (
-        ball, n, float(rew.mean()), float(best.mean()), bool(torch.isfinite(st[:, :98]).all()), int(st[:, _lib.S_INVALID].sum())))
+        ball, n, float(rew.mean()), float(best.mean()), bool(torch.isfinite(st[:, :_lib.S_TIP]).all()), int(st[:, _lib.S_INVALID].sum())))
