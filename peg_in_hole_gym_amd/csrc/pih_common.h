@@ -139,6 +139,49 @@ inline Params params_from_config(const pih_config* c) {
   return P;
 }
 
+// The iteration loop of every PGS solver (the three of pih_wave.h, the random-fly one of pih_fly.h, the host one of tests/emul) and the
+// cadence of Bullet's early exit (largest squared row residual <= residual_threshold).
+// Bullet evaluates the test after EVERY iteration; `stride` = pih_config.exit_check_stride selects how often the product does:
+//   stride = 1: every iteration (Bullet's cadence);
+//   stride = s > 1 (default 16): iterations 1..4 -- where it actually fires: envs in free flight converge in two -- then iterations
+//   4 + s k and the last one; in between the body runs without the per-row compare (one v_cmp + one scalar OR per row, ~15 % of a row
+//   update).  An env that would have met the threshold between two tests performs at most s - 1 further iterations whose updates are
+//   all below the threshold.  The oracle has the same switch (piho_config.exit_check_stride); tests/test_gpu_defaults.py compares the
+//   product at its defaults with the oracle at both cadences.
+// (No per-iteration modulo: as `(i - 4) % stride` it was a 40-instruction integer division in front of every sweep.)
+// DOUBLED: the unchecked body is instantiated twice per trip: the multipliers are loop-carried, and with a single copy every new value is
+// moved back into the register the loop header expects.
+template <bool DOUBLED = true, class FC, class FN> PIH_HD int pgs_iteration_loop(int iters, int stride, FC checked, FN unchecked) {
+  int it = 0;
+  const int lead = stride <= 1 ? iters : 4;
+  // iterations 1..lead with the test
+  while (it < iters && it < lead) { it++; if (checked()) return it; }
+  // then groups of `stride`: stride - 1 without, one with (the last iteration always with)
+  while (it < iters) {
+    const int stop = it + stride - 1 < iters - 1 ? it + stride - 1 : iters - 1;
+    if (DOUBLED) {
+      while (it < stop) {
+        it++; unchecked();
+        if (it >= stop) break;
+        it++; unchecked();
+      }
+    } else {
+#pragma nounroll
+      while (it < stop) { it++; unchecked(); }
+    }
+    it++; if (checked()) return it;
+  }
+  return it;
+}
+
+// An env whose state became non-finite is about to be reset (both tasks): its draw counter RNG_HI * 2^24 + RNG survives where it still is
+// a pair of 24-bit integers, and the SPARE word counts the event
+PIH_HD void count_nonfinite_reset(real& rng, real& rng_hi, real& count) {
+  rng = (finite_small(rng) && rng >= 0 && rng < (real)16777216) ? rng : (real)0;
+  rng_hi = (finite_small(rng_hi) && rng_hi >= 0 && rng_hi < (real)16777216) ? rng_hi : (real)0;
+  const real nb = count; count = (finite_small(nb) && nb >= 0 ? nb : (real)0) + 1;
+}
+
 // dof index of link L: arm link i -> i ; pipe root (link 9) -> 9..14 (lin xyz, ang xyz) ; pipe link L>=10 -> L+5
 PIH_HD int link_dof(int L) { return L < ANL ? L : (L == ANL ? 9 : L + 5); }
 

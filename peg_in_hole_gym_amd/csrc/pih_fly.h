@@ -13,7 +13,7 @@
 // for a wavefront per env.  The per-env code is plain scalar code per lane, state in HBM as structure-of-arrays [word][env]; the
 // rigid-body quantities of the six links stay in registers; contact candidates and solver rows are staged in LDS, lane-major
 // ([word][lane]: conflict-free, and a lane may index its rows dynamically without spilling to scratch).
-//   * one env per LANE (`NoQuad`; rounds 2-3, schedule + 32): 64 envs per wavefront;
+//   * one env per LANE (Q = `NoQuad`; rounds 2-3, schedule + 32): 64 envs per wavefront;
 //   * one env per QUAD (`Q::QUAD`): 16 envs per wavefront; kinematics, dynamics and the row build run replicated in the quad's four lanes
 //     (a wavefront issues the same instructions whether 16 or 64 of its lanes hold distinct envs, and 4 x the wavefronts spread over 4 x
 //     the SIMDs), the PGS sweep -- 75 % of the step -- is split over the quad (see CWQ below).
@@ -70,16 +70,13 @@ constexpr int CANDQ0 = 16, KWQ = CWQ;
 constexpr int LANE_WORDS_Q = CANDQ0 + NC * KWQ;
 static_assert(KW <= KWQ && CANDQ0 + KWQ > FQ_LAM + FK_DEPTH + 1 && 6 * NJ <= LANE_WORDS_Q, "candidate k must not be overwritten by record k");
 constexpr int KR = 8;              // quad layout: the records of the first KR contacts of an env stay in REGISTERS over the PGS iterations (72 per lane)
-struct NoQuad {                   // (the members are never called: they keep the discarded quad branches well-formed)
-  static constexpr bool QUAD = false;
-  PIH_HD int lane4() const { return 0; }
-  template <int K> PIH_HD real bcast(real x) const { return x; }
-  PIH_HD real xor1(real x) const { return x; }
-  PIH_HD real xor2(real x) const { return x; }
-  PIH_HD int wave_max(int x) const { return x; }
+// What step_env asks of the wavefront: on the GPU ballots over the active lanes (FlyWave, pih_hip.hip); here a "wavefront" of ONE env, the
+// host build's, where the envs run one after the other
+struct OneEnvWave {
   PIH_HD int wave_or(int x) const { return x; }
   PIH_HD bool wave_any(bool x) const { return x; }
 };
+struct NoQuad : OneEnvWave { static constexpr bool QUAD = false; };      // one env per lane: no quad primitives
 
 PIH_CONST real U_MASS[NJ] = PIH_UR5_MASS;
 PIH_CONST real U_COM[NJ][3] = PIH_UR5_COM;
@@ -198,15 +195,19 @@ struct FlyStamp {
 struct FlyStamp { FlyStamp(real*, bool) {} void operator()(int) {} };
 #endif
 
+// The constants of a layout's records in lane memory: RW words per contact record, LAMW its multiplier word, candidate k at CAND + k * KS
+// (lane layout: the candidates follow the compacted row records).  step_env picks Layout<Q::QUAD>.
+template <bool QUAD> struct Layout;
+template <> struct Layout<false> { static constexpr int RW = CW, LAMW = FC_LAM, CAND = CAND0, KS = KW; };
+template <> struct Layout<true> { static constexpr int RW = CWQ, LAMW = FQ_LAM, CAND = CANDQ0, KS = KWQ; };
+
 // One dt of one env.  S: the env's state record (a per-lane local array); mem: this lane's contact-row scratch; ctl: InlineIk or the
 // mailbox reader of the fused launch (MailboxIk, pih_hip.hip).
 // Q: NoQuad (one env per lane) or the quad primitives (QuadDpp / the host's lockstep threads, pih_ikq.h) of the one-env-per-quad layout.
 template <class Ctl = InlineIk, class Q = NoQuad, class Mem>
 PIH_HD void step_env(real* S, const Params& P, int env_global, const real* action, real* obs, real* reward, unsigned char* done, Mem mem, real* dbg, Ctl ctl = Ctl(), Q quad = Q()) {
-  constexpr int RW = Q::QUAD ? CWQ : CW;          // words of a contact record in this lane's memory
-  constexpr int LAMW = Q::QUAD ? FQ_LAM : FC_LAM;   // ... and its multiplier word
-  constexpr int CANDQ = Q::QUAD ? CANDQ0 : NC * RW;        // lane layout: candidates follow the (compacted) row records
-  constexpr int KS = Q::QUAD ? KWQ : KW;                   // stride of the candidates
+  using Lay = Layout<Q::QUAD>;
+  constexpr int RW = Lay::RW, LAMW = Lay::LAMW, CANDQ = Lay::CAND, KS = Lay::KS;
   const real dt = P.dt;
   const bool frozen = !P.autoreset && S[PIH_F_DONE] != 0;   // finished envs keep their last values (envs/base_env.py:62,66)
   bool landed = false;
@@ -491,7 +492,6 @@ PIH_HD void step_env(real* S, const Params& P, int env_global, const real* actio
 #pragma unroll
       for (int k = 0; k < 3; k++) {
         if constexpr (Q::QUAD) Wq[j][k] = quad.lane4() == 0 ? Wm[j][k] : quad.lane4() == 1 ? Wm[j][3 + k] : (real)0;
-        else Wq[j][k] = 0;
       }
     }
     // SPECULATE AND VERIFY on the joint-limit rows.  A limit row whose multiplier is zero and whose right-hand side stays <= 0 is a no-op,
@@ -537,14 +537,15 @@ PIH_HD void step_env(real* S, const Params& P, int env_global, const real* actio
     auto sweep = [&](auto CHECKTAG) __attribute__((always_inline)) -> real {
       constexpr bool CHECK = decltype(CHECKTAG)::value;
       real worst = -1;
-      auto joint_rows = [&](auto JTAG) __attribute__((always_inline)) {
-        constexpr int j = decltype(JTAG)::value;
-        const real tot = joint_tot(JTAG, du[j], CHECKTAG, worst);
+      if constexpr (!Q::QUAD) {             // one env per lane: the lane holds the whole du
+        auto joint_rows = [&](auto JTAG) __attribute__((always_inline)) {
+          constexpr int j = decltype(JTAG)::value;
+          const real tot = joint_tot(JTAG, du[j], CHECKTAG, worst);
   #pragma unroll
-        for (int k = 0; k < NJ; k++) du[k] += Wm[j][k] * tot;
-      };
-      joint_rows(std::integral_constant<int, 0>{}); joint_rows(std::integral_constant<int, 1>{}); joint_rows(std::integral_constant<int, 2>{});
-      joint_rows(std::integral_constant<int, 3>{}); joint_rows(std::integral_constant<int, 4>{}); joint_rows(std::integral_constant<int, 5>{});
+          for (int k = 0; k < NJ; k++) du[k] += Wm[j][k] * tot;
+        };
+        joint_rows(std::integral_constant<int, 0>{}); joint_rows(std::integral_constant<int, 1>{}); joint_rows(std::integral_constant<int, 2>{});
+        joint_rows(std::integral_constant<int, 3>{}); joint_rows(std::integral_constant<int, 4>{}); joint_rows(std::integral_constant<int, 5>{});
         // Contact rows.  The whole 24-word record of a contact is read in ONE batch and pinned in registers before any of it is used: left
         // to the compiler (at the register limit) the loop read two words, waited, used them, read the next two -- twelve LDS round trips
         // per contact, 4 - 6 k cycles per PGS iteration for a wave whose lanes have up to six contacts (profiles/r04_fly_trace.txt).  And
@@ -584,12 +585,7 @@ PIH_HD void step_env(real* S, const Params& P, int env_global, const real* actio
             if (c + 1 < nc) solve_rec(Rb, c + 1);
           }
         }
-      return worst;
-    };
-    auto sweep_quad = [&](auto CHECKTAG) __attribute__((always_inline)) -> real {
-      constexpr bool CHECK = decltype(CHECKTAG)::value;
-      real worst = -1;
-      if constexpr (Q::QUAD) {
+      } else {                              // one env per quad: du3, Wq and the register records Rr / lamr
         auto joint_rows = [&](auto JTAG) __attribute__((always_inline)) {
           constexpr int j = decltype(JTAG)::value;
           const real tot = joint_tot(JTAG, quad.template bcast<(j / 3)>(du3[j % 3]), CHECKTAG, worst);
@@ -598,20 +594,22 @@ PIH_HD void step_env(real* S, const Params& P, int env_global, const real* actio
         };
         joint_rows(std::integral_constant<int, 0>{}); joint_rows(std::integral_constant<int, 1>{}); joint_rows(std::integral_constant<int, 2>{});
         joint_rows(std::integral_constant<int, 3>{}); joint_rows(std::integral_constant<int, 4>{}); joint_rows(std::integral_constant<int, 5>{});
+        // one row: the lane's three multiply-adds, the two-step quad all-reduce, the update of the lane's three components
+        auto row = [&](const real* R, real lam, real& lam_out) __attribute__((always_inline)) {
+          real jd = R[FQ_J] * du3[0] + R[FQ_J + 1] * du3[1] + R[FQ_J + 2] * du3[2];
+          jd += quad.xor1(jd); jd += quad.xor2(jd);
+          const real di = R[FQ_DINV];
+          real dl = R[FQ_RHS] - jd * di;
+          const real sum = max_(lam + dl, (real)0);
+          dl = sum - lam; lam_out = sum;
+  #pragma unroll
+          for (int k = 0; k < 3; k++) du3[k] += R[FQ_W + k] * dl;
+          if (CHECK) { const real v = dl * dl - P.resid * di * di; worst = v > worst ? v : worst; }
+        };
   #pragma unroll
         for (int c = 0; c < KR; c++) {
           if (c >= ncw) break;               // (wave-uniform: ONE taken branch per sweep, past the remaining register records)
-          {
-            real jd = Rr[c][FQ_J] * du3[0] + Rr[c][FQ_J + 1] * du3[1] + Rr[c][FQ_J + 2] * du3[2];
-            jd += quad.xor1(jd); jd += quad.xor2(jd);
-            const real di = Rr[c][FQ_DINV];
-            real dl = Rr[c][FQ_RHS] - jd * di;
-            const real sum = max_(lamr[c] + dl, (real)0);
-            dl = sum - lamr[c]; lamr[c] = sum;
-  #pragma unroll
-            for (int k = 0; k < 3; k++) du3[k] += Rr[c][FQ_W + k] * dl;
-            if (CHECK) { const real v = dl * dl - P.resid * di * di; worst = v > worst ? v : worst; }
-          }
+          row(Rr[c], lamr[c], lamr[c]);
         }
         // contacts KR .. (rare: a ninth contact of one env): from lane memory
         if (ncw > KR) {
@@ -619,26 +617,13 @@ PIH_HD void step_env(real* S, const Params& P, int env_global, const real* actio
             real R[CWQ];
   #pragma unroll
             for (int i = 0; i < CWQ; i++) R[i] = mem.at(c * CWQ + i);
-            real jd = R[FQ_J] * du3[0] + R[FQ_J + 1] * du3[1] + R[FQ_J + 2] * du3[2];
-            jd += quad.xor1(jd); jd += quad.xor2(jd);
-            const real di = R[FQ_DINV], lam = R[FQ_LAM];
-            real dl = R[FQ_RHS] - jd * di;
-            const real sum = max_(lam + dl, (real)0);
-            dl = sum - lam; mem.at(c * CWQ + FQ_LAM) = sum;
-  #pragma unroll
-            for (int k = 0; k < 3; k++) du3[k] += R[FQ_W + k] * dl;
-            if (CHECK) { const real v = dl * dl - P.resid * di * di; worst = v > worst ? v : worst; }
+            row(R, R[FQ_LAM], mem.at(c * CWQ + FQ_LAM));
           }
         }
       }
       return worst;
     };
-    auto one = [&](bool chk) __attribute__((always_inline)) -> bool {
-      if constexpr (Q::QUAD) {
-        return chk ? sweep_quad(std::true_type{}) <= 0 : (sweep_quad(std::false_type{}), false);
-      }
-      else return chk ? sweep(std::true_type{}) <= 0 : (sweep(std::false_type{}), false);
-    };
+    auto one = [&](bool chk) __attribute__((always_inline)) -> bool { return chk ? sweep(std::true_type{}) <= 0 : (sweep(std::false_type{}), false); };
     int it = 0; const int limmask0 = limmask; bool redone = false;
 #pragma nounroll
     for (int pass = 0; pass < 2; pass++) {
@@ -659,14 +644,15 @@ PIH_HD void step_env(real* S, const Params& P, int env_global, const real* actio
       for (int i = 0; i < FND; i++) du[i] = 0;
 #pragma unroll
       for (int j = 0; j < NJ; j++) { lam_m[j] = 0; lam_lo[j] = 0; lam_hi[j] = 0; }
-      du3[0] = du3[1] = du3[2] = 0; viol = -1;
+      if constexpr (Q::QUAD) { du3[0] = du3[1] = du3[2] = 0; }
+      viol = -1;
       if constexpr (Q::QUAD) {
 #pragma unroll
         for (int c = 0; c < KR; c++) lamr[c] = 0;
       }
       if (pass == 1) for (int c = 0; c < nc; c++) mem.at(c * RW + LAMW) = 0;
       // iterations 1 .. 4 with the test, then groups of `checkstride`: stride - 1 without, one with; the last iteration always with (the
-      // structure of pgs_iteration_loop, pih_wave.h: no per-iteration modulo -- as `(i - 4) % stride` it was a 40-instruction integer
+      // structure of pgs_iteration_loop, pih_common.h: no per-iteration modulo -- as `(i - 4) % stride` it was a 40-instruction integer
       // division in front of every sweep)
       it = 0;
       const int iters = P.iters, stride = P.checkstride, lead = stride <= 1 ? iters : 4;
@@ -730,11 +716,7 @@ PIH_HD void step_env(real* S, const Params& P, int env_global, const real* actio
   obs[3] = S[PIH_F_OPOS] + S[PIH_F_OFFSET]; obs[4] = S[PIH_F_OPOS + 1] + S[PIH_F_OFFSET + 1]; obs[5] = S[PIH_F_OPOS + 2] + S[PIH_F_OFFSET + 2];
   *reward = rew; *done = (unsigned char)((S[PIH_F_DONE] != 0 || bad) ? 1 : 0);
   if (bad || (P.autoreset && S[PIH_F_DONE] != 0)) {
-    if (bad) {
-      S[PIH_F_RNG] = (finite_small(S[PIH_F_RNG]) && S[PIH_F_RNG] >= 0 && S[PIH_F_RNG] < (real)16777216) ? S[PIH_F_RNG] : (real)0;
-      S[PIH_F_RNG_HI] = (finite_small(S[PIH_F_RNG_HI]) && S[PIH_F_RNG_HI] >= 0 && S[PIH_F_RNG_HI] < (real)16777216) ? S[PIH_F_RNG_HI] : (real)0;
-      const real nb = S[PIH_F_SPARE]; S[PIH_F_SPARE] = (finite_small(nb) && nb >= 0 ? nb : (real)0) + 1;
-    }
+    if (bad) count_nonfinite_reset(S[PIH_F_RNG], S[PIH_F_RNG_HI], S[PIH_F_SPARE]);
     fly::reset_state(S, P, env_global);
     if (bad && !P.autoreset) { S[PIH_F_DONE] = 1; S[PIH_F_INVALID] = 1; }
   }

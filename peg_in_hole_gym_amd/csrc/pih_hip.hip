@@ -305,26 +305,25 @@ struct MailboxIk {
 };
 // QUAD: one env per quad of lanes (pih_fly.h): a step wavefront holds 16 envs, the PGS sweep is split over the quad; the controller
 // wavefronts stay one env per lane, so one flag covers four step wavefronts.
-__device__ __forceinline__ int fly_wave_or(int x) {     // OR of a 6-bit mask over the wavefront's active lanes, as a scalar
-  int m = 0;
+struct FlyWave {           // what fly::step_env asks of the wavefront, as scalars over its active lanes
+  __device__ __forceinline__ int wave_or(int x) const {     // OR of a 6-bit mask
+    int m = 0;
 #pragma unroll
-  for (int k = 0; k < fly::NJ; k++) if (__builtin_amdgcn_ballot_w64((x >> k) & 1) != 0) m |= 1 << k;
-  return __builtin_amdgcn_readfirstlane(m);
-}
-struct FlyLane : fly::NoQuad {
-  __device__ __forceinline__ int wave_or(int x) const { return fly_wave_or(x); }
+    for (int k = 0; k < fly::NJ; k++) if (__builtin_amdgcn_ballot_w64((x >> k) & 1) != 0) m |= 1 << k;
+    return __builtin_amdgcn_readfirstlane(m);
+  }
   __device__ __forceinline__ bool wave_any(bool x) const { return __builtin_amdgcn_ballot_w64(x) != 0; }
 };
-struct FlyQuad : QuadDpp {
+struct FlyLane : FlyWave { static constexpr bool QUAD = false; __device__ __forceinline__ explicit FlyLane(int) {} };
+struct FlyQuad : QuadDpp, FlyWave {
   static constexpr bool QUAD = true;
-  __device__ __forceinline__ int wave_max(int x) const {     // the largest x of the wavefront's active lanes (0 <= x <= fly::NC), as a scalar
+  __device__ __forceinline__ explicit FlyQuad(int lane) { l = lane & 3; }
+  __device__ __forceinline__ int wave_max(int x) const {     // the largest x (0 <= x <= fly::NC)
     int m = 0;
 #pragma unroll
     for (int k = 1; k <= fly::NC; k++) if (__builtin_amdgcn_ballot_w64(x >= k) != 0) m = k;
     return __builtin_amdgcn_readfirstlane(m);
   }
-  __device__ __forceinline__ int wave_or(int x) const { return fly_wave_or(x); }
-  __device__ __forceinline__ bool wave_any(bool x) const { return __builtin_amdgcn_ballot_w64(x) != 0; }
 };
 template <bool FUSED, bool QUAD>
 __global__ void __launch_bounds__(64, 1) pih_fly_step_kernel(Params P, float* __restrict__ state, const float* __restrict__ actions,
@@ -370,12 +369,10 @@ __global__ void __launch_bounds__(64, 1) pih_fly_step_kernel(Params P, float* __
   float o[PIH_FLY_OBS_DIM], r; unsigned char d;
   fly::LaneMem mem; mem.p = lanemem + threadIdx.x; mem.stride = 64;
   float* dbge = dbg ? dbg + (size_t)env * PIH_DEBUG_WORDS : nullptr;
-  if constexpr (FUSED) {
-    MailboxIk mb; mb.flag = F.flags + (env >> 6); mb.mail = F.mail; mb.err = F.err; mb.epoch = F.epoch; mb.env = env; mb.n = n;
-    if constexpr (QUAD) { FlyQuad qd; qd.l = threadIdx.x & 3; fly::step_env(S, P, P.env0 + env, a, o, &r, &d, mem, dbge, mb, qd); }
-    else fly::step_env(S, P, P.env0 + env, a, o, &r, &d, mem, dbge, mb, FlyLane());
-  } else if constexpr (QUAD) { FlyQuad qd; qd.l = threadIdx.x & 3; fly::step_env(S, P, P.env0 + env, a, o, &r, &d, mem, dbge, fly::InlineIk(), qd); }
-  else fly::step_env(S, P, P.env0 + env, a, o, &r, &d, mem, dbge, fly::InlineIk(), FlyLane());
+  // the IK targets from the controller wavefront's mailbox (FUSED) or computed here
+  std::conditional_t<FUSED, MailboxIk, fly::InlineIk> ctl;
+  if constexpr (FUSED) { ctl.flag = F.flags + (env >> 6); ctl.mail = F.mail; ctl.err = F.err; ctl.epoch = F.epoch; ctl.env = env; ctl.n = n; }
+  fly::step_env(S, P, P.env0 + env, a, o, &r, &d, mem, dbge, ctl, std::conditional_t<QUAD, FlyQuad, FlyLane>((int)threadIdx.x));
   if (writer) {
 #pragma unroll
     for (int w = 0; w < fly::SW; w++) state[(size_t)w * n + env] = S[w];
@@ -563,6 +560,20 @@ static int next_epoch(pih_handle* h) {
   return ++h->epoch;
 }
 
+// The random-fly step launch of a handle in its layout (h->flyquad), fused or not: the instantiation of pih_fly_step_kernel, the grid (G
+// controller workgroups in front of the step workgroups when fused), the dynamic LDS of every workgroup, and how many of them a CU holds
+struct FlyLaunch { decltype(&pih_fly_step_kernel<false, false>) kernel; int G, grid, per_cu; size_t lds; };
+static_assert((size_t)fly::LANE_WORDS * 64 * sizeof(float) <= 160 * 1024 && (size_t)fly::LANE_WORDS_Q * 64 * sizeof(float) * 4 <= 160 * 1024, "the random-fly kernel's per-wave LDS exceeds its share of a CU's 160 KB");
+static FlyLaunch fly_launch(const pih_handle* h, bool fused) {
+  const int n = h->cfg.n_envs;
+  FlyLaunch L;
+  L.G = (n + 63) / 64;
+  if (h->flyquad) { L.kernel = fused ? pih_fly_step_kernel<true, true> : pih_fly_step_kernel<false, true>; L.grid = (n + 15) / 16; L.per_cu = 4; L.lds = (size_t)fly::LANE_WORDS_Q * 64 * sizeof(float); }
+  else { L.kernel = fused ? pih_fly_step_kernel<true, false> : pih_fly_step_kernel<false, false>; L.grid = L.G; L.per_cu = 1; L.lds = (size_t)fly::LANE_WORDS * 64 * sizeof(float); }
+  if (fused) L.grid += L.G;
+  return L;
+}
+
 // allocation + first reset; on any failure the caller (pih_create) destroys the half-built handle
 static int create_impl(pih_handle* h, const float* offsets_host, float** offd) {
   const pih_config* cfg = &h->cfg;
@@ -575,25 +586,19 @@ static int create_impl(pih_handle* h, const float* offsets_host, float** offd) {
     HIPCHK(h, hipMemcpy(*offd, offsets_host, (size_t)cfg->n_envs * 3 * sizeof(float), hipMemcpyHostToDevice));
   }
   if (h->fly) {
-    // (dynamic LDS beyond the default 64 KB limit: the per-lane contact rows and candidate staging of 64 envs are LANE_WORDS * 64 words)
-    static_assert((size_t)fly::LANE_WORDS * 64 * sizeof(float) <= 160 * 1024, "the random-fly kernel's per-wave LDS exceeds a CU's 160 KB");
-    HIPCHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(pih_fly_step_kernel<false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(fly::LANE_WORDS * 64 * sizeof(float))));
-    HIPCHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(pih_fly_step_kernel<true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(fly::LANE_WORDS * 64 * sizeof(float))));
-    HIPCHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(pih_fly_step_kernel<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(fly::LANE_WORDS_Q * 64 * sizeof(float))));
-    HIPCHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(pih_fly_step_kernel<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(fly::LANE_WORDS_Q * 64 * sizeof(float))));
-    {
-      // fused launch (controller wavefronts + step wavefronts in one grid) while both sets of workgroups -- each with the step's 120 KB of
-      // LDS -- fit the chip's CUs at once; schedule + 8: IK inside the step wavefront (switch)
-      int cus = 0; HIPCHK(h, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device));
-      const int G = (cfg->n_envs + 63) / 64;
-      // One env per QUAD of lanes in the step wavefronts (38 KB of LDS: four workgroups per CU) unless schedule + 32; its fused launch needs
-      // the G controller workgroups and the ceil(n / 16) step workgroups resident together: 4 per CU (n <= 13 104 on 256 CUs); bigger
-      // batches run the IK inside the quad's step wavefront.  The lane layout (120 KB per workgroup) fuses while 2 G <= CUs.
-      h->flyquad = (cfg->schedule & 32) == 0;
-      h->fused = (cfg->schedule & 8) == 0 && (h->flyquad ? G + (cfg->n_envs + 15) / 16 <= 4 * cus : 2 * G <= cus);
-      // mailbox [group][word][64 lanes]: the two 128-byte lines of a (group, word) hold no other group's targets
-      if (h->fused) { int rc = mailbox_alloc(h, (size_t)G * 64 * fly::NJ); if (rc) return rc; }
-    }
+    // One env per QUAD of lanes in the step wavefronts unless schedule + 32.  The fused launch (controller wavefronts + step wavefronts in
+    // one grid; schedule + 8: IK inside the step wavefront) is used while ALL its workgroups -- each with the step's dynamic LDS -- are
+    // resident at once: 4 per CU in the quad layout (n <= 13 104 on 256 CUs), 1 per CU in the lane layout; bigger batches run the IK inside
+    // the step wavefront.
+    h->flyquad = (cfg->schedule & 32) == 0;
+    int cus = 0; HIPCHK(h, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device));
+    const FlyLaunch fused = fly_launch(h, true);
+    h->fused = (cfg->schedule & 8) == 0 && fused.grid <= fused.per_cu * cus;
+    // (dynamic LDS beyond the default 64 KB limit: the per-lane contact rows and candidate staging of 64 lanes)
+    for (const FlyLaunch& L : {fly_launch(h, false), fused})
+      HIPCHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(L.kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.lds));
+    // mailbox [group][word][64 lanes]: the two 128-byte lines of a (group, word) hold no other group's targets
+    if (h->fused) { int rc = mailbox_alloc(h, (size_t)fused.G * 64 * fly::NJ); if (rc) return rc; }
     const int nb64 = (cfg->n_envs + 63) / 64;
     hipLaunchKernelGGL(pih_fly_init_offsets_kernel, dim3(nb64), dim3(64), 0, 0, h->state, *offd, cfg->n_envs);
     hipLaunchKernelGGL(pih_fly_reset_kernel, dim3(nb64), dim3(64), 0, 0, h->P, h->state, (const unsigned char*)nullptr, 0, 0, cfg->n_envs);
@@ -690,24 +695,15 @@ static int launch_step(pih_handle* h, const float* actions, float* obs, float* r
   // random-fly: the fused launch (IK in controller wavefronts of the same grid) while all its workgroups fit the chip at once, else (and
   // with schedule + 8) the IK inside the step wavefront.  peg-in-hole: the fused launch, or with schedule + 8 the two-launch step.
   if (h->fly) {
-    const int G = (h->cfg.n_envs + 63) / 64; const size_t lds = (size_t)fly::LANE_WORDS * 64 * sizeof(float);
+    const FlyLaunch L = fly_launch(h, h->fused);
     FlyFused FF; memset(&FF, 0, sizeof FF);
     if (h->fused) {
       const int e = next_epoch(h);
       if (e < 0) return e;
-      FF.G = G; FF.epoch = e; FF.mail = h->mail; FF.flags = h->flags; FF.err = h->errw;
-      if (t) HIPCHK(h, hipEventRecord(t->b, s));
-      if (h->flyquad)
-        hipLaunchKernelGGL((pih_fly_step_kernel<true, true>), dim3(G + (h->cfg.n_envs + 15) / 16), dim3(64), (size_t)fly::LANE_WORDS_Q * 64 * sizeof(float), s, h->P, h->state, actions, obs, reward, done, h->dbg, h->cfg.n_envs, FF);
-      else
-        hipLaunchKernelGGL((pih_fly_step_kernel<true, false>), dim3(2 * G), dim3(64), lds, s, h->P, h->state, actions, obs, reward, done, h->dbg, h->cfg.n_envs, FF);
-    } else {
-      if (t) HIPCHK(h, hipEventRecord(t->b, s));
-      if (h->flyquad)
-        hipLaunchKernelGGL((pih_fly_step_kernel<false, true>), dim3((h->cfg.n_envs + 15) / 16), dim3(64), (size_t)fly::LANE_WORDS_Q * 64 * sizeof(float), s, h->P, h->state, actions, obs, reward, done, h->dbg, h->cfg.n_envs, FF);
-      else
-        hipLaunchKernelGGL((pih_fly_step_kernel<false, false>), dim3(G), dim3(64), lds, s, h->P, h->state, actions, obs, reward, done, h->dbg, h->cfg.n_envs, FF);
+      FF.G = L.G; FF.epoch = e; FF.mail = h->mail; FF.flags = h->flags; FF.err = h->errw;
     }
+    if (t) HIPCHK(h, hipEventRecord(t->b, s));
+    hipLaunchKernelGGL(L.kernel, dim3(L.grid), dim3(64), L.lds, s, h->P, h->state, actions, obs, reward, done, h->dbg, h->cfg.n_envs, FF);
     if (t) HIPCHK(h, hipEventRecord(t->c, s));
     HIPCHK(h, hipGetLastError());
     return 0;

@@ -193,9 +193,7 @@ PIH_HD void step_env(W& w, Shared& sh, const Params& P, const Ovf& ov, int env, 
   *reward = rew; *done = (unsigned char)((S[PIH_S_DONE] != 0 || bad) ? 1 : 0);
   w.sync();
   if (bad || (P.autoreset && S[PIH_S_DONE] != 0)) {
-    if (bad) { S[PIH_S_RNG] = (finite_small(S[PIH_S_RNG]) && S[PIH_S_RNG] >= 0 && S[PIH_S_RNG] < (real)16777216) ? S[PIH_S_RNG] : (real)0;
-               S[PIH_S_RNG_HI] = (finite_small(S[PIH_S_RNG_HI]) && S[PIH_S_RNG_HI] >= 0 && S[PIH_S_RNG_HI] < (real)16777216) ? S[PIH_S_RNG_HI] : (real)0;
-               real nb = S[PIH_S_SPARE]; S[PIH_S_SPARE] = (finite_small(nb) && nb >= 0 ? nb : (real)0) + 1; }   // count non-finite resets
+    if (bad) count_nonfinite_reset(S[PIH_S_RNG], S[PIH_S_RNG_HI], S[PIH_S_SPARE]);
     reset_state(S, P, P.env0 + env);
     // auto_reset = 0 (the reference-shaped facade): a non-finite env does not silently start a second episode -- it is put back
     // into a finite initial state, reported done, flagged invalid, and stays frozen until the caller resets it

@@ -376,38 +376,7 @@ PIH_HD void row16_sum3(real& a, real& b, real& c) {
 // limit; the 23 pipe motors; per contact: normal, dir1, dir2).  The DOF velocities are recovered at the end as du = sum_i W_i
 // lambda_i.  The arm-row and pipe-row columns are disjoint (A[arm][pipe motor] = 0), so the motor chain runs on two accumulators
 // for ILP exactly like the DOF-space chain.  (tools/micro/rowchain.hip times the row chain in isolation.)
-// The iteration loop of all three solvers and the cadence of Bullet's early exit (largest squared row residual <= residual_threshold).
-// Bullet evaluates the test after EVERY iteration; `stride` = pih_config.exit_check_stride selects how often the product does:
-//   stride = 1: every iteration (Bullet's cadence);
-//   stride = s > 1 (default 16): iterations 1..4 -- where it actually fires: envs in free flight converge in two -- then iterations
-//   4 + s k and the last one; in between the body runs without the per-row compare (one v_cmp + one scalar OR per row, ~15 % of a row
-//   update).  An env that would have met the threshold between two tests performs at most s - 1 further iterations whose updates are
-//   all below the threshold.  The oracle has the same switch (piho_config.exit_check_stride); tests/test_gpu_defaults.py compares the
-//   product at its defaults with the oracle at both cadences.
-// The unchecked body is instantiated twice per trip: the multipliers are loop-carried, and with a single copy every new value is
-// moved back into the register the loop header expects.
-template <bool DOUBLED = true, class FC, class FN> PIH_HD int pgs_iteration_loop(int iters, int stride, FC checked, FN unchecked) {
-  int it = 0;
-  const int lead = stride <= 1 ? iters : 4;
-  // iterations 1..lead with the test
-  while (it < iters && it < lead) { it++; if (checked()) return it; }
-  // then groups of `stride`: stride - 1 without, one with (the last iteration always with)
-  while (it < iters) {
-    const int stop = it + stride - 1 < iters - 1 ? it + stride - 1 : iters - 1;
-    if (DOUBLED) {
-      while (it < stop) {
-        it++; unchecked();
-        if (it >= stop) break;
-        it++; unchecked();
-      }
-    } else {
-#pragma nounroll
-      while (it < stop) { it++; unchecked(); }
-    }
-    it++; if (checked()) return it;
-  }
-  return it;
-}
+// (The iteration loop of all three solvers and the cadence of the exit test: pgs_iteration_loop, pih_common.h.)
 // Word W (a CR_* / MR_* / LR_* name, pih_common.h) of a record held in registers as 16-byte groups: component W % 4 of group W / 4,
 // picked at compile time; rec4v: words W .. W + 2 as a vector
 template <int W> PIH_HD real rec4(const real4* q) { constexpr int c = W % 4; return c == 0 ? q[W / 4].x : c == 1 ? q[W / 4].y : c == 2 ? q[W / 4].z : q[W / 4].w; }

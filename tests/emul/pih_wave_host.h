@@ -174,8 +174,8 @@ PIH_HD int pgs(Wave& w, Shared& sh, const Params& P, const Ovf& ov, const MotorW
   real mlam[NMOT], llam[NLIM];
   for (int m = 0; m < NMOT; m++) mlam[m] = 0;
   for (int k = 0; k < NLIM; k++) llam[k] = 0;
-  int it = 0;
-  for (; it < P.iters; it++) {
+  // one sweep over the rows; returns the exit test (evaluated by pgs_iteration_loop at the product's cadence)
+  auto iterate = [&]() -> bool {
     real worst = -1;
     auto track = [&](real dl, real di) { real v = dl * dl - P.resid * di * di; if (v > worst) worst = v; };
     for (int m = 0; m < NMOT; m++) {
@@ -213,12 +213,9 @@ PIH_HD int pgs(Wave& w, Shared& sh, const Params& P, const Ovf& ov, const MotorW
         track(dl, di);
       }
     }
-    // the product's cadence of the early-exit test (pih_wave.h pgs_iteration_loop): stride 1 = every iteration, s > 1 = iterations
-    // 1..4, 4 + s k, and the last one
-    const int itn = it + 1, s = P.checkstride;
-    const bool checked = s <= 1 || itn <= 4 || itn == P.iters || (itn - 4) % s == 0;
-    if (checked && worst <= 0) { it++; break; }
-  }
+    return worst <= 0;
+  };
+  const int it = pgs_iteration_loop<false>(P.iters, P.checkstride, iterate, iterate);
   for (int d = 0; d < ND; d++) sh.u[d] += du[d];
   (void)mw;
   return it;
