@@ -13,6 +13,9 @@
  *                           (envs/utils.py:67,79; envs/meta_env.py:92,104)
  *   pih_render    replaces  p.computeViewMatrix / computeProjectionMatrixFOV / getCameraImage of PegInHole.render
  *                           (envs/peg_in_hole.py:276-304) with an analytic ray caster over the primitive scene
+ *   pih_render_cam replaces p.computeViewMatrix / computeProjectionMatrixFOV / getCameraImage for the 'random-fly' task (README.md:38; the
+ *                           task class and with it its camera are not in the snapshot): a caller-given camera over the UR5's collision
+ *                           capsules, the object's sphere cover and the table plane
  *   pih_get_state replaces  p.getLinkState / p.getJointState / (north_star) getContactPoints normal force read-backs
  *
  * Conventions: every call returns 0 on success, <0 on error (pih_last_error gives the text).  All *_dev pointers
@@ -211,6 +214,21 @@ int pih_render(pih_handle* h, float* out_dev, int width, int height, int env_beg
  * TinyRenderer's default light (getCameraImage without light arguments; specular term and shadow map not reproduced) */
 #define PIH_RENDER_SHADED 1
 int pih_render_ex(pih_handle* h, float* out_dev, int width, int height, int env_begin, int env_count, int flags, void* stream);
+/* free camera of the 'random-fly' task (fly handles only; a peg-in-hole handle gets -2, and pih_render / pih_render_ex keep rejecting fly
+ * handles).  The camera is given as p.computeViewMatrix (eye, target, up) and p.computeProjectionMatrixFOV (fov, aspect, near, far) take
+ * it, the image comes back as p.getCameraImage's (envs/peg_in_hole.py:276-304): out_dev float[env_count, height, width, 4] = (OpenGL
+ * depth-buffer value, r, g, b), row 0 on top, from the CURRENT state, 16-byte aligned, env_count <= 65535.  Scene: the six UR5 collision
+ * capsules (255 x PIH_UR5_RGB), the object's sphere cover (255 x PIH_FLY_OBJ_RGB), the table plane (153), background 255 at depth 1; a hit
+ * outside [near, far] is clipped.  flags: PIH_RENDER_SHADED as in pih_render_ex (same light, ambient and diffuse terms);
+ * PIH_RENDER_CAM_EE = eye, target and up are given in the ee_link frame of each env's UR5 (eye-in-hand) instead of the env-local frame
+ * (the env's offset does not enter either way).  cam_host: HOST float[PIH_CAM_WORDS], read during the call, one camera for all envs of
+ * the call; NULL = PIH_FLY_CAM_DEFAULT.  A degenerate camera (eye == target, up parallel to the view axis, fov outside (0, 180),
+ * aspect <= 0, near <= 0, far <= near) returns -2 and pih_last_error names the field. */
+#define PIH_CAM_WORDS 13        /* eye xyz, target xyz, up xyz, fov [deg, vertical], aspect, near, far */
+#define PIH_FLY_CAM_DEFAULT {1.6f, 0.f, 1.2f,  0.f, 0.f, 0.2f,  0.f, 0.f, 1.f,  60.f, 1.f, 0.01f, 100.f}
+#define PIH_RENDER_CAM_EE 2     /* camera given in the ee_link frame of each env's UR5 (eye-in-hand) instead of the env-local frame */
+int pih_render_cam(pih_handle* h, float* out_dev, const float* cam_host /* [PIH_CAM_WORDS] or NULL = default */,
+                   int width, int height, int env_begin, int env_count, int flags, void* stream);
 /* grasp-rectangle label images of random_grasp (envs/peg_in_hole.py:72-99,116) from the angle each env recorded when its
  * state machine entered state 2 (PIH_S_GRASP_ANGLE): out_dev float[env_count, 4, size, size] = pos (50 inside the rectangle),
  * sin(2 angle), cos(2 angle), width in pixels; meta_dev (may be NULL) float[env_count, 5] = x, y, angle [deg], width, length.

@@ -10,6 +10,9 @@ LIB_PATH = os.environ.get("PIH_LIB_PATH") or os.path.join(_HERE, "csrc", "libpih
 ABI_VERSION = 4
 STATE_WORDS, DEBUG_WORDS, ACTION_DIM, OBS_DIM = 256, 1024, 4, 5
 FLY_STATE_WORDS, FLY_ACTION_DIM, FLY_OBS_DIM = 48, 6, 6
+CAM_WORDS = 13     # pih_render_cam: eye xyz, target xyz, up xyz, fov [deg, vertical], aspect, near, far
+FLY_CAM_DEFAULT = (1.6, 0.0, 1.2, 0.0, 0.0, 0.2, 0.0, 0.0, 1.0, 60.0, 1.0, 0.01, 100.0)    # PIH_FLY_CAM_DEFAULT
+RENDER_SHADED, RENDER_CAM_EE = 1, 2                # flags of pih_render_ex / pih_render_cam
 FIELD_STATE, FIELD_TIP_POSE, FIELD_CONTACT_FORCE, FIELD_DEBUG, FIELD_EE_POS = 0, 1, 2, 3, 4
 TASK_PEG_IN_HOLE, TASK_RANDOM_FLY = 0, 1
 # state record word offsets (PIH_S_*)
@@ -26,7 +29,7 @@ DBG_FLY_UDOT, DBG_FLY_NCONTACT, DBG_FLY_PGS_ITERS, DBG_FLY_LIMIT_ROWS, DBG_FLY_C
 DBG_CYCLES, DBG_T_START, DBG_T_END, DBG_HW_ID, DBG_XCC_ID = 900, 940, 943, 946, 947
 
 EXPORTS = ["pih_default_config", "pih_abi_version", "pih_task_dims", "pih_object_name", "pih_create", "pih_destroy", "pih_reset", "pih_reseed", "pih_step", "pih_step_n",
-           "pih_get_state", "pih_set_state", "pih_ik", "pih_ik_ur5", "pih_render", "pih_render_ex", "pih_grasp_labels", "pih_timing", "pih_timing2", "pih_set_timing", "pih_last_error"]
+           "pih_get_state", "pih_set_state", "pih_ik", "pih_ik_ur5", "pih_render", "pih_render_ex", "pih_render_cam", "pih_grasp_labels", "pih_timing", "pih_timing2", "pih_set_timing", "pih_last_error"]
 
 
 class PihConfig(C.Structure):
@@ -76,6 +79,7 @@ def load():
     L.pih_ik_ur5.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp]
     L.pih_render.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]
     L.pih_render_ex.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]
+    L.pih_render_cam.argtypes = [vp, vp, C.POINTER(C.c_float * CAM_WORDS), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]
     L.pih_grasp_labels.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp]
     L.pih_reseed.argtypes = [vp, C.c_uint64]
     L.pih_timing.argtypes = [vp, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int64)]

@@ -1,0 +1,201 @@
+// pih_fly_render.h -- a free camera for the 'random-fly' task (pih_render_cam, include/pih.h): the UR5's six collision capsules, the
+// object's sphere cover and the table plane, ray-cast from a caller-given viewpoint.
+//
+// The task class is not in the reference snapshot, so there is no prescribed camera pose: the camera comes from the caller in the terms
+// of p.computeViewMatrix (eye, target, up) and p.computeProjectionMatrixFOV (fov, aspect, near, far), the image in the layout of
+// p.getCameraImage as PegInHole.render uses it (envs/peg_in_hole.py:276-304): (depth-buffer value, r, g, b) per pixel.
+//   basis   f = normalize(target - eye), s = normalize(f x up), u = s x f                          (computeViewMatrix)
+//   pixel   (i, j), row 0 on top: xc = (2 (j + 1/2) / W - 1) tan(fov / 2) aspect, yc = (1 - 2 (i + 1/2) / H) tan(fov / 2),
+//           ray d = normalize(f + xc s + yc u); the eye-space depth of a hit at ray parameter t is z = t (d . f)
+//   scene   (env-local frame) the plane z = PIH_TABLE_Z; link capsules o_L + R_L CAP_A[L] .. o_L + R_L CAP_B[L], radius CAP_R[L], with the
+//           link frames of fly::step_env; the object's first NSPH spheres at opos + R(oquat) SPH_C
+//   hit     the nearest one with near <= z <= far; a primitive's hit outside [near, far] is dropped and the ray goes on to the others
+//   depth   far (z - near) / (z (far - near)), 1 where nothing was hit
+//   rgb     0 .. 255: table 153, link L 255 PIH_UR5_RGB[L], object 255 PIH_FLY_OBJ_RGB[object], nothing 255; PIH_RENDER_SHADED multiplies
+//           by ambient + diffuse max(0, n . l) of pih_raycast.h (n: +z on the table, radial on capsules and spheres)
+// PIH_RENDER_CAM_EE: eye, target and up are given in the ee_link frame of the env's UR5 (chain_ee<Ur5Chain>) -- an eye-in-hand camera.
+//
+// Mapping (as pih_render.h): one 256-thread workgroup per (env, strip of rows), the scene once per workgroup in LDS; each WAVE walks
+// 16-row x 64-column tiles; lane i < FLY_NPRIM tests the conservative screen bound of primitive i (camera coordinates; a capsule's bound
+// is the union of its two end spheres' bounds; a sphere that reaches the eye plane keeps its primitive on for every tile) against the
+// tile, the ballot is the tile's primitive list, one tile row is one coalesced 1 KB store.
+// Everything here is PIH_HD on `real`: the host build of tests/emul compiles the same per-scene and per-pixel code in fp64 and fp32.
+#pragma once
+#include "pih_common.h"
+#include "pih_raycast.h"
+
+namespace pih {
+namespace fly {
+
+constexpr int RCAP = PIH_UR5_NJ, RSPH = PIH_FLY_OBJ_MAXSPH;
+constexpr int FLY_NPRIM = RCAP + RSPH;      // primitive i: capsule of link i (i < RCAP), object sphere i - RCAP
+static_assert(FLY_NPRIM <= 32, "the tile's primitive list is a 32-bit mask");
+// colour classes of a pixel = rows of FlyScene::rgb: link L, then
+constexpr int KIND_OBJECT = RCAP, KIND_TABLE = RCAP + 1, KIND_NONE = RCAP + 2, NKIND = RCAP + 3;
+
+PIH_CONST real R_UR5_RGB[RCAP][3] = PIH_UR5_RGB;
+PIH_CONST real R_OBJ_RGB[PIH_FLY_NOBJ][3] = PIH_FLY_OBJ_RGB;
+PIH_CONST real R_CAP_A[RCAP][3] = PIH_UR5_CAP_A;
+PIH_CONST real R_CAP_B[RCAP][3] = PIH_UR5_CAP_B;
+PIH_CONST real R_CAP_R[RCAP] = PIH_UR5_CAP_R;
+PIH_CONST int R_NSPH[PIH_FLY_NOBJ] = PIH_FLY_OBJ_NSPH;
+PIH_CONST real R_SPH_C[PIH_FLY_NOBJ][RSPH][3] = PIH_FLY_OBJ_SPH_C;
+PIH_CONST real R_SPH_R[PIH_FLY_NOBJ][RSPH] = PIH_FLY_OBJ_SPH_R;
+
+// the camera as the caller gives it (PIH_CAM_WORDS floats, passed to the kernel by value)
+struct FlyCam { float w[PIH_CAM_WORDS]; };
+enum : int { CAM_EYE = 0, CAM_TARGET = 3, CAM_UP = 6, CAM_FOV = 9, CAM_ASPECT = 10, CAM_NEAR = 11, CAM_FAR = 12 };
+static_assert(CAM_FAR + 1 == PIH_CAM_WORDS, "camera words (include/pih.h)");
+// the words of an env's state record the camera needs
+struct FlyPose { real q[RCAP], opos[3], oquat[4]; };
+
+struct FlyScene {
+  real eye[3], s[3], u[3], f[3];            // camera position and basis (env-local frame)
+  real tx, ty, znear, zfar;                 // tan(fov / 2) aspect, tan(fov / 2), clip planes
+  real cap[RCAP][2][3], capr[RCAP];         // capsule end points and radii
+  real sph[RSPH][3], sphr[RSPH];
+  real bnd[FLY_NPRIM][4];                   // screen bound (u0, u1, v0, v1) of every primitive; u0 > u1 = "always on"
+  real rgb[NKIND][3];
+};
+
+// Scene set-up, part 1 (threads 0 .. 15 of the workgroup do something): thread L < 6 walks the chain to link L and places its capsule,
+// thread 6 walks it to ee_link and builds the camera basis, threads 8 .. 12 place the object's spheres, thread 15 fills the colours.
+PIH_HD void scene_setup_poses(FlyScene& sc, const FlyPose& ps, const FlyCam& cam, int object, int flags, int tid) {
+  if (tid <= RCAP) {
+    // link frames as fly::step_env builds them: R_L = R_parent RFIX[L] rot(AXIS[L], q[L]), o_L = o_parent + R_parent TFIX[L]
+    M3 R = ldm(IDENT3); V3 org = ld3(UR5_BASE_T);
+    const int last = tid < RCAP ? tid : RCAP - 1;
+#pragma unroll
+    for (int L = 0; L < RCAP; L++) {                  // (unrolled: q[L] stays in registers)
+      if (L > last) break;
+      org = org + mul(R, ld3(UR5_TFIX[L]));
+      R = mul(mul(R, ldm(UR5_RFIX[L])), axis_angle(ld3(UR5_AXIS[L]), ps.q[L]));
+    }
+    if (tid < RCAP) {
+      st3(sc.cap[tid][0], org + mul(R, ld3(R_CAP_A[tid]))); st3(sc.cap[tid][1], org + mul(R, ld3(R_CAP_B[tid])));
+      sc.capr[tid] = R_CAP_R[tid];
+    } else {
+      V3 eye = mk((real)cam.w[CAM_EYE], (real)cam.w[CAM_EYE + 1], (real)cam.w[CAM_EYE + 2]);
+      V3 tgt = mk((real)cam.w[CAM_TARGET], (real)cam.w[CAM_TARGET + 1], (real)cam.w[CAM_TARGET + 2]);
+      V3 up = mk((real)cam.w[CAM_UP], (real)cam.w[CAM_UP + 1], (real)cam.w[CAM_UP + 2]);
+      if (flags & PIH_RENDER_CAM_EE) {
+        const M3 Re = mul(R, ldm(UR5_EE_R)); const V3 pe = org + mul(R, ld3(UR5_EE_T));
+        eye = pe + mul(Re, eye); tgt = pe + mul(Re, tgt); up = mul(Re, up);
+      }
+      V3 f = tgt - eye; f = rsqrt_(dot(f, f)) * f;
+      V3 s = cross(f, up); s = rsqrt_(dot(s, s)) * s;
+      st3(sc.eye, eye); st3(sc.f, f); st3(sc.s, s); st3(sc.u, cross(s, f));
+      real sn, cs; sincos_((real)cam.w[CAM_FOV] * (PIH_PI / (real)360), &sn, &cs);
+      sc.ty = sn / cs; sc.tx = sc.ty * (real)cam.w[CAM_ASPECT];
+      sc.znear = (real)cam.w[CAM_NEAR]; sc.zfar = (real)cam.w[CAM_FAR];
+    }
+  } else if (tid >= 8 && tid < 8 + RSPH) {
+    const int i = tid - 8;
+    Q4 oq; oq.x = ps.oquat[0]; oq.y = ps.oquat[1]; oq.z = ps.oquat[2]; oq.w = ps.oquat[3];
+    st3(sc.sph[i], ld3(ps.opos) + mul(q_to_m(oq), ld3(R_SPH_C[object][i])));
+    sc.sphr[i] = R_SPH_R[object][i];
+  } else if (tid == 15) {
+    for (int c = 0; c < 3; c++) {
+      for (int L = 0; L < RCAP; L++) sc.rgb[L][c] = (real)255 * R_UR5_RGB[L][c];
+      sc.rgb[KIND_OBJECT][c] = (real)255 * R_OBJ_RGB[object][c];
+      sc.rgb[KIND_TABLE][c] = PIH_COL_TABLE; sc.rgb[KIND_NONE][c] = PIH_COL_BG;
+    }
+  }
+}
+// part 2, after a barrier (threads 0 .. FLY_NPRIM - 1): the screen bound of primitive `tid` in camera coordinates
+PIH_HD V3 to_camera(const FlyScene& sc, V3 p) {      // (x right, y up, z = -depth: what sphere_bound takes)
+  const V3 rel = p - ld3(sc.eye);
+  return mk(dot(rel, ld3(sc.s)), dot(rel, ld3(sc.u)), -dot(rel, ld3(sc.f)));
+}
+PIH_HD void scene_setup_bounds(FlyScene& sc, int object, int tid) {
+  if (tid >= FLY_NPRIM) return;
+  real u0 = 1, u1 = -1, v0 = 1, v1 = -1;              // "cannot bound": keep for every tile
+  if (tid < RCAP) {
+    real a0, a1, b0, b1, c0, c1, d0, d1;
+    if (sphere_bound(to_camera(sc, ld3(sc.cap[tid][0])), sc.capr[tid], a0, a1, b0, b1) && sphere_bound(to_camera(sc, ld3(sc.cap[tid][1])), sc.capr[tid], c0, c1, d0, d1)) {
+      u0 = a0 < c0 ? a0 : c0; u1 = a1 > c1 ? a1 : c1; v0 = b0 < d0 ? b0 : d0; v1 = b1 > d1 ? b1 : d1;
+    }
+  } else if (tid - RCAP < R_NSPH[object]) {
+    real a0, a1, b0, b1;
+    if (sphere_bound(to_camera(sc, ld3(sc.sph[tid - RCAP])), sc.sphr[tid - RCAP], a0, a1, b0, b1)) { u0 = a0; u1 = a1; v0 = b0; v1 = b1; }
+  } else {
+    u0 = u1 = v0 = v1 = PIH_BIG;                      // padding sphere of the object table: on no tile
+  }
+  sc.bnd[tid][0] = u0; sc.bnd[tid][1] = u1; sc.bnd[tid][2] = v0; sc.bnd[tid][3] = v1;
+}
+
+// does primitive `i` (this lane's) touch the tile [tu0, tu1] x [tv0, tv1] of the camera plane?
+PIH_HD bool prim_on_tile(const FlyScene& sc, int i, real tu0, real tu1, real tv0, real tv1) {
+  if (i >= FLY_NPRIM) return false;
+  const real u0 = sc.bnd[i][0], u1 = sc.bnd[i][1], v0 = sc.bnd[i][2], v1 = sc.bnd[i][3];
+  if (u0 > u1) return true;
+  return !(u1 < tu0 || u0 > tu1 || v1 < tv0 || v0 > tv1);
+}
+// the mask with every primitive of the object on (what a tile without culling sees)
+PIH_HD unsigned all_prims(int object) { return (1u << (RCAP + R_NSPH[object])) - 1u; }
+
+// one pixel: xc, yc = camera-plane coordinates of the pixel centre (already multiplied by tx / ty); prims = bit i set if primitive i
+// may cover the pixel (wave-uniform)
+PIH_HD real4 shade(const FlyScene& sc, unsigned prims, real xc, real yc, int flags) {
+  const V3 eye = ld3(sc.eye);
+  const real inv = rsqrt_((real)1 + xc * xc + yc * yc);      // = d . f
+  const V3 d = inv * (ld3(sc.f) + xc * ld3(sc.s) + yc * ld3(sc.u));
+  const real tnear = sc.znear / inv, tfar = sc.zfar / inv;   // ray parameters of the clip planes
+  real best = PIH_BIG;
+  int kind = KIND_NONE, which = 0;
+  if (absr(d.z) > (real)1e-30) {
+    const real t = ((real)PIH_TABLE_Z - eye.z) / d.z;
+    if (t >= tnear && t <= tfar) { best = t; kind = KIND_TABLE; }
+  }
+  unsigned caps = prims & ((1u << RCAP) - 1u);
+  while (caps) {
+    const int L = __builtin_ctz(caps); caps &= caps - 1u;
+    const real t = ray_capsule(eye, d, ld3(sc.cap[L][0]), ld3(sc.cap[L][1]), sc.capr[L]);
+    if (t < best && t >= tnear && t <= tfar) { best = t; kind = L; }
+  }
+  unsigned sphs = prims >> RCAP;
+  while (sphs) {
+    const int i = __builtin_ctz(sphs); sphs &= sphs - 1u;
+    const real t = ray_sphere(eye - ld3(sc.sph[i]), d, sc.sphr[i]);
+    if (t < best && t >= tnear && t <= tfar) { best = t; kind = KIND_OBJECT; which = i; }
+  }
+  real depth = 1;
+  if (kind != KIND_NONE) {
+    const real z = best * inv;
+    depth = sc.zfar * (z - sc.znear) / (z * (sc.zfar - sc.znear));
+  }
+  real lit = 1;
+  if ((flags & PIH_RENDER_SHADED) && kind != KIND_NONE) {
+    // surface normal at the hit point, Lambert term against the fixed light
+    const V3 ph = eye + best * d;
+    V3 n = mk(0, 0, 1);
+    if (kind < RCAP) {
+      const V3 a = ld3(sc.cap[kind][0]), ba = ld3(sc.cap[kind][1]) - a;
+      real q = dot(ph - a, ba) / max_(dot(ba, ba), (real)1e-20);
+      q = q < 0 ? (real)0 : (q > 1 ? (real)1 : q);
+      const V3 r = ph - (a + q * ba);
+      n = ((real)1 / max_(norm(r), (real)1e-12)) * r;
+    } else if (kind == KIND_OBJECT) {
+      const V3 r = ph - ld3(sc.sph[which]);
+      n = ((real)1 / max_(norm(r), (real)1e-12)) * r;
+    }
+    const real ndl = n.x * PIH_LIGHT_X + n.y * PIH_LIGHT_Y + n.z * PIH_LIGHT_Z;
+    lit = PIH_LIGHT_AMBIENT + PIH_LIGHT_DIFFUSE * max_(ndl, (real)0);
+  }
+  real4 o; o.x = depth; o.y = sc.rgb[kind][0] * lit; o.z = sc.rgb[kind][1] * lit; o.w = sc.rgb[kind][2] * lit;
+  return o;
+}
+
+// The pixel grid, shared by the kernel and the host build: pixel-centre and tile-edge coordinates on the camera plane
+struct FlyGrid {
+  real sx, sy, tx, ty;
+  PIH_HD FlyGrid(const FlyScene& sc, int W, int H) : sx((real)2 / (real)W), sy((real)2 / (real)H), tx(sc.tx), ty(sc.ty) {}
+  PIH_HD real xc(int j) const { return (sx * ((real)j + (real)0.5) - (real)1) * tx; }
+  PIH_HD real yc(int i) const { return ((real)1 - sy * ((real)i + (real)0.5)) * ty; }
+  PIH_HD real xedge(int j) const { return (sx * (real)j - (real)1) * tx; }
+  PIH_HD real yedge(int i) const { return ((real)1 - sy * (real)i) * ty; }
+};
+constexpr int TILE_ROWS = 16, TILE_COLS = 64;        // one row of a tile per wave instruction
+
+}  // namespace fly
+}  // namespace pih

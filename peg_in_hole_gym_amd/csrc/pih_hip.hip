@@ -10,6 +10,7 @@
 #include "pih_device.h"
 #include "pih_render.h"
 #include "pih_fly.h"
+#include "pih_fly_render.h"
 
 using namespace pih;
 
@@ -237,6 +238,48 @@ __global__ void __launch_bounds__(RENDER_THREADS) pih_render_kernel(const float*
       for (int i = i0; i < i1; i++) {
         real4 c = shade(sc, prims, xc, (1.0f - sy * (i + 0.5f)) * T, flags);
         img[i * W + j] = make_float4(c.x, c.y, c.z, c.w);
+      }
+    }
+  }
+}
+
+// free camera of the random-fly task (pih_fly_render.h): grid = (strips, envs), 256 threads (4 waves); out float[count, H, W, 4] = depth,
+// r, g, b.  state is structure-of-arrays: the 13 words the scene needs are wave-uniform (scalar) loads.
+__global__ void __launch_bounds__(RENDER_THREADS) pih_fly_render_kernel(const float* __restrict__ state, float* __restrict__ out, fly::FlyCam cam,
+                                                                        int n, int object, int env_begin, int W, int H, int rows_per_strip, int flags) {
+  using namespace fly;
+  __shared__ FlyScene sc;
+  const int tid = threadIdx.x, e = blockIdx.y, env = env_begin + e;
+  const int r0 = blockIdx.x * rows_per_strip, r1 = min(H, r0 + rows_per_strip);
+  if (tid < 16) {
+    FlyPose ps;
+    const float* rec = state + env;
+#pragma unroll
+    for (int i = 0; i < 6; i++) ps.q[i] = rec[(size_t)(PIH_F_Q + i) * n];
+#pragma unroll
+    for (int i = 0; i < 3; i++) ps.opos[i] = rec[(size_t)(PIH_F_OPOS + i) * n];
+#pragma unroll
+    for (int i = 0; i < 4; i++) ps.oquat[i] = rec[(size_t)(PIH_F_OQUAT + i) * n];
+    scene_setup_poses(sc, ps, cam, object, flags, tid);
+  }
+  __syncthreads();
+  scene_setup_bounds(sc, object, tid);
+  __syncthreads();
+  const FlyGrid g(sc, W, H);
+  float4* img = reinterpret_cast<float4*>(out) + (size_t)e * H * W;
+  const int lane = tid & 63, wave = tid >> 6;
+  const int tcols = (W + TILE_COLS - 1) / TILE_COLS, trows = (r1 - r0 + TILE_ROWS - 1) / TILE_ROWS;
+  for (int tile = wave; tile < tcols * trows; tile += RENDER_THREADS / 64) {
+    const int ti = tile / tcols, tj = tile - ti * tcols;
+    const int i0 = r0 + ti * TILE_ROWS, i1 = min(r1, i0 + TILE_ROWS), j0 = tj * TILE_COLS, j1 = min(W, j0 + TILE_COLS);
+    // camera-plane rectangle of the tile's pixel edges (row 0 is the top of the image, v grows upwards)
+    const unsigned prims = (unsigned)__ballot(prim_on_tile(sc, lane, g.xedge(j0), g.xedge(j1), g.yedge(i1), g.yedge(i0)));
+    const int j = j0 + lane;
+    if (j < j1) {
+      const float xc = g.xc(j);
+      for (int i = i0; i < i1; i++) {
+        real4 c = shade(sc, prims, xc, g.yc(i), flags);
+        img[(size_t)i * W + j] = make_float4(c.x, c.y, c.z, c.w);
       }
     }
   }
@@ -804,6 +847,17 @@ int pih_ik_ur5(pih_handle* h, int n, const float* q0_dev, const float* tpos_dev,
   return 0;
 }
 
+// rows per workgroup of the two cameras.  Every workgroup sets its env's scene up once (forward kinematics): few strips per env when the
+// batch alone gives the chip several rounds of workgroups (>= 8192: images differ ~3x in cost, the tail matters), more strips for small
+// batches.  Returns the number of strips; *rows = rows per strip, a multiple of the 16-row tile.
+static int render_strips(int height, int env_count, int* rows) {
+  int strips = (8192 + env_count - 1) / env_count;
+  const int max_strips = (height + 31) / 32;
+  strips = strips < 1 ? 1 : (strips > max_strips ? max_strips : strips);
+  *rows = ((height + strips - 1) / strips + 15) / 16 * 16;
+  return (height + *rows - 1) / *rows;
+}
+
 int pih_render(pih_handle* h, float* out_dev, int width, int height, int env_begin, int env_count, void* stream) {
   return pih_render_ex(h, out_dev, width, height, env_begin, env_count, 0, stream);
 }
@@ -816,15 +870,44 @@ int pih_render_ex(pih_handle* h, float* out_dev, int width, int height, int env_
   if (h->fly) { h->err = "pih_render: the wrist camera belongs to the peg-in-hole task"; return -2; }
   if ((reinterpret_cast<uintptr_t>(out_dev) & 15) != 0) { h->err = "pih_render: out_dev must be 16-byte aligned"; return -2; }
   PIH_ENTER(h);
-  // every workgroup runs the forward kinematics of its env once: few strips per env when the batch alone gives the chip
-  // several rounds of workgroups (>= 8192: images differ ~3x in cost, the tail matters), more strips for small batches
-  int strips = (8192 + env_count - 1) / env_count;
-  const int max_strips = (height + 31) / 32;
-  strips = strips < 1 ? 1 : (strips > max_strips ? max_strips : strips);
-  const int rows = ((height + strips - 1) / strips + 15) / 16 * 16;
-  strips = (height + rows - 1) / rows;
+  int rows; const int strips = render_strips(height, env_count, &rows);
   if (env_count > 65535) { h->err = "pih_render: env_count > 65535 per call"; return -2; }
   hipLaunchKernelGGL(pih_render_kernel, dim3(strips, env_count), dim3(RENDER_THREADS), 0, (hipStream_t)stream, h->state, out_dev, env_begin, width, height, rows, flags);
+  HIPCHK(h, hipGetLastError());
+  return 0;
+}
+
+int pih_render_cam(pih_handle* h, float* out_dev, const float* cam_host, int width, int height, int env_begin, int env_count, int flags, void* stream) {
+  if (!h || !out_dev || width <= 0 || height <= 0 || env_begin < 0 || env_count <= 0 || env_begin + env_count > h->cfg.n_envs ||
+      (flags & ~(PIH_RENDER_SHADED | PIH_RENDER_CAM_EE)) != 0) {
+    if (h) h->err = "pih_render_cam: bad arguments";
+    return -2;
+  }
+  if (!h->fly) { h->err = "pih_render_cam: the free camera belongs to the random-fly task (peg-in-hole: pih_render / pih_render_ex)"; return -2; }
+  if ((reinterpret_cast<uintptr_t>(out_dev) & 15) != 0) { h->err = "pih_render_cam: out_dev must be 16-byte aligned"; return -2; }
+  if (env_count > 65535) { h->err = "pih_render_cam: env_count > 65535 per call"; return -2; }
+  static const float cam_default[PIH_CAM_WORDS] = PIH_FLY_CAM_DEFAULT;
+  fly::FlyCam cam;
+  memcpy(cam.w, cam_host ? cam_host : cam_default, sizeof cam.w);
+  {
+    // degenerate cameras (the tests are frame-independent, so they hold for PIH_RENDER_CAM_EE as well); !(a > b) also catches NaN
+    const float* c = cam.w;
+    const double f[3] = {(double)c[3] - c[0], (double)c[4] - c[1], (double)c[5] - c[2]}, up[3] = {c[6], c[7], c[8]};
+    const double fl = sqrt(f[0] * f[0] + f[1] * f[1] + f[2] * f[2]), ul = sqrt(up[0] * up[0] + up[1] * up[1] + up[2] * up[2]);
+    const double cx = f[1] * up[2] - f[2] * up[1], cy = f[2] * up[0] - f[0] * up[2], cz = f[0] * up[1] - f[1] * up[0];
+    const char* bad = nullptr;
+    if (!(fl > 1e-9 && fl < 1e15)) bad = "eye == target (or not finite)";
+    else if (!(ul > 0 && ul < 1e15 && sqrt(cx * cx + cy * cy + cz * cz) > 1e-6 * fl * ul)) bad = "up is zero or parallel to the view axis target - eye";
+    else if (!(c[fly::CAM_FOV] > 0.f && c[fly::CAM_FOV] < 180.f)) bad = "fov outside (0, 180) degrees";
+    else if (!(c[fly::CAM_ASPECT] > 0.f && c[fly::CAM_ASPECT] < 1e15f)) bad = "aspect <= 0";
+    else if (!(c[fly::CAM_NEAR] > 0.f && c[fly::CAM_NEAR] < 1e15f)) bad = "near <= 0";
+    else if (!(c[fly::CAM_FAR] > c[fly::CAM_NEAR] && c[fly::CAM_FAR] < 1e15f)) bad = "far <= near";
+    if (bad) { h->err = std::string("pih_render_cam: degenerate camera: ") + bad; return -2; }
+  }
+  PIH_ENTER(h);
+  int rows; const int strips = render_strips(height, env_count, &rows);
+  hipLaunchKernelGGL(pih_fly_render_kernel, dim3(strips, env_count), dim3(RENDER_THREADS), 0, (hipStream_t)stream, h->state, out_dev, cam,
+                     h->cfg.n_envs, h->P.object, env_begin, width, height, rows, flags);
   HIPCHK(h, hipGetLastError());
   return 0;
 }

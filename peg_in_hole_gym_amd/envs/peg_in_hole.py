@@ -6,6 +6,7 @@ was generated from, and how the reference's constructor `args` map to library se
 library for ONE agent, so code written against the reference's task objects keeps working."""
 import numpy as np
 
+from .. import _lib
 from .utils import Box
 
 
@@ -129,6 +130,7 @@ class RandomFly(MetaEnv):
     urEndEffectorIndex = 7
     urNumDofs = 6
     OBJECTS = _objects_from_model_header()
+    CAMERA = _lib.FLY_CAM_DEFAULT      # eye, target, up, fov, aspect, near, far of render() (build-defined: the task class and its camera are absent)
 
     @classmethod
     def cfg_from_args(cls, args):
@@ -140,3 +142,9 @@ class RandomFly(MetaEnv):
         if len(args) > 1:
             kw["dt"] = float(args[1])
         return kw
+
+    def render(self, mode="rgb_array", camera=None, ee_frame=False):
+        """[300,300,4] = depth, r, g, b (shaded) like PegInHole.render, from `camera` (13 numbers: eye, target, up, fov, aspect, near,
+        far; None = CAMERA) in the env-local frame, or with ee_frame=True in the UR5's ee_link frame (eye-in-hand)"""
+        img = self._backend.render(300, 300, shaded=True, camera=camera, ee_frame=ee_frame)
+        return (img.detach().cpu().numpy() if hasattr(img, "detach") else np.asarray(img))[0].astype(np.float64)

@@ -187,15 +187,34 @@ class PihVecEnv:
             self._chk(self.L.pih_ik_ur5(self.h, n, q0.data_ptr(), tpos.data_ptr(), tquat.data_ptr(), out.data_ptr(), self._stream()), "pih_ik_ur5")
         return out
 
-    def render(self, width=300, height=300, env_begin=0, env_count=None, out=None, shaded=False):
-        """PegInHole.render (envs/peg_in_hole.py:276-304) for a block of envs: float32 [count, height, width, 4] =
-        (depth buffer, r, g, b) from the wrist camera at the current state (analytic ray caster).  RGB is one flat value per
-        object, or (shaded=True) that value times ambient + diffuse of TinyRenderer's default light (pih_render_ex)."""
+    def render(self, width=300, height=300, env_begin=0, env_count=None, out=None, shaded=False, camera=None, ee_frame=False):
+        """Camera image of a block of envs at the current state (analytic ray caster): float32 [count, height, width, 4] =
+        (depth buffer, r, g, b), RGB on the 0..255 scale, flat per object or (shaded=True) times ambient + diffuse of TinyRenderer's
+        default light.
+        peg-in-hole: PegInHole.render (envs/peg_in_hole.py:276-304), the wrist camera (pih_render_ex); the camera is fixed, so
+            `camera` / `ee_frame` raise ValueError.
+        random-fly: a free camera over the UR5's capsules, the object and the table (pih_render_cam).  camera = 13 numbers (eye xyz,
+            target xyz, up xyz, vertical fov in degrees, aspect, near, far: the arguments of computeViewMatrix and
+            computeProjectionMatrixFOV) or None = _lib.FLY_CAM_DEFAULT, one camera for all envs of the call, in each env's local frame
+            (the env offset does not enter); ee_frame=True: in the ee_link frame of each env's UR5 (eye-in-hand)."""
         count = self.n - env_begin if env_count is None else env_count
+        fly = self.task_id == _lib.TASK_RANDOM_FLY
+        if not fly and (camera is not None or ee_frame):
+            raise ValueError("render: the peg-in-hole task has a fixed wrist camera; camera / ee_frame belong to the random-fly task")
+        cam = None
+        if camera is not None:
+            vals = [float(x) for x in camera]
+            if len(vals) != _lib.CAM_WORDS:
+                raise ValueError("render: camera must have %d numbers (eye, target, up, fov, aspect, near, far), got %d" % (_lib.CAM_WORDS, len(vals)))
+            cam = (C.c_float * _lib.CAM_WORDS)(*vals)
         if out is None:
             out = torch.empty(count, height, width, 4, device=self.device)
         with torch.cuda.device(self.device):
-            self._chk(self.L.pih_render_ex(self.h, out.data_ptr(), width, height, env_begin, count, 1 if shaded else 0, self._stream()), "pih_render_ex")
+            if fly:
+                flags = (_lib.RENDER_SHADED if shaded else 0) | (_lib.RENDER_CAM_EE if ee_frame else 0)
+                self._chk(self.L.pih_render_cam(self.h, out.data_ptr(), cam, width, height, env_begin, count, flags, self._stream()), "pih_render_cam")
+            else:
+                self._chk(self.L.pih_render_ex(self.h, out.data_ptr(), width, height, env_begin, count, 1 if shaded else 0, self._stream()), "pih_render_ex")
         return out
 
     def grasp_labels(self, size=300, env_begin=0, env_count=None):

@@ -304,6 +304,7 @@ for k in range(6):
 print("#define PIH_UR5_CAP_A {" + ", ".join(arr(np.round(c[0], 9)) for c in caps) + "}   /* capsule end points / radius in the link frame */")
 print("#define PIH_UR5_CAP_B {" + ", ".join(arr(np.round(c[1], 9)) for c in caps) + "}")
 print("#define PIH_UR5_CAP_R " + arr(round(c[2], 9) for c in caps))
+print("#define PIH_UR5_RGB {" + ", ".join(arr(c) for c in UR5["rgb"]) + "}   /* <material> colour of each link's visual (the fly camera, pih_render_cam) */")
 print("#define PIH_UR5_REST {0.0, %s, %s, %s, %s, 0.0}   /* BUILD-DEFINED rest pose (the reference passes ur_orn from a task that is not in the snapshot) */" % (
     fmt(-math.pi / 2), fmt(math.pi / 2), fmt(-math.pi / 2), fmt(-math.pi / 2)))
 # ----------------------------------------------------------------------------- free-flying objects of the random-fly task

@@ -1,9 +1,52 @@
 #!/usr/bin/env python3
-"""Timing of pih_render (wrist camera, 300x300) and pih_grasp_labels for a block of envs."""
+"""Timing of pih_render (wrist camera, 300x300) and pih_grasp_labels for a block of envs.
+usage: render_bench.py [n]
+       render_bench.py --task random-fly [--n N] --width W --height H [--repeats K]
+           the free camera of the random-fly task (pih_render_cam, default camera), flat and shaded, alternating with the peg-in-hole wrist
+           camera at the same n and size as the yardstick of the same run; stores = 16 bytes per pixel against the 6.3 TB/s of HBM
+           bandwidth a kernel can reach on the MI355X"""
 import sys, os, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from peg_in_hole_gym_amd.vec_env import PihVecEnv
+
+
+def _arg(name, default):
+    return type(default)(sys.argv[sys.argv.index(name) + 1]) if name in sys.argv else default
+
+
+def fly_bench():
+    n, W, H, K = _arg("--n", 1024), _arg("--width", 300), _arg("--height", 300), max(5, _arg("--repeats", 5))
+    HBM = 6.3e12
+    fly = PihVecEnv(n, task_id=1, max_episode_steps=480, contact_margin=0.02, dt=1.0 / 120.0, seed=1)
+    act = torch.zeros(n, 6, device="cuda"); act[:, 0] = 0.4; act[:, 2] = 0.5
+    fly.step_n(20, act)                          # objects in flight, arms off their rest pose
+    peg = PihVecEnv(n, mode=1, dv=0.05)
+    peg.step_n(540)
+    out = torch.empty(n, H, W, 4, device="cuda")
+    cases = (("random-fly flat", lambda: fly.render(W, H, out=out)), ("random-fly shaded", lambda: fly.render(W, H, out=out, shaded=True)),
+             ("peg-in-hole flat", lambda: peg.render(W, H, out=out)))
+    for _, f in cases:                           # warm-up
+        for _ in range(2):
+            f()
+    torch.cuda.synchronize()
+    ms = {name: [] for name, _ in cases}
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+    for _ in range(K):                           # alternating: every repeat times each case once
+        for name, f in cases:
+            ev[0].record(); f(); ev[1].record(); ev[1].synchronize()
+            ms[name].append(ev[0].elapsed_time(ev[1]))
+    for name, _ in cases:
+        v = sorted(ms[name]); med = v[len(v) // 2]
+        print("%-18s %d envs x %dx%d: median %.3f ms (min %.3f, max %.3f, %d repeats) = %.0f Mpixel/s, %.2f TB/s stored = %.0f %% of 6.3 TB/s"
+              % (name, n, W, H, med, v[0], v[-1], K, n * W * H / med / 1e3, n * W * H * 16 / med / 1e9, 100 * n * W * H * 16 / (med * 1e-3) / HBM))
+
+
+if "--task" in sys.argv:
+    if _arg("--task", "") != "random-fly":
+        sys.exit("render_bench.py: --task takes random-fly (the peg-in-hole timing is the default: render_bench.py [n])")
+    fly_bench()
+    sys.exit(0)
 
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 1024
 g = PihVecEnv(n, mode=1, dv=0.05)

@@ -167,7 +167,7 @@ def ur5_tables(ref_root):
     return {"base_xyz": fixed[0]["xyz"], "rpy": [j["rpy"] for j in rev], "xyz": [j["xyz"] for j in rev], "axis": [j["axis"] for j in rev],
             "effort": [j["effort"] for j in rev], "damping": [j["damping"] for j in rev], "ee_rpy": fixed[-1]["rpy"], "ee_xyz": fixed[-1]["xyz"],
             "lower": [float(j["lower"]) for j in rev], "upper": [float(j["upper"]) for j in rev],
-            "mass": [u.links[l]["mass"] for l in links], "com": [u.links[l]["com"] for l in links],
+            "mass": [u.links[l]["mass"] for l in links], "com": [u.links[l]["com"] for l in links], "rgb": [u.links[l]["rgba"][:3] for l in links],
             "aabb": [[a.tolist() for a in u.mesh_aabb(l)] for l in links],
             "ee_mass": u.links[ee]["mass"], "ee_com": u.links[ee]["com"], "ee_aabb": [a.tolist() for a in u.mesh_aabb(ee)]}
 
