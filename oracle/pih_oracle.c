@@ -359,6 +359,29 @@ static void arm_jacobian(const LinkKin* K, const v3 p, real* Jl, real* Ja) { /* 
     L = L_PARENT[L];
   }
 }
+/* Orientation part of the IK error: angle * axis of deltaQ = target * current^-1, angle = 2 acos(w) wrapped to (-pi,pi], axis =
+ * xyz / sqrt(1-w^2) (btQuaternion::getAngle / getAxis).  `tquat` must be a UNIT quaternion, as calculateInverseKinematics gets one from
+ * getQuaternionFromEuler in double: d(2 acos w) = 2 dw / sin(angle / 2) turns the norm error 6e-8 of a quaternion that was rounded to fp32
+ * into 2.4e-4 rad at an orientation error of 1e-3 rad and into 7e-4 rad about a meaningless axis at convergence (tests/ik_cases.py
+ * normalises in double what it hands over; the product's 2 atan2(|xyz|, w) does not depend on the norm).
+ * Below 1 - w^2 = 1e-12 (angle < 2e-6 rad) the same angle and axis are evaluated as 2 atan2(|xyz|, w) and xyz / |xyz|: there acos
+ * amplifies the fp64 rounding of w itself, up to 3e-8 rad about a meaningless axis at w = 1 - 1e-16 (tests/test_ik_domain.py class C
+ * measured 4e-8 rad in q* against the fp64 host build of the product).  Above it the arithmetic is Bullet's, unchanged, and its
+ * rounding stays below 2.2e-10 rad. */
+static void ik_rot_error(const real* tquat, const real* cq, real* e3) {
+  real ci[4] = {-cq[0], -cq[1], -cq[2], cq[3]}, dq[4];
+  q_mul(dq, tquat, ci);
+  real w = clampd(dq[3], -1.0, 1.0), ang = 2.0 * acos(w), s2 = 1.0 - w * w;
+  v3 ax;
+  if (s2 < 1e-12) {
+    real sn = sqrt(dq[0] * dq[0] + dq[1] * dq[1] + dq[2] * dq[2]);
+    ang = 2.0 * atan2(sn, dq[3]);
+    if (sn < 1e-12) v_set(ax, 1, 0, 0); else v_set(ax, dq[0] / sn, dq[1] / sn, dq[2] / sn);
+  } else { real s = 1.0 / sqrt(s2); v_set(ax, dq[0] * s, dq[1] * s, dq[2] * s); }
+  if (ang > PI) ang -= 2 * PI;
+  real an = v_norm(ax); if (an > 0) { ax[0] /= an; ax[1] /= an; ax[2] /= an; }
+  e3[0] = ang * ax[0]; e3[1] = ang * ax[1]; e3[2] = ang * ax[2];
+}
 static void ik_solve(const piho_config* c, const real* q0, const v3 tpos, const real* tquat, real* qout) {
   real q[9]; memcpy(q, q0, sizeof q);
   LinkKin K[ANL];
@@ -370,15 +393,7 @@ static void ik_solve(const piho_config* c, const real* q0, const v3 tpos, const 
     real e[6];
     v_sub(e, tpos, p);
     if (v_norm(e) < c->ik_residual) break;
-    /* deltaQ = target * current^-1 ; angle = 2 acos(w) wrapped to (-pi,pi] ; axis = xyz / sqrt(1-w^2) */
-    real ci[4] = {-cq[0], -cq[1], -cq[2], cq[3]}, dq[4];
-    q_mul(dq, tquat, ci);
-    real w = clampd(dq[3], -1.0, 1.0), ang = 2.0 * acos(w), s2 = 1.0 - w * w;
-    v3 ax;
-    if (s2 < 1e-14) v_set(ax, 1, 0, 0); else { real s = 1.0 / sqrt(s2); v_set(ax, dq[0] * s, dq[1] * s, dq[2] * s); }
-    if (ang > PI) ang -= 2 * PI;
-    real an = v_norm(ax); if (an > 0) { ax[0] /= an; ax[1] /= an; ax[2] /= an; }
-    e[3] = ang * ax[0]; e[4] = ang * ax[1]; e[5] = ang * ax[2];
+    ik_rot_error(tquat, cq, e + 3);
     real J[54];
     arm_jacobian(K, p, J, J + 27);
     real A[81], b[9];
@@ -433,14 +448,7 @@ void piho_ik_ur5(const piho_config* c, const real q0[6], const real tpos[3], con
     ur5_fk(q, R, o, a, p, eR); m_to_q(cq, eR);
     real e[6]; v_sub(e, tpos, p);
     if (v_norm(e) < c->ik_residual) break;
-    real ci[4] = {-cq[0], -cq[1], -cq[2], cq[3]}, dq[4];
-    q_mul(dq, tquat, ci);
-    real w = clampd(dq[3], -1.0, 1.0), ang = 2.0 * acos(w), s2 = 1.0 - w * w;
-    v3 ax;
-    if (s2 < 1e-14) v_set(ax, 1, 0, 0); else { real sc = 1.0 / sqrt(s2); v_set(ax, dq[0] * sc, dq[1] * sc, dq[2] * sc); }
-    if (ang > PI) ang -= 2 * PI;
-    real an = v_norm(ax); if (an > 0) { ax[0] /= an; ax[1] /= an; ax[2] /= an; }
-    e[3] = ang * ax[0]; e[4] = ang * ax[1]; e[5] = ang * ax[2];
+    ik_rot_error(tquat, cq, e + 3);
     real J[36];
     for (int j = 0; j < 6; j++) { v3 r, t; v_sub(r, p, o[j]); v_cross(t, a[j], r); for (int k = 0; k < 3; k++) { J[k * 6 + j] = t[k]; J[(3 + k) * 6 + j] = a[j][k]; } }
     real A[36], b[6];

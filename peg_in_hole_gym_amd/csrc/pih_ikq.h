@@ -18,9 +18,12 @@
 // prefix rotation), so a local transform costs a sin / cos pair and 12 multiply-adds for any chain table.
 //
 // The arithmetic is the algorithm of ik_chain (pih_common.h; BussIK DLS restated [UNVERIFIED], the oracle's ik_solve): same error
-// vector, same J J^T + d I system, same 30-degree step clamp and exit test; sums are associated differently (tests: pih_ik against the
-// oracle, tests/test_gpu_parity.py, tests/test_ur5_chain.py).  `Q` supplies the quad primitives: QuadDpp on the device; the host
-// harness (tests/emul) supplies four threads in lockstep, so the same source is checked on the CPU.
+// vector, same J J^T + d I system, same 30-degree step clamp and exit test; sums are associated differently (tests: both against the
+// oracle over the whole input domain -- every m_to_q branch, the angle wrap, -tquat, the clamp, the exit test in mid-loop, other
+// damping / iteration counts -- in the host builds, tests/test_ik_domain.py, and on the GPU through pih_ik / pih_ik_ur5 with ragged
+// batches and inside the step, tests/test_gpu_ik.py; near the rest pose: tests/test_gpu_parity.py, tests/test_ur5_chain.py).  `Q`
+// supplies the quad primitives: QuadDpp on the device; the host harness (tests/emul) supplies four threads in lockstep, so the same
+// source is checked on the CPU.
 #pragma once
 #include "pih_common.h"
 

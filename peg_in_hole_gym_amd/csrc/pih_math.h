@@ -64,7 +64,8 @@ PIH_HD M3 mul(const M3& a, const M3& b) {
 PIH_HD V3 col(const M3& a, int j) { return mk(a.m[j], a.m[3 + j], a.m[6 + j]); }
 // sin / cos of a JOINT ANGLE inside the IK loop (|a| stays below a few tens of radians: 20 clamped DLS steps from a pose inside the joint
 // limits): three-constant Cody-Waite reduction by pi/2 (exact for |k| < 2^16) and the Cephes single-precision polynomials on
-// [-pi/4, pi/4], |error| < 1.2e-7 -- 21 instructions instead of the device library's general-argument sincosf (which spends most of
+// [-pi/4, pi/4], |error| < 1.2e-7 (measured 9.2e-8 against fp64 over |a| <= 64 and around every multiple of pi/4:
+// tests/test_ik_domain.py) -- 21 instructions instead of the device library's general-argument sincosf (which spends most of
 // its instructions on the range reduction of huge arguments).  The IK evaluates it 140 (Panda) / 120 (UR5) times per env-step, one env
 // per lane, on the critical path of pih_pre_kernel / pih_fly_step_kernel.  fp64 host builds keep the library call.
 template <class T> PIH_HD void sincos_joint(T a, T* s, T* c) { sincos_(a, s, c); }

@@ -48,6 +48,7 @@ def lib(prec):
         L.emul_ik_ur5.argtypes = [C.POINTER(PihConfig), dp, dp, dp, dp]
         L.emul_ikq.argtypes = [C.POINTER(PihConfig), dp, dp, dp, dp, dp]
         L.emul_ikq_ur5.argtypes = [C.POINTER(PihConfig), dp, dp, dp, dp, dp]
+        L.emul_sincos_joint.argtypes = [C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]
         L.emul_fly_create.restype = C.c_void_p
         L.emul_fly_create.argtypes = [C.POINTER(PihConfig), dp, C.c_double]
         L.emul_fly_destroy.argtypes = [C.c_void_p]
@@ -121,6 +122,13 @@ def ikq(q0, tpos, tquat, prec="f64", cfg=None, ur5=False):
     q0 = np.ascontiguousarray(q0, dtype=np.float64); tp = np.ascontiguousarray(tpos, dtype=np.float64)
     tq = np.ascontiguousarray(tquat, dtype=np.float64); out = np.zeros(6 if ur5 else 9); ee = np.zeros((4, 12))
     (lib(prec).emul_ikq_ur5 if ur5 else lib(prec).emul_ikq)(C.byref(cfg), _dp(q0), _dp(tp), _dp(tq), _dp(out), _dp(ee)); return out, ee
+
+
+def sincos_joint(a, prec="f32"):
+    """sincos_joint<real> of pih_math.h on a float32 array -> (sin, cos) as float32"""
+    a = np.ascontiguousarray(a, dtype=np.float32); s = np.empty_like(a); c = np.empty_like(a)
+    fp = C.POINTER(C.c_float)
+    lib(prec).emul_sincos_joint(a.size, a.ctypes.data_as(fp), s.ctypes.data_as(fp), c.ctypes.data_as(fp)); return s, c
 
 
 class EmulFly:

@@ -129,6 +129,10 @@ void emul_ikq(const pih_config* c, const double* q0, const double* tpos, const d
 void emul_ikq_ur5(const pih_config* c, const double* q0, const double* tpos, const double* tquat, double* qout, double* ee_out) {
   ikq_host<Ur5Chain>(c, q0, tpos, tquat, qout, ee_out);
 }
+// sincos_joint<real> (pih_math.h) on an array: in the f32 build the hand-written reduction + polynomials (tests/test_ik_domain.py)
+void emul_sincos_joint(int n, const float* a, float* s, float* c) {
+  for (int i = 0; i < n; i++) { real sn, cs; sincos_joint<real>((real)a[i], &sn, &cs); s[i] = (float)sn; c[i] = (float)cs; }
+}
 
 // ---- 'random-fly' task (pih_fly.h): the same per-lane scalar code the GPU runs, one env after the other
 struct EmulFly { Params P; int n; std::vector<real> state, dbg; };
