@@ -211,7 +211,8 @@ int pih_ik_ur5(pih_handle* h, int n, const float* q0_dev, const float* tpos_dev,
  * terms.  out_dev must be 16-byte aligned. */
 int pih_render(pih_handle* h, float* out_dev, int width, int height, int env_begin, int env_count, void* stream);
 /* the same with options: flags = PIH_RENDER_SHADED multiplies the per-object RGB value by ambient + diffuse x max(0, n . l) of
- * TinyRenderer's default light (getCameraImage without light arguments; specular term and shadow map not reproduced) */
+ * TinyRenderer's default light (getCameraImage without light arguments; specular term and shadow map not reproduced); any other bit,
+ * the output formats of pih_render_cam included, returns -2: the wrist camera has the one format */
 #define PIH_RENDER_SHADED 1
 int pih_render_ex(pih_handle* h, float* out_dev, int width, int height, int env_begin, int env_count, int flags, void* stream);
 /* free camera of the 'random-fly' task (fly handles only; a peg-in-hole handle gets -2, and pih_render / pih_render_ex keep rejecting fly
@@ -221,13 +222,28 @@ int pih_render_ex(pih_handle* h, float* out_dev, int width, int height, int env_
  * capsules (255 x PIH_UR5_RGB), the object's sphere cover (255 x PIH_FLY_OBJ_RGB), the table plane (153), background 255 at depth 1; a hit
  * outside [near, far] is clipped.  flags: PIH_RENDER_SHADED as in pih_render_ex (same light, ambient and diffuse terms);
  * PIH_RENDER_CAM_EE = eye, target and up are given in the ee_link frame of each env's UR5 (eye-in-hand) instead of the env-local frame
- * (the env's offset does not enter either way).  cam_host: HOST float[PIH_CAM_WORDS], read during the call, one camera for all envs of
+ * (the env's offset does not enter either way).  cam: HOST float[PIH_CAM_WORDS], read during the call, one camera for all envs of
  * the call; NULL = PIH_FLY_CAM_DEFAULT.  A degenerate camera (eye == target, up parallel to the view axis, fov outside (0, 180),
- * aspect <= 0, near <= 0, far <= near) returns -2 and pih_last_error names the field. */
+ * aspect <= 0, near <= 0, far <= near) returns -2 and pih_last_error names the field.
+ * Output formats (at most one; both: -2; none: the float4 image above; out_dev is 16-byte aligned for each, any width, height >= 1):
+ *   PIH_RENDER_OUT_RGBA8  out_dev uint8[env_count, height, width, 4] = (r, g, b, seg): the r, g, b of the float4 image (flat or
+ *                         PIH_RENDER_SHADED) as bytes min(255, (int)(v + 0.5f)) -- rounded half up, the arm's flat 178.5 is 179 -- and
+ *                         the segmentation value of what the ray hit: the link index 0 .. 5, PIH_SEG_OBJECT, PIH_SEG_TABLE, PIH_SEG_NONE
+ *   PIH_RENDER_OUT_DEPTH  out_dev float[env_count, height, width]: the depth-buffer value alone (PIH_RENDER_SHADED has no effect)
+ * PIH_RENDER_CAM_DEVICE: the camera argument is a DEVICE pointer float[env_count, PIH_CAM_WORDS], row e = the camera of env
+ * env_begin + e, read by the kernel (no host copy, no synchronisation); NULL: -2.  Combines with PIH_RENDER_CAM_EE and every format.
+ * The host cannot see these cameras, so the kernel applies the same test per env: an env whose camera is degenerate (or holds a NaN)
+ * gets the background image -- depth 1, rgb 255, seg PIH_SEG_NONE -- and the call returns 0. */
 #define PIH_CAM_WORDS 13        /* eye xyz, target xyz, up xyz, fov [deg, vertical], aspect, near, far */
 #define PIH_FLY_CAM_DEFAULT {1.6f, 0.f, 1.2f,  0.f, 0.f, 0.2f,  0.f, 0.f, 1.f,  60.f, 1.f, 0.01f, 100.f}
 #define PIH_RENDER_CAM_EE 2     /* camera given in the ee_link frame of each env's UR5 (eye-in-hand) instead of the env-local frame */
-int pih_render_cam(pih_handle* h, float* out_dev, const float* cam_host /* [PIH_CAM_WORDS] or NULL = default */,
+#define PIH_RENDER_OUT_RGBA8 4  /* out_dev is uint8[env_count, height, width, 4] = (r, g, b, seg) */
+#define PIH_RENDER_OUT_DEPTH 8  /* out_dev is float[env_count, height, width] = the depth-buffer value */
+#define PIH_RENDER_CAM_DEVICE 16 /* the camera argument is a device pointer float[env_count, PIH_CAM_WORDS], one camera per env */
+#define PIH_SEG_OBJECT 6        /* seg byte of PIH_RENDER_OUT_RGBA8: links are 0 .. 5 (PIH_SEG_OBJECT = PIH_UR5_NJ), then the object, */
+#define PIH_SEG_TABLE 7         /* the table */
+#define PIH_SEG_NONE 255        /* and nothing (background) */
+int pih_render_cam(pih_handle* h, float* out_dev, const float* cam /* [PIH_CAM_WORDS] on the host, NULL = default; PIH_RENDER_CAM_DEVICE: [env_count][PIH_CAM_WORDS] on the device */,
                    int width, int height, int env_begin, int env_count, int flags, void* stream);
 /* grasp-rectangle label images of random_grasp (envs/peg_in_hole.py:72-99,116) from the angle each env recorded when its
  * state machine entered state 2 (PIH_S_GRASP_ANGLE): out_dev float[env_count, 4, size, size] = pos (50 inside the rectangle),

@@ -13,6 +13,8 @@ FLY_STATE_WORDS, FLY_ACTION_DIM, FLY_OBS_DIM = 48, 6, 6
 CAM_WORDS = 13     # pih_render_cam: eye xyz, target xyz, up xyz, fov [deg, vertical], aspect, near, far
 FLY_CAM_DEFAULT = (1.6, 0.0, 1.2, 0.0, 0.0, 0.2, 0.0, 0.0, 1.0, 60.0, 1.0, 0.01, 100.0)    # PIH_FLY_CAM_DEFAULT
 RENDER_SHADED, RENDER_CAM_EE = 1, 2                # flags of pih_render_ex / pih_render_cam
+RENDER_OUT_RGBA8, RENDER_OUT_DEPTH, RENDER_CAM_DEVICE = 4, 8, 16     # pih_render_cam: output format (at most one), per-env cameras in device memory
+SEG_OBJECT, SEG_TABLE, SEG_NONE = 6, 7, 255        # seg byte of RENDER_OUT_RGBA8: UR5 links are 0 .. 5
 FIELD_STATE, FIELD_TIP_POSE, FIELD_CONTACT_FORCE, FIELD_DEBUG, FIELD_EE_POS = 0, 1, 2, 3, 4
 TASK_PEG_IN_HOLE, TASK_RANDOM_FLY = 0, 1
 # state record word offsets (PIH_S_*)
@@ -79,7 +81,8 @@ def load():
     L.pih_ik_ur5.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp]
     L.pih_render.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]
     L.pih_render_ex.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]
-    L.pih_render_cam.argtypes = [vp, vp, C.POINTER(C.c_float * CAM_WORDS), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]
+    L.pih_render_cam.argtypes = [vp, vp, vp,      # (camera: a (c_float * CAM_WORDS) array, None, or with RENDER_CAM_DEVICE a device address)
+                                  C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]
     L.pih_grasp_labels.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp]
     L.pih_reseed.argtypes = [vp, C.c_uint64]
     L.pih_timing.argtypes = [vp, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int64)]

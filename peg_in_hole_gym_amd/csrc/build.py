@@ -5,9 +5,10 @@ import subprocess
 import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, "pih_hip.hip")
+SRCS = [os.path.join(HERE, f) for f in ("pih_hip.hip", "pih_fly_image.hip")]      # one translation unit each, linked into one library
+SRC = SRCS[0]
 OUT = os.path.join(HERE, "libpih_hip.so")
-DEPS = [SRC] + glob.glob(os.path.join(HERE, "*.h")) + glob.glob(os.path.join(HERE, "..", "..", "include", "*.h"))
+DEPS = SRCS + glob.glob(os.path.join(HERE, "*.h")) + glob.glob(os.path.join(HERE, "..", "..", "include", "*.h"))
 # compiler flags of the device code (tools/isa_fingerprint.py compiles with the same ones)
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-value", "-fno-slp-vectorize", "-fno-hip-fp32-correctly-rounded-divide-sqrt", "-ffast-math"]
 
@@ -23,7 +24,7 @@ def build(force=False, verbose=False):
     if not force and not needs_build():
         return OUT
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    cmd = [hipcc] + FLAGS + ["-shared", "-o", OUT, SRC]
+    cmd = [hipcc] + FLAGS + ["-shared", "-o", OUT] + SRCS
     if verbose:
         cmd.insert(1, "-Rpass-analysis=kernel-resource-usage")
         print(" ".join(cmd))

@@ -14,6 +14,10 @@
 //   rgb     0 .. 255: table 153, link L 255 PIH_UR5_RGB[L], object 255 PIH_FLY_OBJ_RGB[object], nothing 255; PIH_RENDER_SHADED multiplies
 //           by ambient + diffuse max(0, n . l) of pih_raycast.h (n: +z on the table, radial on capsules and spheres)
 // PIH_RENDER_CAM_EE: eye, target and up are given in the ee_link frame of the env's UR5 (chain_ee<Ur5Chain>) -- an eye-in-hand camera.
+// Output formats: float4 (depth, r, g, b) as above; PIH_RENDER_OUT_RGBA8 = bytes (r, g, b, seg), seg = the hit's kind (link 0 .. 5,
+// PIH_SEG_OBJECT, PIH_SEG_TABLE, PIH_SEG_NONE); PIH_RENDER_OUT_DEPTH = the depth value alone.  PIH_RENDER_CAM_DEVICE: one camera per env,
+// read by the kernel, tested by the kernel (cam_degenerate): a degenerate one gives its env the background.  Kernels: pih_fly_render_kernel
+// (pih_hip.hip; float4, one host camera) and pih_fly_image_kernel (pih_fly_image.hip; everything else).
 //
 // Mapping (as pih_render.h): one 256-thread workgroup per (env, strip of rows), the scene once per workgroup in LDS; each WAVE walks
 // 16-row x 64-column tiles; lane i < FLY_NPRIM tests the conservative screen bound of primitive i (camera coordinates; a capsule's bound
@@ -135,8 +139,8 @@ PIH_HD bool prim_on_tile(const FlyScene& sc, int i, real tu0, real tu1, real tv0
 PIH_HD unsigned all_prims(int object) { return (1u << (RCAP + R_NSPH[object])) - 1u; }
 
 // one pixel: xc, yc = camera-plane coordinates of the pixel centre (already multiplied by tx / ty); prims = bit i set if primitive i
-// may cover the pixel (wave-uniform)
-PIH_HD real4 shade(const FlyScene& sc, unsigned prims, real xc, real yc, int flags) {
+// may cover the pixel (wave-uniform); kind = what the ray hit: link 0 .. RCAP - 1, KIND_OBJECT, KIND_TABLE or KIND_NONE
+PIH_HD real4 shade_kind(const FlyScene& sc, unsigned prims, real xc, real yc, int flags, int& kind_out) {
   const V3 eye = ld3(sc.eye);
   const real inv = rsqrt_((real)1 + xc * xc + yc * yc);      // = d . f
   const V3 d = inv * (ld3(sc.f) + xc * ld3(sc.s) + yc * ld3(sc.u));
@@ -183,7 +187,64 @@ PIH_HD real4 shade(const FlyScene& sc, unsigned prims, real xc, real yc, int fla
     lit = PIH_LIGHT_AMBIENT + PIH_LIGHT_DIFFUSE * max_(ndl, (real)0);
   }
   real4 o; o.x = depth; o.y = sc.rgb[kind][0] * lit; o.z = sc.rgb[kind][1] * lit; o.w = sc.rgb[kind][2] * lit;
+  kind_out = kind;
   return o;
+}
+PIH_HD real4 shade(const FlyScene& sc, unsigned prims, real xc, real yc, int flags) {
+  int kind;
+  return shade_kind(sc, prims, xc, yc, flags, kind);
+}
+
+// The packed formats of pih_render_cam.  PIH_RENDER_OUT_RGBA8: one 32-bit word per pixel, bytes (r, g, b, seg) in memory order.
+// A colour value v (fp32, 0 .. 255) becomes the byte min(255, (int)(v + 0.5)): rounded half up, so 178.5 -> 179; v is never negative.
+PIH_HD unsigned pack_byte(real v) {
+  const int b = (int)(v + (real)0.5);
+  return b > 255 ? 255u : (unsigned)b;
+}
+// segmentation value of a pixel's kind: the link index, PIH_SEG_OBJECT, PIH_SEG_TABLE, PIH_SEG_NONE
+static_assert(PIH_SEG_OBJECT == RCAP && PIH_SEG_OBJECT == KIND_OBJECT && PIH_SEG_TABLE == KIND_TABLE, "seg values of links, object and table are the pixel kinds");
+PIH_HD unsigned seg_of_kind(int kind) { return kind < KIND_NONE ? (unsigned)kind : (unsigned)PIH_SEG_NONE; }
+PIH_HD unsigned pack_rgba8(const real4& c, int kind) {
+  return pack_byte(c.y) | (pack_byte(c.z) << 8) | (pack_byte(c.w) << 16) | (seg_of_kind(kind) << 24);
+}
+// what a pixel of an env with a degenerate camera holds: depth 1, rgb 255, PIH_SEG_NONE
+PIH_HD real4 background() { real4 o; o.x = 1; o.y = o.z = o.w = PIH_COL_BG; return o; }
+// one pixel of each format (`bad`: the env's camera is degenerate, wave-uniform)
+PIH_HD real4 pixel_float4(const FlyScene& sc, unsigned prims, real xc, real yc, int flags, bool bad) {
+  return bad ? background() : shade(sc, prims, xc, yc, flags);
+}
+PIH_HD unsigned pixel_rgba8(const FlyScene& sc, unsigned prims, real xc, real yc, int flags, bool bad) {
+  int kind = KIND_NONE;
+  const real4 c = bad ? background() : shade_kind(sc, prims, xc, yc, flags, kind);
+  return pack_rgba8(c, kind);
+}
+PIH_HD real pixel_depth(const FlyScene& sc, unsigned prims, real xc, real yc, bool bad) {
+  return bad ? (real)1 : shade(sc, prims, xc, yc, 0).x;
+}
+
+// Is the camera degenerate?  -> 0 or the code of the first field that is.  The host validates a camera it can read with this
+// (pih_render_cam maps the code to its message); a camera in device memory (PIH_RENDER_CAM_DEVICE) is tested by the kernel, once per
+// workgroup, and a degenerate one gives its env the background image.  The tests are frame-independent, so they hold for
+// PIH_RENDER_CAM_EE as well.  !(a > b) also catches NaN where the compiler honours NaN; the library is built with -ffast-math, which does
+// not, so a non-finite word is found by its bit pattern first -- with finite words no expression below can produce a NaN.
+enum : int { CAM_OK = 0, CAM_BAD_VIEW = 1, CAM_BAD_UP = 2, CAM_BAD_FOV = 3, CAM_BAD_ASPECT = 4, CAM_BAD_NEAR = 5, CAM_BAD_FAR = 6 };
+PIH_HHD bool cam_word_finite(float x) {
+  unsigned u; __builtin_memcpy(&u, &x, sizeof u);
+  return (u & 0x7f800000u) != 0x7f800000u;
+}
+PIH_HHD int cam_degenerate(const float* c) {
+  bool fin[PIH_CAM_WORDS];
+  for (int i = 0; i < PIH_CAM_WORDS; i++) fin[i] = cam_word_finite(c[i]);
+  const double f[3] = {(double)c[3] - c[0], (double)c[4] - c[1], (double)c[5] - c[2]}, up[3] = {c[6], c[7], c[8]};
+  const double fl = sqrt(f[0] * f[0] + f[1] * f[1] + f[2] * f[2]), ul = sqrt(up[0] * up[0] + up[1] * up[1] + up[2] * up[2]);
+  const double cx = f[1] * up[2] - f[2] * up[1], cy = f[2] * up[0] - f[0] * up[2], cz = f[0] * up[1] - f[1] * up[0];
+  if (!(fin[0] && fin[1] && fin[2] && fin[3] && fin[4] && fin[5]) || !(fl > 1e-9 && fl < 1e15)) return CAM_BAD_VIEW;
+  if (!(fin[6] && fin[7] && fin[8]) || !(ul > 0 && ul < 1e15 && sqrt(cx * cx + cy * cy + cz * cz) > 1e-6 * fl * ul)) return CAM_BAD_UP;
+  if (!fin[CAM_FOV] || !(c[CAM_FOV] > 0.f && c[CAM_FOV] < 180.f)) return CAM_BAD_FOV;
+  if (!fin[CAM_ASPECT] || !(c[CAM_ASPECT] > 0.f && c[CAM_ASPECT] < 1e15f)) return CAM_BAD_ASPECT;
+  if (!fin[CAM_NEAR] || !(c[CAM_NEAR] > 0.f && c[CAM_NEAR] < 1e15f)) return CAM_BAD_NEAR;
+  if (!fin[CAM_FAR] || !(c[CAM_FAR] > c[CAM_NEAR] && c[CAM_FAR] < 1e15f)) return CAM_BAD_FAR;
+  return CAM_OK;
 }
 
 // The pixel grid, shared by the kernel and the host build: pixel-centre and tile-edge coordinates on the camera plane

@@ -14,6 +14,12 @@
 
 using namespace pih;
 
+// pih_fly_image.hip: the kernels of the packed output formats and of the per-env cameras in device memory
+namespace pih {
+void fly_image_launch(int fmt, dim3 grid, hipStream_t stream, const float* state, void* out, const fly::FlyCam& cam, const float* cam_dev,
+                      int n, int object, int env_begin, int W, int H, int rows_per_strip, int flags);
+}
+
 // ------------------------------------------------------------------------------------------------ kernels
 // state: float[n][256] (env-major records: the 64 lanes of the env's wave read/write consecutive words, so every
 // access is a fully coalesced 256 B segment).
@@ -869,6 +875,8 @@ int pih_render_ex(pih_handle* h, float* out_dev, int width, int height, int env_
   }
   if (h->fly) { h->err = "pih_render: the wrist camera belongs to the peg-in-hole task"; return -2; }
   if ((reinterpret_cast<uintptr_t>(out_dev) & 15) != 0) { h->err = "pih_render: out_dev must be 16-byte aligned"; return -2; }
+  // (the output formats and the device cameras of pih_render_cam do not exist here: out_dev is float[count, H, W, 4] whatever the flags say)
+  if ((flags & ~PIH_RENDER_SHADED) != 0) { h->err = "pih_render_ex: unknown flag (the wrist camera takes PIH_RENDER_SHADED only)"; return -2; }
   PIH_ENTER(h);
   int rows; const int strips = render_strips(height, env_count, &rows);
   if (env_count > 65535) { h->err = "pih_render: env_count > 65535 per call"; return -2; }
@@ -877,37 +885,34 @@ int pih_render_ex(pih_handle* h, float* out_dev, int width, int height, int env_
   return 0;
 }
 
-int pih_render_cam(pih_handle* h, float* out_dev, const float* cam_host, int width, int height, int env_begin, int env_count, int flags, void* stream) {
+int pih_render_cam(pih_handle* h, float* out_dev, const float* cam_ptr, int width, int height, int env_begin, int env_count, int flags, void* stream) {
+  const int fmt = flags & (PIH_RENDER_OUT_RGBA8 | PIH_RENDER_OUT_DEPTH);
+  const bool cam_on_device = (flags & PIH_RENDER_CAM_DEVICE) != 0;
   if (!h || !out_dev || width <= 0 || height <= 0 || env_begin < 0 || env_count <= 0 || env_begin + env_count > h->cfg.n_envs ||
-      (flags & ~(PIH_RENDER_SHADED | PIH_RENDER_CAM_EE)) != 0) {
+      (flags & ~(PIH_RENDER_SHADED | PIH_RENDER_CAM_EE | PIH_RENDER_OUT_RGBA8 | PIH_RENDER_OUT_DEPTH | PIH_RENDER_CAM_DEVICE)) != 0) {
     if (h) h->err = "pih_render_cam: bad arguments";
     return -2;
   }
   if (!h->fly) { h->err = "pih_render_cam: the free camera belongs to the random-fly task (peg-in-hole: pih_render / pih_render_ex)"; return -2; }
+  if (fmt == (PIH_RENDER_OUT_RGBA8 | PIH_RENDER_OUT_DEPTH)) { h->err = "pih_render_cam: PIH_RENDER_OUT_RGBA8 and PIH_RENDER_OUT_DEPTH exclude each other"; return -2; }
+  if (cam_on_device && !cam_ptr) { h->err = "pih_render_cam: PIH_RENDER_CAM_DEVICE needs a camera array (NULL = default is for a host camera)"; return -2; }
   if ((reinterpret_cast<uintptr_t>(out_dev) & 15) != 0) { h->err = "pih_render_cam: out_dev must be 16-byte aligned"; return -2; }
   if (env_count > 65535) { h->err = "pih_render_cam: env_count > 65535 per call"; return -2; }
-  static const float cam_default[PIH_CAM_WORDS] = PIH_FLY_CAM_DEFAULT;
-  fly::FlyCam cam;
-  memcpy(cam.w, cam_host ? cam_host : cam_default, sizeof cam.w);
-  {
-    // degenerate cameras (the tests are frame-independent, so they hold for PIH_RENDER_CAM_EE as well); !(a > b) also catches NaN
-    const float* c = cam.w;
-    const double f[3] = {(double)c[3] - c[0], (double)c[4] - c[1], (double)c[5] - c[2]}, up[3] = {c[6], c[7], c[8]};
-    const double fl = sqrt(f[0] * f[0] + f[1] * f[1] + f[2] * f[2]), ul = sqrt(up[0] * up[0] + up[1] * up[1] + up[2] * up[2]);
-    const double cx = f[1] * up[2] - f[2] * up[1], cy = f[2] * up[0] - f[0] * up[2], cz = f[0] * up[1] - f[1] * up[0];
-    const char* bad = nullptr;
-    if (!(fl > 1e-9 && fl < 1e15)) bad = "eye == target (or not finite)";
-    else if (!(ul > 0 && ul < 1e15 && sqrt(cx * cx + cy * cy + cz * cz) > 1e-6 * fl * ul)) bad = "up is zero or parallel to the view axis target - eye";
-    else if (!(c[fly::CAM_FOV] > 0.f && c[fly::CAM_FOV] < 180.f)) bad = "fov outside (0, 180) degrees";
-    else if (!(c[fly::CAM_ASPECT] > 0.f && c[fly::CAM_ASPECT] < 1e15f)) bad = "aspect <= 0";
-    else if (!(c[fly::CAM_NEAR] > 0.f && c[fly::CAM_NEAR] < 1e15f)) bad = "near <= 0";
-    else if (!(c[fly::CAM_FAR] > c[fly::CAM_NEAR] && c[fly::CAM_FAR] < 1e15f)) bad = "far <= near";
-    if (bad) { h->err = std::string("pih_render_cam: degenerate camera: ") + bad; return -2; }
+  fly::FlyCam cam = {PIH_FLY_CAM_DEFAULT};
+  if (!cam_on_device) {
+    if (cam_ptr) memcpy(cam.w, cam_ptr, sizeof cam.w);
+    static const char* const what[] = {nullptr, "eye == target (or not finite)", "up is zero or parallel to the view axis target - eye", "fov outside (0, 180) degrees",
+                                       "aspect <= 0", "near <= 0", "far <= near"};
+    const int code = fly::cam_degenerate(cam.w);
+    if (code != fly::CAM_OK) { h->err = std::string("pih_render_cam: degenerate camera: ") + what[code]; return -2; }
   }
   PIH_ENTER(h);
   int rows; const int strips = render_strips(height, env_count, &rows);
-  hipLaunchKernelGGL(pih_fly_render_kernel, dim3(strips, env_count), dim3(RENDER_THREADS), 0, (hipStream_t)stream, h->state, out_dev, cam,
-                     h->cfg.n_envs, h->P.object, env_begin, width, height, rows, flags);
+  if (fmt || cam_on_device)
+    fly_image_launch(fmt, dim3(strips, env_count), (hipStream_t)stream, h->state, out_dev, cam, cam_on_device ? cam_ptr : nullptr, h->cfg.n_envs, h->P.object, env_begin, width, height, rows, flags);
+  else      // the float4 image of one host camera: the kernel it has always been
+    hipLaunchKernelGGL(pih_fly_render_kernel, dim3(strips, env_count), dim3(RENDER_THREADS), 0, (hipStream_t)stream, h->state, out_dev, cam,
+                       h->cfg.n_envs, h->P.object, env_begin, width, height, rows, flags);
   HIPCHK(h, hipGetLastError());
   return 0;
 }

@@ -10,6 +10,7 @@
 #include <hip/hip_runtime.h>
 typedef float real;
 #define PIH_HD __device__ __forceinline__
+#define PIH_HHD __host__ __device__ __forceinline__   // the few functions the library's host code calls as well
 // (measured: a non-inlined phase loses the LDS address space of `Shared&` and falls back to flat loads: 45 % slower PGS)
 #define PIH_NOINL __device__ __attribute__((noinline))
 #define PIH_CONST static __device__ __constant__ const
@@ -22,6 +23,9 @@ PIH_HD real max_(real a, real b) { return __builtin_fmaxf(a, b); }
 PIH_HD void sincos_(float a, float* s, float* c) { sincosf(a, s, c); }
 PIH_HD float acos_(float a) { return acosf(a); }
 }  // namespace pih
+#endif
+#ifndef PIH_HHD
+#define PIH_HHD PIH_HD
 #endif
 
 namespace pih {

@@ -9,6 +9,22 @@ import torch
 from . import _lib
 
 
+def tracking_cameras(opos, eye, up=(0.0, 0.0, 1.0), fov=60.0, aspect=1.0, near=0.01, far=100.0):
+    """Cameras that follow a point per env: opos float [n, 3] (any device) -> float32 [n, 13] on the same device, row e = (eye, target =
+    opos[e], up, fov, aspect, near, far) in the camera words of pih_render_cam.  eye and up: 3 numbers for all envs, or [n, 3].  Pure
+    torch: with PihVecEnv.render(camera=...) the viewpoint moves with the simulation without leaving the device."""
+    opos = torch.as_tensor(opos).to(torch.float32)
+    if opos.ndim != 2 or opos.shape[1] != 3:
+        raise ValueError("tracking_cameras: opos must have shape [n, 3], got %s" % (tuple(opos.shape),))
+    n = opos.shape[0]
+    cam = torch.empty(n, _lib.CAM_WORDS, dtype=torch.float32, device=opos.device)
+    cam[:, 0:3] = torch.as_tensor(eye, dtype=torch.float32, device=opos.device)
+    cam[:, 3:6] = opos
+    cam[:, 6:9] = torch.as_tensor(up, dtype=torch.float32, device=opos.device)
+    cam[:, 9] = float(fov); cam[:, 10] = float(aspect); cam[:, 11] = float(near); cam[:, 12] = float(far)
+    return cam
+
+
 class PihVecEnv:
     """N independent worlds of one task on one MI355X.
 
@@ -187,35 +203,71 @@ class PihVecEnv:
             self._chk(self.L.pih_ik_ur5(self.h, n, q0.data_ptr(), tpos.data_ptr(), tquat.data_ptr(), out.data_ptr(), self._stream()), "pih_ik_ur5")
         return out
 
-    def render(self, width=300, height=300, env_begin=0, env_count=None, out=None, shaded=False, camera=None, ee_frame=False):
+    def _here(self, t):
+        """is the tensor on this handle's device? (a handle made with device="cuda" has no index)"""
+        return t.device.type == self.device.type and (self.device.index is None or t.device.index == self.device.index)
+
+    _RENDER_FMT = {"float4": (0, torch.float32, (4,)), "rgba8": (_lib.RENDER_OUT_RGBA8, torch.uint8, (4,)), "depth": (_lib.RENDER_OUT_DEPTH, torch.float32, ())}
+
+    def render(self, width=300, height=300, env_begin=0, env_count=None, out=None, shaded=False, camera=None, ee_frame=False, fmt="float4"):
         """Camera image of a block of envs at the current state (analytic ray caster): float32 [count, height, width, 4] =
         (depth buffer, r, g, b), RGB on the 0..255 scale, flat per object or (shaded=True) times ambient + diffuse of TinyRenderer's
         default light.
-        peg-in-hole: PegInHole.render (envs/peg_in_hole.py:276-304), the wrist camera (pih_render_ex); the camera is fixed, so
-            `camera` / `ee_frame` raise ValueError.
+        peg-in-hole: PegInHole.render (envs/peg_in_hole.py:276-304), the wrist camera (pih_render_ex); the camera and the format are
+            fixed, so `camera` / `ee_frame` / a `fmt` other than "float4" raise ValueError.
         random-fly: a free camera over the UR5's capsules, the object and the table (pih_render_cam).  camera = 13 numbers (eye xyz,
             target xyz, up xyz, vertical fov in degrees, aspect, near, far: the arguments of computeViewMatrix and
             computeProjectionMatrixFOV) or None = _lib.FLY_CAM_DEFAULT, one camera for all envs of the call, in each env's local frame
-            (the env offset does not enter); ee_frame=True: in the ee_link frame of each env's UR5 (eye-in-hand)."""
+            (the env offset does not enter); ee_frame=True: in the ee_link frame of each env's UR5 (eye-in-hand).
+            camera of shape [count, 13]: one camera per env of the call (row e: env env_begin + e), read by the kernel from device memory
+            -- a float32 tensor on this handle's device is used in place, anything else is converted and uploaded.  These cameras are
+            not validated on the host: an env whose row is degenerate gets the background image (a 1-D camera raises PihError).
+            fmt: what getCameraImage returns, in two calls --
+              "float4"  float32 [count, height, width, 4]   (depth buffer, r, g, b)
+              "rgba8"   uint8   [count, height, width, 4]   (r, g, b, seg): the colours rounded half up to bytes; seg = link index 0..5,
+                                                            _lib.SEG_OBJECT, _lib.SEG_TABLE or _lib.SEG_NONE
+              "depth"   float32 [count, height, width]      the depth buffer alone
+            out: for "rgba8" / "depth" it must be a contiguous tensor of that dtype and shape on this handle's device (ValueError)."""
         count = self.n - env_begin if env_count is None else env_count
         fly = self.task_id == _lib.TASK_RANDOM_FLY
         if not fly and (camera is not None or ee_frame):
             raise ValueError("render: the peg-in-hole task has a fixed wrist camera; camera / ee_frame belong to the random-fly task")
-        cam = None
-        if camera is not None:
+        if fmt not in self._RENDER_FMT:
+            raise ValueError("render: fmt must be one of %s, got %r" % (sorted(self._RENDER_FMT), fmt))
+        if not fly and fmt != "float4":
+            raise ValueError("render: the peg-in-hole wrist camera has the one format 'float4'; 'rgba8' / 'depth' belong to the random-fly task")
+        fmt_flag, dtype, tail = self._RENDER_FMT[fmt]
+        cam, cam_flag = None, 0
+        if camera is not None and (camera.ndim if hasattr(camera, "ndim") else np.ndim(camera)) >= 2:
+            if not (torch.is_tensor(camera) and camera.dtype == torch.float32 and self._here(camera) and camera.is_contiguous()):
+                camera = torch.as_tensor(np.asarray(camera.cpu() if torch.is_tensor(camera) else camera, dtype=np.float32)).to(self.device).contiguous()
+            if tuple(camera.shape) != (count, _lib.CAM_WORDS):
+                raise ValueError("render: per-env cameras must have shape [%d, %d] (one row per env of the call), got %s" % (count, _lib.CAM_WORDS, tuple(camera.shape)))
+            cam, cam_flag = C.c_void_p(camera.data_ptr()), _lib.RENDER_CAM_DEVICE
+        elif camera is not None:
             vals = [float(x) for x in camera]
             if len(vals) != _lib.CAM_WORDS:
                 raise ValueError("render: camera must have %d numbers (eye, target, up, fov, aspect, near, far), got %d" % (_lib.CAM_WORDS, len(vals)))
             cam = (C.c_float * _lib.CAM_WORDS)(*vals)
+        shape = (count, height, width) + tail
         if out is None:
-            out = torch.empty(count, height, width, 4, device=self.device)
+            out = torch.empty(shape, dtype=dtype, device=self.device)
+        elif fmt != "float4" and not (torch.is_tensor(out) and out.dtype == dtype and tuple(out.shape) == shape and self._here(out) and out.is_contiguous()):
+            raise ValueError("render: out must be a contiguous %s tensor of shape %s on %s for fmt=%r" % (dtype, shape, self.device, fmt))
         with torch.cuda.device(self.device):
             if fly:
-                flags = (_lib.RENDER_SHADED if shaded else 0) | (_lib.RENDER_CAM_EE if ee_frame else 0)
+                flags = (_lib.RENDER_SHADED if shaded else 0) | (_lib.RENDER_CAM_EE if ee_frame else 0) | fmt_flag | cam_flag
                 self._chk(self.L.pih_render_cam(self.h, out.data_ptr(), cam, width, height, env_begin, count, flags, self._stream()), "pih_render_cam")
             else:
                 self._chk(self.L.pih_render_ex(self.h, out.data_ptr(), width, height, env_begin, count, 1 if shaded else 0, self._stream()), "pih_render_ex")
         return out
+
+    def tracking_cameras(self, eye, up=(0.0, 0.0, 1.0), fov=60.0, aspect=1.0, near=0.01, far=100.0):
+        """random-fly: float32 [n, 13] device tensor, one camera per env that looks from `eye` (env-local frame) at the env's object (the
+        PIH_F_OPOS words of the device state, no host synchronisation) -- feed it to render(camera=...)."""
+        if self.task_id != _lib.TASK_RANDOM_FLY:
+            raise ValueError("tracking_cameras: the object to follow belongs to the random-fly task")
+        return tracking_cameras(self.state()[:, _lib.F_OPOS:_lib.F_OPOS + 3], eye, up, fov, aspect, near, far)
 
     def grasp_labels(self, size=300, env_begin=0, env_count=None):
         """Label images + [x, y, angle_deg, width, length] of random_grasp (envs/peg_in_hole.py:72-99,116):

@@ -1,0 +1,247 @@
+"""Output formats and per-env cameras of the random-fly camera on the GPU: pih_render_cam with PIH_RENDER_OUT_RGBA8, PIH_RENDER_OUT_DEPTH
+and PIH_RENDER_CAM_DEVICE through PihVecEnv.render(fmt=..., camera=[count, 13]) and PihVecEnv.tracking_cameras, against the numpy fp64
+ray caster of tests/test_fly_render.py.  Rules, caps and the per-env-camera cases come from tests/test_fly_image.py (`I`), where the fp32
+host build of the same per-pixel code meets them first; the caps themselves are those of tests/test_gpu_fly_render.py (`G`)."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from peg_in_hole_gym_amd import _lib
+from tests import test_fly_image as I
+from tests import test_fly_render as T
+from tests import test_gpu_fly_render as G
+
+GUARD = 4096
+
+
+@pytest.fixture(scope="module")
+def torch_mod():
+    import torch
+    assert torch.cuda.is_available(), "GPU tests need a ROCm device"
+    return torch
+
+
+class Guarded:
+    """a tensor of the given shape and dtype inside a larger buffer of 0xA5 bytes, GUARD bytes before and after it"""
+    def __init__(self, torch, shape, dtype):
+        self.torch = torch
+        self.nbytes = int(np.prod(shape)) * torch.empty(0, dtype=dtype).element_size()
+        self.buf = torch.full((2 * GUARD + self.nbytes,), 0xA5, dtype=torch.uint8, device="cuda")
+        self.view = self.buf[GUARD:GUARD + self.nbytes].view(dtype).view(shape)
+
+    def intact(self):
+        return bool((self.buf[:GUARD] == 0xA5).all()) and bool((self.buf[GUARD + self.nbytes:] == 0xA5).all())
+
+
+def _render_guarded(torch, g, W, H, fmt, count=None, **kw):
+    count = g.n if count is None else count
+    shape, dtype = {"rgba8": ((count, H, W, 4), torch.uint8), "depth": ((count, H, W), torch.float32), "float4": ((count, H, W, 4), torch.float32)}[fmt]
+    box = Guarded(torch, shape, dtype)
+    out = g.render(W, H, out=box.view, fmt=fmt, env_count=count, **kw)
+    assert out.data_ptr() == box.view.data_ptr() and out.shape == shape and out.dtype == dtype
+    res = out.cpu().numpy()
+    assert box.intact(), "bytes outside the image were written (%s, %dx%d)" % (fmt, W, H)
+    assert not (fmt == "rgba8" and W * H > 64 and (res == 0xA5).all()), "the image was not written"
+    return res
+
+
+def _check_packed(O, fig, rgba_flat, rgba_lit, depth, rec, cam, ee, obj, ref):
+    """one env's three images against the reference, into the running figures"""
+    assert np.array_equal(rgba_flat[..., 3], rgba_lit[..., 3])                             # shading does not touch the segmentation
+    same = I.check_seg(O, rgba_flat[..., 3], rec, cam, ee, ref, exact=False)
+    fig.add_depth(I.depth_errors(depth, same, ref, cam))
+    fig.add_colour(I.colour_excess(rgba_flat[..., :3], same, ref[0]), False)
+    fig.add_colour(I.colour_excess(rgba_lit[..., :3], same, ref[1]), True)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("obj", [0, 1])
+def test_formats_all_cameras_and_sizes(torch_mod, oracle_mod, obj):
+    """N = 6, the four cameras, T.SIZES plus (5, 3): rgba8 flat and shaded, and depth, every env against the reference fed with the handle's
+    own state(); every call writes into a guarded view"""
+    n = 6
+    g = G._gpu(n, object_id=obj)
+    fig = I.Figures()
+    for name in T.CAMERA_NAMES:
+        g.set_state(torch_mod.tensor(T.make_states(oracle_mod, obj, n, seed=G.SCENE_SEED[(obj, name)], eye_in_hand=name == "eye-in-hand")))
+        st = g.state().cpu().numpy()
+        for (W, H) in I.SIZES:
+            cam, ee = T.cameras(W, H)[name]
+            flat = _render_guarded(torch_mod, g, W, H, "rgba8", camera=cam, ee_frame=ee)
+            lit = _render_guarded(torch_mod, g, W, H, "rgba8", camera=cam, ee_frame=ee, shaded=True)
+            depth = _render_guarded(torch_mod, g, W, H, "depth", camera=cam, ee_frame=ee)
+            assert np.array_equal(depth, _render_guarded(torch_mod, g, W, H, "depth", camera=cam, ee_frame=ee, shaded=True))
+            for e in range(n):
+                ref = T.reference_render(oracle_mod, st[e], cam, obj, W, H, ee)
+                T.check_reference_scene(name, W, H, ref[2], obj)
+                _check_packed(oracle_mod, fig, flat[e], lit[e], depth[e], st[e], cam, ee, obj, ref)
+    print("object %d: %s" % (obj, fig.text()))
+    fig.limits()
+
+
+@pytest.mark.gpu
+def test_depth_plane_is_the_float4_depth(torch_mod, oracle_mod):
+    n, obj = 6, 0
+    g = G._gpu(n, object_id=obj)
+    g.set_state(torch_mod.tensor(T.make_states(oracle_mod, obj, n, seed=G.SCENE_SEED[(obj, "close-up")])))
+    worst = 0.0
+    for (W, H) in I.SIZES:
+        cam, ee = T.cameras(W, H)["close-up"]
+        depth = g.render(W, H, camera=cam, fmt="depth").cpu().numpy()
+        img = g.render(W, H, camera=cam).cpu().numpy()
+        assert depth.shape == (n, H, W) and depth.dtype == np.float32
+        worst = max(worst, float(np.abs(depth - img[..., 0]).max()))
+    print("max |depth plane - float4 channel 0| = %.3e (0 expected)" % worst)
+    assert worst <= G.DEPTH_VALUE_TOL
+
+
+def _case_handle(torch, case):
+    g = G._gpu(len(case["states"]), object_id=case["obj"])
+    g.set_state(torch.tensor(case["states"]))
+    return g, g.state().cpu().numpy(), torch.tensor(case["cams"], device="cuda")
+
+
+@pytest.mark.gpu
+def test_per_env_cameras(torch_mod, oracle_mod):
+    """N = 70: the camera of env e is row e of a device tensor (three cameras in turn); the full range and env_begin = 3, env_count = 5,
+    where row e belongs to env 3 + e.  The envs of I.per_env_cases against the reference rendered with their own row, and against a call
+    with that row as the one host camera."""
+    case = I.per_env_cases(oracle_mod)["cycle"]
+    (W, H), obj, cams = case["size"], case["obj"], case["cams"]
+    g, st, cams_dev = _case_handle(torch_mod, case)
+    f4 = _render_guarded(torch_mod, g, W, H, "float4", camera=cams_dev)
+    u8 = _render_guarded(torch_mod, g, W, H, "rgba8", camera=cams_dev)
+    dp = _render_guarded(torch_mod, g, W, H, "depth", camera=cams_dev)
+    sub = cams_dev[3:8].contiguous()
+    assert np.array_equal(_render_guarded(torch_mod, g, W, H, "float4", count=5, env_begin=3, camera=sub), f4[3:8])
+    assert np.array_equal(_render_guarded(torch_mod, g, W, H, "rgba8", count=5, env_begin=3, camera=sub), u8[3:8])
+    assert np.array_equal(g.render(W, H, camera=cams[3:8].tolist(), env_begin=3, env_count=5, fmt="rgba8").cpu().numpy(), u8[3:8])      # converted and uploaded
+    fig = I.Figures(); zmax = dmax = cmax = 0.0; identical = True
+    for e in case["checked"]:
+        ref = T.reference_render(oracle_mod, st[e], cams[e], obj, W, H, False)
+        same = I.check_seg(oracle_mod, u8[e][..., 3], st[e], cams[e], False, ref, exact=False)
+        fig.add_depth(I.depth_errors(dp[e], same, ref, cams[e]))
+        fig.add_colour(I.colour_excess(u8[e][..., :3], same, ref[0]), False)
+        z, d, c = T.compare(f4[e].astype(np.float64), f4[e].astype(np.float64), ref[0], ref[2], ref[3], cams[e], obj, exact_class=False)
+        zmax = max(zmax, z); dmax = max(dmax, d); cmax = max(cmax, c.max())
+        # the same env with its row as the single host camera
+        one4 = g.render(W, H, camera=cams[e].tolist(), env_begin=e, env_count=1).cpu().numpy()[0]
+        one8 = g.render(W, H, camera=cams[e].tolist(), env_begin=e, env_count=1, fmt="rgba8").cpu().numpy()[0]
+        identical = identical and np.array_equal(one4, f4[e]) and np.array_equal(one8, u8[e])
+        agree = one8[..., 3] == u8[e][..., 3]
+        assert (~agree).mean() <= T.CLASS_SHARE and np.array_equal(one8[agree], u8[e][agree])
+        assert np.abs(one4[..., 0] - f4[e][..., 0])[agree].max() <= G.DEPTH_VALUE_TOL and np.abs(one4[..., 1:] - f4[e][..., 1:])[agree].max() <= G.COLOUR_TOL
+    print("per-env cameras: %s; float4: max relative depth error %.3e, depth-buffer value %.3e, colour %.3e; bit-identical to the single-camera calls: %s"
+          % (fig.text(), zmax, dmax, cmax, identical))
+    fig.limits()
+    assert zmax <= G.DEPTH_REL_TOL and dmax <= G.DEPTH_VALUE_TOL and cmax <= G.COLOUR_TOL
+
+
+@pytest.mark.gpu
+def test_per_env_eye_in_hand_cameras(torch_mod, oracle_mod):
+    """N = 6: rows that differ in fov (50 .. 70 degrees), given in each env's ee_link frame"""
+    case = I.per_env_cases(oracle_mod)["eye-in-hand"]
+    (W, H), obj, cams = case["size"], case["obj"], case["cams"]
+    g, st, cams_dev = _case_handle(torch_mod, case)
+    flat = _render_guarded(torch_mod, g, W, H, "rgba8", camera=cams_dev, ee_frame=True)
+    lit = _render_guarded(torch_mod, g, W, H, "rgba8", camera=cams_dev, ee_frame=True, shaded=True)
+    depth = _render_guarded(torch_mod, g, W, H, "depth", camera=cams_dev, ee_frame=True)
+    fig = I.Figures()
+    for e in case["checked"]:
+        ref = T.reference_render(oracle_mod, st[e], cams[e], obj, W, H, True)
+        T.check_reference_scene("eye-in-hand", W, H, ref[2], obj)
+        _check_packed(oracle_mod, fig, flat[e], lit[e], depth[e], st[e], cams[e], True, obj, ref)
+    print("per-env eye-in-hand: %s" % fig.text())
+    fig.limits()
+
+
+@pytest.mark.gpu
+def test_degenerate_rows_give_the_background(torch_mod, oracle_mod):
+    """N = 6: row 2 has eye == target, row 4 fov = NaN: those two images are background and finite, the other four are what they were"""
+    case = I.per_env_cases(oracle_mod)["degenerate"]
+    (W, H), obj, cams = case["size"], case["obj"], case["cams"]
+    assert case["degenerate"] == (2, 4)
+    g, st, cams_dev = _case_handle(torch_mod, case)
+    u8 = _render_guarded(torch_mod, g, W, H, "rgba8", camera=cams_dev)
+    lit = _render_guarded(torch_mod, g, W, H, "rgba8", camera=cams_dev, shaded=True)
+    dp = _render_guarded(torch_mod, g, W, H, "depth", camera=cams_dev)
+    f4 = _render_guarded(torch_mod, g, W, H, "float4", camera=cams_dev, shaded=True)
+    assert np.isfinite(dp).all() and np.isfinite(f4).all()
+    for e in case["degenerate"]:
+        assert (dp[e] == 1.0).all() and (u8[e] == 255).all() and (lit[e] == 255).all()
+        assert (f4[e][..., 0] == 1.0).all() and (f4[e][..., 1:] == 255.0).all()
+    fig = I.Figures()
+    for e in case["checked"]:
+        ref = T.reference_render(oracle_mod, st[e], cams[e], obj, W, H, False)
+        _check_packed(oracle_mod, fig, u8[e], lit[e], dp[e], st[e], cams[e], False, obj, ref)
+        assert np.abs(f4[e][..., 0] - dp[e]).max() <= G.DEPTH_VALUE_TOL
+    print("rows next to degenerate ones: %s" % fig.text())
+    fig.limits()
+
+
+@pytest.mark.gpu
+def test_tracking_cameras_follow_the_object(torch_mod, oracle_mod):
+    """after reset and 40 steps every env is seen from (1.2, 0.6, 0.9) looking at its own object, cameras built on the device"""
+    n, obj, (W, H) = 6, 0, (61, 61)
+    g = G._gpu(n, object_id=obj, auto_reset=0)
+    g.reset(seed=11)
+    rng = np.random.default_rng(11)
+    for _ in range(40):
+        g.step(torch_mod.tensor(rng.uniform(-1, 1, (n, 6)), dtype=torch_mod.float32))
+    cams_dev = g.tracking_cameras(eye=(1.2, 0.6, 0.9))
+    assert cams_dev.shape == (n, _lib.CAM_WORDS) and cams_dev.is_cuda and cams_dev.dtype == torch_mod.float32
+    u8 = g.render(W, H, camera=cams_dev, fmt="rgba8").cpu().numpy()
+    dp = g.render(W, H, camera=cams_dev, fmt="depth").cpu().numpy()
+    st = g.state().cpu().numpy(); cams = cams_dev.cpu().numpy()
+    assert np.array_equal(cams[:, 3:6], st[:, _lib.F_OPOS:_lib.F_OPOS + 3])
+    fig = I.Figures(); centred = 0
+    for e in range(n):
+        ref = T.reference_render(oracle_mod, st[e], cams[e], obj, W, H, False)
+        same = I.check_seg(oracle_mod, u8[e][..., 3], st[e], cams[e], False, ref, exact=False)
+        fig.add_depth(I.depth_errors(dp[e], same, ref, cams[e]))
+        fig.add_colour(I.colour_excess(u8[e][..., :3], same, ref[0]), False)
+        if ref[2][H // 2, W // 2] == T.OBJECT:
+            centred += 1
+            assert u8[e][H // 2, W // 2, 3] == _lib.SEG_OBJECT
+    print("tracking cameras: the object is on the centre pixel of %d of %d reference images; %s" % (centred, n, fig.text()))
+    fig.limits()
+
+
+@pytest.mark.gpu
+def test_errors(torch_mod):
+    from peg_in_hole_gym_amd.vec_env import PihVecEnv
+    torch = torch_mod
+    L = _lib.load()
+    fly = G._gpu(3)
+    out = torch.empty(3, 48, 64, 4, device="cuda")
+    cams = torch.tensor([_lib.FLY_CAM_DEFAULT] * 3, device="cuda")
+    both = _lib.RENDER_OUT_RGBA8 | _lib.RENDER_OUT_DEPTH
+    assert L.pih_render_cam(fly.h, out.data_ptr(), None, 64, 48, 0, 3, both, None) == -2
+    assert L.pih_render_cam(fly.h, out.data_ptr(), None, 64, 48, 0, 3, _lib.RENDER_CAM_DEVICE, None) == -2
+    assert b"PIH_RENDER_CAM_DEVICE" in L.pih_last_error(fly.h)
+    assert L.pih_render_cam(fly.h, out.data_ptr(), None, 64, 48, 0, 3, 32, None) == -2                         # a bit nobody defined
+    assert L.pih_render_cam(fly.h, out.data_ptr(), C.c_void_p(cams.data_ptr()), 64, 48, 0, 3, _lib.RENDER_CAM_DEVICE, None) == 0
+    peg = PihVecEnv(3, seed=7)
+    assert L.pih_render_ex(peg.h, out.data_ptr(), 64, 48, 0, 3, _lib.RENDER_OUT_RGBA8, None) == -2
+    assert b"flag" in L.pih_last_error(peg.h)
+    assert L.pih_render_ex(peg.h, out.data_ptr(), 64, 48, 0, 3, _lib.RENDER_SHADED, None) == 0
+    with pytest.raises(ValueError):
+        peg.render(64, 48, fmt="rgba8")
+    with pytest.raises(ValueError):
+        fly.render(64, 48, fmt="rgb")
+    with pytest.raises(ValueError):
+        fly.render(64, 48, fmt="rgba8", out=out)                                                               # float32 where uint8 is due
+    with pytest.raises(ValueError):
+        fly.render(64, 48, fmt="depth", out=torch.empty(3, 48, 64, 4, device="cuda"))                          # the shape of another format
+    with pytest.raises(ValueError):
+        fly.render(64, 48, fmt="rgba8", out=torch.empty(3, 48, 64, 4, dtype=torch.uint8))                      # on the host
+    with pytest.raises(ValueError):
+        fly.render(64, 48, camera=torch.zeros(3, 12, device="cuda"))
+    with pytest.raises(ValueError):
+        fly.render(64, 48, camera=cams[:2].contiguous())
+    with pytest.raises(ValueError):
+        fly.render(64, 48, camera=cams, env_begin=1, env_count=2)
+    img = fly.render(64, 48)
+    assert img.shape == (3, 48, 64, 4) and img.dtype == torch.float32 and bool(torch.isfinite(img).all())
+    assert fly.render(64, 48, fmt="rgba8").dtype == torch.uint8

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Fingerprint of the gfx950 code of every kernel in pih_hip.hip, without a GPU: one line per kernel with a hash of its instruction
+"""Fingerprint of the gfx950 code of every kernel of the library (pih_hip.hip, pih_fly_image.hip), without a GPU: one line per kernel with a hash of its instruction
 stream, the instruction count and the VGPR / AGPR / SGPR / LDS / scratch numbers of the code object metadata.  A refactor that leaves
 the lines of the hot kernels unchanged leaves their speed unchanged (the step kernels sit at the 256-register limit).
 usage: python tools/isa_fingerprint.py [SOURCE_TREE]    (default: this checkout; e.g. a `git worktree add` of another commit)"""
@@ -17,10 +17,13 @@ from peg_in_hole_gym_amd.csrc.build import FLAGS  # noqa: E402
 META = ("vgpr_count", "agpr_count", "sgpr_count", "group_segment_fixed_size", "private_segment_fixed_size")
 
 
-def assembly(tree):
-    src = os.path.join(tree, "peg_in_hole_gym_amd", "csrc", "pih_hip.hip")
+SOURCES = ("pih_hip.hip", "pih_fly_image.hip")       # the library's translation units (a tree from before one existed is read without it)
+
+
+def assembly(tree, name="pih_hip.hip"):
+    src = os.path.join(tree, "peg_in_hole_gym_amd", "csrc", name)
     with tempfile.TemporaryDirectory() as d:
-        out = os.path.join(d, "pih_hip.s")
+        out = os.path.join(d, "out.s")
         subprocess.run([os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")] + FLAGS + ["--offload-device-only", "-S", "-w", "-o", out, src],
                        check=True, cwd=os.path.dirname(src))
         return open(out).read()
@@ -61,10 +64,14 @@ def metadata(asm):
 
 
 def main():
-    asm = assembly(os.path.abspath(sys.argv[1]) if len(sys.argv) > 1 else ROOT)
-    meta = metadata(asm)
+    tree = os.path.abspath(sys.argv[1]) if len(sys.argv) > 1 else ROOT
+    meta, body = {}, {}
+    for src in SOURCES:
+        if os.path.exists(os.path.join(tree, "peg_in_hole_gym_amd", "csrc", src)):
+            asm = assembly(tree, src)
+            meta.update(metadata(asm)); body.update(kernels(asm))
     print("%-16s %6s  %4s %4s %4s %6s %4s  %s" % ("sha256[:16]", "instr", "vgpr", "agpr", "sgpr", "lds", "scr", "kernel"))
-    for name, ins in sorted(kernels(asm).items()):
+    for name, ins in sorted(body.items()):
         md = meta.get(name, {})
         print("%-16s %6d  %4s %4s %4s %6s %4s  %s" % (hashlib.sha256("\n".join(ins).encode()).hexdigest()[:16], sum(not i.endswith(":") for i in ins),
                                                     *(md.get(k, "?") for k in META), name))

@@ -2,12 +2,14 @@
 """Timing of pih_render (wrist camera, 300x300) and pih_grasp_labels for a block of envs.
 usage: render_bench.py [n]
        render_bench.py --task random-fly [--n N] --width W --height H [--repeats K]
-           the free camera of the random-fly task (pih_render_cam, default camera), flat and shaded, alternating with the peg-in-hole wrist
-           camera at the same n and size as the yardstick of the same run; stores = 16 bytes per pixel against the 6.3 TB/s of HBM
-           bandwidth a kernel can reach on the MI355X"""
+           the free camera of the random-fly task (pih_render_cam, default camera): float4 flat and shaded, rgba8 flat and shaded, depth,
+           float4 and rgba8 with per-env cameras in device memory, alternating with the peg-in-hole wrist camera at the same n and size as
+           the yardstick of the same run; stores = 16, 4 and 4 bytes per pixel against the 6.3 TB/s of HBM bandwidth a kernel can reach
+           on the MI355X; the last lines compare rgba8 and depth with float4 of the same run"""
 import sys, os, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
+from peg_in_hole_gym_amd import _lib
 from peg_in_hole_gym_amd.vec_env import PihVecEnv
 
 
@@ -24,22 +26,36 @@ def fly_bench():
     peg = PihVecEnv(n, mode=1, dv=0.05)
     peg.step_n(540)
     out = torch.empty(n, H, W, 4, device="cuda")
-    cases = (("random-fly flat", lambda: fly.render(W, H, out=out)), ("random-fly shaded", lambda: fly.render(W, H, out=out, shaded=True)),
-             ("peg-in-hole flat", lambda: peg.render(W, H, out=out)))
-    for _, f in cases:                           # warm-up
+    out8 = torch.empty(n, H, W, 4, dtype=torch.uint8, device="cuda")
+    outd = torch.empty(n, H, W, device="cuda")
+    cams = torch.tensor([_lib.FLY_CAM_DEFAULT] * n, device="cuda")      # per-env cameras in device memory: the default camera in every row, so the pixels are the same work
+    # (name, bytes stored per pixel, call); "float4 flat" is pih_fly_render_kernel, the kernel from before the packed formats
+    cases = (("random-fly float4 flat", 16, lambda: fly.render(W, H, out=out)),
+             ("random-fly float4 shaded", 16, lambda: fly.render(W, H, out=out, shaded=True)),
+             ("random-fly rgba8 flat", 4, lambda: fly.render(W, H, out=out8, fmt="rgba8")),
+             ("random-fly rgba8 shaded", 4, lambda: fly.render(W, H, out=out8, fmt="rgba8", shaded=True)),
+             ("random-fly depth", 4, lambda: fly.render(W, H, out=outd, fmt="depth")),
+             ("random-fly float4 flat, per-env cameras", 16, lambda: fly.render(W, H, out=out, camera=cams)),
+             ("random-fly rgba8 flat, per-env cameras", 4, lambda: fly.render(W, H, out=out8, fmt="rgba8", camera=cams)),
+             ("peg-in-hole float4 flat", 16, lambda: peg.render(W, H, out=out)))
+    for _, _, f in cases:                        # warm-up
         for _ in range(2):
             f()
     torch.cuda.synchronize()
-    ms = {name: [] for name, _ in cases}
+    ms = {name: [] for name, _, _ in cases}
     ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
     for _ in range(K):                           # alternating: every repeat times each case once
-        for name, f in cases:
+        for name, _, f in cases:
             ev[0].record(); f(); ev[1].record(); ev[1].synchronize()
             ms[name].append(ev[0].elapsed_time(ev[1]))
-    for name, _ in cases:
+    for name, bpp, _ in cases:
         v = sorted(ms[name]); med = v[len(v) // 2]
-        print("%-18s %d envs x %dx%d: median %.3f ms (min %.3f, max %.3f, %d repeats) = %.0f Mpixel/s, %.2f TB/s stored = %.0f %% of 6.3 TB/s"
-              % (name, n, W, H, med, v[0], v[-1], K, n * W * H / med / 1e3, n * W * H * 16 / med / 1e9, 100 * n * W * H * 16 / (med * 1e-3) / HBM))
+        print("%-40s %d envs x %dx%d: median %.3f ms (min %.3f, max %.3f, %d repeats) = %.0f images/s, %.0f Mpixel/s, %d B/pixel stored: %.2f TB/s = %.0f %% of 6.3 TB/s"
+              % (name, n, W, H, med, v[0], v[-1], K, n / (med * 1e-3), n * W * H / med / 1e3, bpp, n * W * H * bpp / med / 1e9, 100 * n * W * H * bpp / (med * 1e-3) / HBM))
+    ref = sorted(ms["random-fly float4 flat"]); spread = ref[-1] - ref[0]
+    for name in ("random-fly rgba8 flat", "random-fly depth"):
+        med = sorted(ms[name])[K // 2]
+        print("%-40s median %.3f ms vs float4 flat %.3f ms + its spread %.3f ms: %s" % (name, med, ref[K // 2], spread, "within" if med <= ref[K // 2] + spread else "SLOWER"))
 
 
 if "--task" in sys.argv:
