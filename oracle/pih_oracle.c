@@ -652,8 +652,8 @@ static void collide(const piho_config* c, Env* E, const LinkKin* K) {
       ga = sa * mx / sdf; gr = sr * my / sdf;
     }
     real depth = sdf - r;
-    if (depth >= margin) continue;
-    v3 rh; if (rho > 1e-9) v_set(rh, 0, d[1] / rho, d[2] / rho); else v_set(rh, 0, 1, 0);
+    if (depth >= margin || rho <= 1e-9) continue;   /* on the axis there is no radial direction (and gr != 0 there): no contact */
+    v3 rh; v_set(rh, 0, d[1] / rho, d[2] / rho);
     v3 n = {ga, gr * rh[1], gr * rh[2]}, p;
     v_cp(p, sp[i]); v_axpy(p, -(r + 0.5 * depth), n);
     int L = ANL + SAMP_LINK[i];
@@ -711,7 +711,7 @@ static void collide(const piho_config* c, Env* E, const LinkKin* K) {
     v3 bc; m_mulv(bc, kf->R, FBOX_C[f]); v_add(bc, bc, kf->o);
     for (int i = 0; i < PIH_PIPE_NSAMP; i++) {
       v3 d, pl; v_sub(d, sp[i], bc);
-      if (v_dot(d, d) > 0.05 * 0.05) continue;
+      if (v_norm(d) > v_norm(FBOX_H) + r + margin + 1e-4) continue;   /* exact for any margin: half diagonal + r + margin */
       m_tmulv(pl, kf->R, d);
       v3 q, nl; int inside = 1;
       for (int k = 0; k < 3; k++) { q[k] = clampd(pl[k], -FBOX_H[k], FBOX_H[k]); if (q[k] != pl[k]) inside = 0; }

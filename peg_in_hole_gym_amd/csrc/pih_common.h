@@ -640,8 +640,10 @@ template <class W> PIH_HD void collide(W& w, Shared& sh, const Params& P) {
         if (dx <= 0 && dy <= 0) { if (dx > dy) { ga = sa; gr = 0; sdf = dx; } else { ga = 0; gr = sr; sdf = dy; } }
         else { real mx = dx > 0 ? dx : 0, my = dy > 0 ? dy : 0; sdf = (real)sqrt(mx * mx + my * my); ga = sa * mx / sdf; gr = sr * my / sdf; }
         depth = sdf - r;
-        if (depth < margin) {
-          V3 rh = rho > (real)1e-9 ? mk(0, d.y / rho, d.z / rho) : mk(0, 1, 0);
+        // (on the axis the nearest point of the wall is a whole circle: there is no radial direction, and rho < Rin means gr != 0 -- no
+        //  contact rather than one along an invented direction; reached only at a margin above Rin - r = 5.36 mm)
+        if (depth < margin && rho > (real)1e-9) {
+          V3 rh = mk(0, d.y / rho, d.z / rho);
           n = mk(ga, gr * rh.y, gr * rh.z); p = sp - (r + (real)0.5 * depth) * n; L = ANL + SAMP_LINK[i]; valid = true;
         }
       }
@@ -715,7 +717,9 @@ template <class W> PIH_HD void collide(W& w, Shared& sh, const Params& P) {
     if (used > allowed) { used = allowed; w.alloc_reset(before + allowed); }
     nca += used;
   }
-  // finger pad boxes (arm links 7, 8)
+  // finger pad boxes (arm links 7, 8); pre-filter on the distance to the box centre, exact for any margin: a sphere within r + margin of
+  // the box has its centre within that plus the half diagonal (+ 0.1 mm against rounding, as the self-collision broad phase)
+  const real padreach = norm(ld3(FBOX_H)) + r + margin + (real)1e-4;
   for (int f = 0; f < 2; f++) {
     const int LF = PIH_FINGER_LINK0 + f;
     M3 Rf = ldm(sh.a.LR[LF]); V3 bc = ld3(sh.LO[LF]) + mul(Rf, ld3(FBOX_C[f])); V3 bh = ld3(FBOX_H);
@@ -725,7 +729,7 @@ template <class W> PIH_HD void collide(W& w, Shared& sh, const Params& P) {
       bool valid = false; V3 n = mk(0, 0, 0), p = mk(0, 0, 0); real depth = 0; int L = 0;
       if (in) {
         V3 sp = ld3(sh.a.SP[i]); V3 d = sp - bc;
-        if (dot(d, d) <= (real)(0.05 * 0.05)) {
+        if (dot(d, d) <= padreach * padreach) {
           V3 pl = tmul(Rf, d);
           V3 q = mk(clampr(pl.x, -bh.x, bh.x), clampr(pl.y, -bh.y, bh.y), clampr(pl.z, -bh.z, bh.z));
           bool inside = q.x == pl.x && q.y == pl.y && q.z == pl.z;
