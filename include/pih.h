@@ -16,6 +16,8 @@
  *   pih_render_cam replaces p.computeViewMatrix / computeProjectionMatrixFOV / getCameraImage for the 'random-fly' task (README.md:38; the
  *                           task class and with it its camera are not in the snapshot): a caller-given camera over the UR5's collision
  *                           capsules, the object's sphere cover and the table plane
+ *   pih_render_view        the same three calls for the peg-in-hole task from ANY viewpoint: the scene of pih_render plus a stand-in arm,
+ *                           with the packed output formats and per-env cameras of pih_render_cam
  *   pih_get_state replaces  p.getLinkState / p.getJointState / (north_star) getContactPoints normal force read-backs
  *
  * Conventions: every call returns 0 on success, <0 on error (pih_last_error gives the text).  All *_dev pointers
@@ -245,6 +247,8 @@ int pih_render_ex(pih_handle* h, float* out_dev, int width, int height, int env_
 #define PIH_SEG_NONE 255        /* and nothing (background) */
 int pih_render_cam(pih_handle* h, float* out_dev, const float* cam /* [PIH_CAM_WORDS] on the host, NULL = default; PIH_RENDER_CAM_DEVICE: [env_count][PIH_CAM_WORDS] on the device */,
                    int width, int height, int env_begin, int env_count, int flags, void* stream);
+/* free camera of the peg-in-hole task -- the scene of pih_render plus a stand-in arm from any viewpoint, with the output formats and the
+ * per-env cameras above: declared in pih_render_view.h, which the end of this header includes */
 /* grasp-rectangle label images of random_grasp (envs/peg_in_hole.py:72-99,116) from the angle each env recorded when its
  * state machine entered state 2 (PIH_S_GRASP_ANGLE): out_dev float[env_count, 4, size, size] = pos (50 inside the rectangle),
  * sin(2 angle), cos(2 angle), width in pixels; meta_dev (may be NULL) float[env_count, 5] = x, y, angle [deg], width, length.
@@ -265,4 +269,5 @@ const char* pih_last_error(pih_handle* h);
 #ifdef __cplusplus
 }
 #endif
+#include "pih_render_view.h"
 #endif

@@ -15,6 +15,11 @@ FLY_CAM_DEFAULT = (1.6, 0.0, 1.2, 0.0, 0.0, 0.2, 0.0, 0.0, 1.0, 60.0, 1.0, 0.01,
 RENDER_SHADED, RENDER_CAM_EE = 1, 2                # flags of pih_render_ex / pih_render_cam
 RENDER_OUT_RGBA8, RENDER_OUT_DEPTH, RENDER_CAM_DEVICE = 4, 8, 16     # pih_render_cam: output format (at most one), per-env cameras in device memory
 SEG_OBJECT, SEG_TABLE, SEG_NONE = 6, 7, 255        # seg byte of RENDER_OUT_RGBA8: UR5 links are 0 .. 5
+# pih_render_view (peg-in-hole from any viewpoint): the frame flag of the reference's wrist camera, the seg bytes, the two preset cameras
+RENDER_CAM_EE_POS = 32                             # eye and target offset by the grasp-target's position, axes env-local
+VIEW_SEG_HOLE, VIEW_SEG_TABLE, VIEW_SEG_PIPE0 = 9, 10, 32     # arm links are 0 .. 6 (the hand is 6), fingers 7 and 8, pipe capsule s is VIEW_SEG_PIPE0 + s
+VIEW_CAM_WRIST = (0.0, 0.0, 0.0, 0.0, 0.0, -10.0, 0.0, 1.0, 0.0, 60.0, 1.0, 0.001, 1000.0)     # PIH_VIEW_CAM_WRIST, with RENDER_CAM_EE_POS: PegInHole.render's camera
+VIEW_CAM_OVERVIEW = (1.33, -0.02, 1.05, 0.05, -0.25, 0.3, 0.0, 0.0, 1.0, 40.0, 1.0, 0.01, 100.0)  # PIH_VIEW_CAM_OVERVIEW
 FIELD_STATE, FIELD_TIP_POSE, FIELD_CONTACT_FORCE, FIELD_DEBUG, FIELD_EE_POS = 0, 1, 2, 3, 4
 TASK_PEG_IN_HOLE, TASK_RANDOM_FLY = 0, 1
 # state record word offsets (PIH_S_*)
@@ -32,6 +37,7 @@ DBG_CYCLES, DBG_T_START, DBG_T_END, DBG_HW_ID, DBG_XCC_ID = 900, 940, 943, 946, 
 
 EXPORTS = ["pih_default_config", "pih_abi_version", "pih_task_dims", "pih_object_name", "pih_create", "pih_destroy", "pih_reset", "pih_reseed", "pih_step", "pih_step_n",
            "pih_get_state", "pih_set_state", "pih_ik", "pih_ik_ur5", "pih_render", "pih_render_ex", "pih_render_cam", "pih_grasp_labels", "pih_timing", "pih_timing2", "pih_set_timing", "pih_last_error"]
+VIEW_EXPORTS = ["pih_render_view"]      # what include/pih_render_view.h declares on top of that (tests/test_peg_view.py compares it with that header)
 
 
 class PihConfig(C.Structure):
@@ -83,6 +89,7 @@ def load():
     L.pih_render_ex.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]
     L.pih_render_cam.argtypes = [vp, vp, vp,      # (camera: a (c_float * CAM_WORDS) array, None, or with RENDER_CAM_DEVICE a device address)
                                   C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]
+    L.pih_render_view.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]      # (camera: as pih_render_cam; None = the wrist preset)
     L.pih_grasp_labels.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp]
     L.pih_reseed.argtypes = [vp, C.c_uint64]
     L.pih_timing.argtypes = [vp, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int64)]

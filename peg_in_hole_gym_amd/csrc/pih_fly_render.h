@@ -250,7 +250,7 @@ PIH_HHD int cam_degenerate(const float* c) {
 // The pixel grid, shared by the kernel and the host build: pixel-centre and tile-edge coordinates on the camera plane
 struct FlyGrid {
   real sx, sy, tx, ty;
-  PIH_HD FlyGrid(const FlyScene& sc, int W, int H) : sx((real)2 / (real)W), sy((real)2 / (real)H), tx(sc.tx), ty(sc.ty) {}
+  template <class S /* FlyScene, view::ViewScene */> PIH_HD FlyGrid(const S& sc, int W, int H) : sx((real)2 / (real)W), sy((real)2 / (real)H), tx(sc.tx), ty(sc.ty) {}
   PIH_HD real xc(int j) const { return (sx * ((real)j + (real)0.5) - (real)1) * tx; }
   PIH_HD real yc(int i) const { return ((real)1 - sy * ((real)i + (real)0.5)) * ty; }
   PIH_HD real xedge(int j) const { return (sx * (real)j - (real)1) * tx; }

@@ -18,6 +18,9 @@ using namespace pih;
 namespace pih {
 void fly_image_launch(int fmt, dim3 grid, hipStream_t stream, const float* state, void* out, const fly::FlyCam& cam, const float* cam_dev,
                       int n, int object, int env_begin, int W, int H, int rows_per_strip, int flags);
+// pih_view.hip: the free camera of the peg-in-hole task
+void view_launch(int fmt, dim3 grid, hipStream_t stream, const float* state, void* out, const fly::FlyCam& cam, const float* cam_dev,
+                 int env_begin, int W, int H, int rows_per_strip, int flags);
 }
 
 // ------------------------------------------------------------------------------------------------ kernels
@@ -913,6 +916,43 @@ int pih_render_cam(pih_handle* h, float* out_dev, const float* cam_ptr, int widt
   else      // the float4 image of one host camera: the kernel it has always been
     hipLaunchKernelGGL(pih_fly_render_kernel, dim3(strips, env_count), dim3(RENDER_THREADS), 0, (hipStream_t)stream, h->state, out_dev, cam,
                        h->cfg.n_envs, h->P.object, env_begin, width, height, rows, flags);
+  HIPCHK(h, hipGetLastError());
+  return 0;
+}
+
+int pih_render_view(pih_handle* h, void* out_dev, const float* cam_ptr, int width, int height, int env_begin, int env_count, int flags, void* stream) {
+  const int fmt = flags & (PIH_RENDER_OUT_RGBA8 | PIH_RENDER_OUT_DEPTH);
+  const bool cam_on_device = (flags & PIH_RENDER_CAM_DEVICE) != 0;
+  if (!h || !out_dev || width <= 0 || height <= 0 || env_begin < 0 || env_count <= 0 || env_begin + env_count > h->cfg.n_envs) {
+    if (h) h->err = "pih_render_view: bad arguments";
+    return -2;
+  }
+  if (h->fly) { h->err = "pih_render_view: this camera belongs to the peg-in-hole task (random-fly: pih_render_cam)"; return -2; }
+  if ((flags & ~(PIH_RENDER_SHADED | PIH_RENDER_CAM_EE | PIH_RENDER_CAM_EE_POS | PIH_RENDER_OUT_RGBA8 | PIH_RENDER_OUT_DEPTH | PIH_RENDER_CAM_DEVICE)) != 0) {
+    h->err = "pih_render_view: unknown flag"; return -2;
+  }
+  if (fmt == (PIH_RENDER_OUT_RGBA8 | PIH_RENDER_OUT_DEPTH)) { h->err = "pih_render_view: PIH_RENDER_OUT_RGBA8 and PIH_RENDER_OUT_DEPTH exclude each other"; return -2; }
+  if ((flags & PIH_RENDER_CAM_EE) && (flags & PIH_RENDER_CAM_EE_POS)) { h->err = "pih_render_view: PIH_RENDER_CAM_EE and PIH_RENDER_CAM_EE_POS exclude each other"; return -2; }
+  if (cam_on_device && !cam_ptr) { h->err = "pih_render_view: PIH_RENDER_CAM_DEVICE needs a camera array (NULL = the wrist preset is for a host camera)"; return -2; }
+  if ((reinterpret_cast<uintptr_t>(out_dev) & 15) != 0) { h->err = "pih_render_view: out_dev must be 16-byte aligned"; return -2; }
+  if (env_count > 65535) { h->err = "pih_render_view: env_count > 65535 per call"; return -2; }
+  fly::FlyCam cam = {PIH_VIEW_CAM_WRIST};
+  if (!cam_on_device) {
+    if (cam_ptr) memcpy(cam.w, cam_ptr, sizeof cam.w);
+    else flags = (flags & ~PIH_RENDER_CAM_EE) | PIH_RENDER_CAM_EE_POS;      // the wrist preset, whatever frame flag was passed
+    static const char* const what[] = {nullptr, "eye == target (or not finite)", "up is zero or parallel to the view axis target - eye", "fov outside (0, 180) degrees",
+                                       "aspect <= 0", "near <= 0", "far <= near"};
+    // (a NaN or an infinity is looked for in the words' bits, as integers: the library's floating-point code is built with -ffast-math)
+    static const char* const word[] = {"eye", "eye", "eye", "target", "target", "target", "up", "up", "up", "fov", "aspect", "near", "far"};
+    uint32_t bits[PIH_CAM_WORDS]; memcpy(bits, cam.w, sizeof bits);
+    for (int i = 0; i < PIH_CAM_WORDS; i++)
+      if ((bits[i] & 0x7f800000u) == 0x7f800000u) { h->err = std::string("pih_render_view: degenerate camera: ") + word[i] + " is not finite"; return -2; }
+    const int code = fly::cam_degenerate(cam.w);
+    if (code != fly::CAM_OK) { h->err = std::string("pih_render_view: degenerate camera: ") + what[code]; return -2; }
+  }
+  PIH_ENTER(h);
+  int rows; const int strips = render_strips(height, env_count, &rows);
+  view_launch(fmt, dim3(strips, env_count), (hipStream_t)stream, h->state, out_dev, cam, cam_on_device ? cam_ptr : nullptr, env_begin, width, height, rows, flags);
   HIPCHK(h, hipGetLastError());
   return 0;
 }

@@ -14,7 +14,9 @@
 // ballot of that test is the tile's primitive list (iterated with scalar bit scans, no LDS list), and one tile row = 64
 // consecutive pixels = one coalesced 1 KB store.  Most tiles see the table plane and 0-2 capsules.
 #pragma once
-#include "pih_device.h"
+#ifndef PIH_PLATFORM_DEFINED
+#include "pih_device.h"      // (a host build brings its own wave layer and pih_common.h first)
+#endif
 #include "pih_raycast.h"
 
 namespace pih {
@@ -73,17 +75,42 @@ PIH_HD real ray_tube(V3 o, V3 d) {
   return best;
 }
 
+// surface normals at a hit point ph, shared by the wrist camera below and the free camera of pih_view.h
+PIH_HD V3 capsule_normal(V3 ph, V3 a, V3 b) {
+  const V3 ba = b - a;
+  real q = dot(ph - a, ba) / max_(dot(ba, ba), (real)1e-20);
+  q = q < 0 ? (real)0 : (q > 1 ? (real)1 : q);
+  const V3 r = ph - (a + q * ba);
+  return ((real)1 / max_(norm(r), (real)1e-12)) * r;
+}
+PIH_HD V3 tube_normal(V3 ph) {
+  const V3 oc = ph - ld3(HOLE_POS);
+  const real rr = (real)sqrt(oc.y * oc.y + oc.z * oc.z);
+  if (absr(oc.x) >= PIH_HOLE_HALFLEN - (real)1e-5) return mk(oc.x > 0 ? (real)1 : (real)-1, 0, 0);
+  const real sgn = rr > (real)0.5 * (PIH_HOLE_RIN + PIH_HOLE_ROUT) ? (real)1 : (real)-1; const real k = sgn / max_(rr, (real)1e-12);
+  return mk(0, oc.y * k, oc.z * k);
+}
+PIH_HD V3 box_normal(V3 ph, const M3& R, V3 c) {
+  const V3 pl = tmul(R, ph - c), h = ld3(FBOX_H);
+  const real ax = absr(pl.x) / h.x, ay = absr(pl.y) / h.y, az = absr(pl.z) / h.z;
+  V3 nl = mk(0, 0, 0);
+  if (ax >= ay && ax >= az) nl.x = pl.x > 0 ? (real)1 : (real)-1; else if (ay >= az) nl.y = pl.y > 0 ? (real)1 : (real)-1; else nl.z = pl.z > 0 ? (real)1 : (real)-1;
+  return mul(R, nl);
+}
+// pipe vertex of collision sample i (a sample with SAMP_VERTEX set), into row k = number of vertices before it
+PIH_HD void place_pipe_vertex(const Shared& sh, real (*vtx)[3], int i) {
+  int k = 0;
+  for (int j = 0; j < i; j++) k += SAMP_VERTEX[j];
+  const int L = ANL + SAMP_LINK[i];
+  st3(vtx[k], ld3(sh.LO[L]) + mul(ldm(sh.a.LR[L]), mk(0, SAMP_Y[i], 0)));
+}
+
 // Scene set-up (all threads of the workgroup call it): forward kinematics, primitive poses and their screen-space bounds.
 template <class W> PIH_HD void scene_setup(W& w, Shared& sh, Scene& sc, int tid) {
   fk_all(w, sh);
   w.sync();
   if (tid == 0) { V3 p; M3 R; ee_pose(sh, p, R); st3(sc.eye, p); }
-  if (tid < NSAMP && SAMP_VERTEX[tid]) {
-    int k = 0;
-    for (int i = 0; i < tid; i++) k += SAMP_VERTEX[i];
-    int L = ANL + SAMP_LINK[tid];
-    st3(sc.vtx[k], ld3(sh.LO[L]) + mul(ldm(sh.a.LR[L]), mk(0, SAMP_Y[tid], 0)));
-  }
+  if (tid < NSAMP && SAMP_VERTEX[tid]) place_pipe_vertex(sh, sc.vtx, tid);
   if (tid < 2) {
     int L = PIH_FINGER_LINK0 + tid;
     M3 R = ldm(sh.a.LR[L]);
@@ -169,6 +196,8 @@ PIH_HD real4 shade(const Scene& sc, unsigned prims, real xc, real yc, int flags)
     // surface normal at the hit point, Lambert term against the fixed light
     const V3 ph = eye + best * d;
     V3 n = mk(0, 0, 1);
+    // (what capsule_normal, tube_normal and box_normal above compute, which pih_view.h calls.  Written out here as it always was: with the
+    //  calls pih_render_kernel comes out one instruction longer and in another schedule, and tools/isa_fingerprint.py is to show it unchanged)
     if (kind == 2) {
       const V3 a = ld3(sc.vtx[which]), ba = ld3(sc.vtx[which + 1]) - a;
       real q = dot(ph - a, ba) / max_(dot(ba, ba), (real)1e-20);

@@ -114,6 +114,11 @@ class PegInHole(MetaEnv):
         img = self._backend.render(300, 300, shaded=True)
         return (img.detach().cpu().numpy() if hasattr(img, "detach") else np.asarray(img))[0].astype(np.float64)
 
+    def render_view(self, **kw):
+        """the scene from any viewpoint, the arm included (PihVecEnv.render_view: camera, frame, fmt, shaded, width, height, ...) -> the
+        backend's image tensor for all its envs"""
+        return self._backend.render_view(**kw)
+
 
 class RandomFly(MetaEnv):
     """'random-fly' (README.md:38: task='random-fly', args=['Banana', 1/120.]): the UR5 of assets/urdf/ur5.urdf driven by

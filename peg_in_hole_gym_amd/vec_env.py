@@ -209,6 +209,33 @@ class PihVecEnv:
 
     _RENDER_FMT = {"float4": (0, torch.float32, (4,)), "rgba8": (_lib.RENDER_OUT_RGBA8, torch.uint8, (4,)), "depth": (_lib.RENDER_OUT_DEPTH, torch.float32, ())}
 
+    def _camera_arg(self, what, camera, count):
+        """camera argument of render / render_view -> (ctypes argument, flag): None -> (None, 0); 13 numbers -> a host array; [count, 13] -> the
+        device address of a float32 tensor on this handle's device (used in place, or converted and uploaded) with RENDER_CAM_DEVICE"""
+        if camera is None:
+            return None, 0
+        if (camera.ndim if hasattr(camera, "ndim") else np.ndim(camera)) >= 2:
+            if not (torch.is_tensor(camera) and camera.dtype == torch.float32 and self._here(camera) and camera.is_contiguous()):
+                camera = torch.as_tensor(np.asarray(camera.cpu() if torch.is_tensor(camera) else camera, dtype=np.float32)).to(self.device).contiguous()
+            if tuple(camera.shape) != (count, _lib.CAM_WORDS):
+                raise ValueError("%s: per-env cameras must have shape [%d, %d] (one row per env of the call), got %s" % (what, count, _lib.CAM_WORDS, tuple(camera.shape)))
+            self._cam_keep = camera          # (the uploaded copy lives until the next call: the launch is asynchronous)
+            return C.c_void_p(camera.data_ptr()), _lib.RENDER_CAM_DEVICE
+        vals = [float(x) for x in camera]
+        if len(vals) != _lib.CAM_WORDS:
+            raise ValueError("%s: camera must have %d numbers (eye, target, up, fov, aspect, near, far), got %d" % (what, _lib.CAM_WORDS, len(vals)))
+        return (C.c_float * _lib.CAM_WORDS)(*vals), 0
+
+    def _out_arg(self, what, out, fmt, count, height, width):
+        """output tensor of render / render_view for format `fmt` -> (tensor, format flag)"""
+        fmt_flag, dtype, tail = self._RENDER_FMT[fmt]
+        shape = (count, height, width) + tail
+        if out is None:
+            out = torch.empty(shape, dtype=dtype, device=self.device)
+        elif fmt != "float4" and not (torch.is_tensor(out) and out.dtype == dtype and tuple(out.shape) == shape and self._here(out) and out.is_contiguous()):
+            raise ValueError("%s: out must be a contiguous %s tensor of shape %s on %s for fmt=%r" % (what, dtype, shape, self.device, fmt))
+        return out, fmt_flag
+
     def render(self, width=300, height=300, env_begin=0, env_count=None, out=None, shaded=False, camera=None, ee_frame=False, fmt="float4"):
         """Camera image of a block of envs at the current state (analytic ray caster): float32 [count, height, width, 4] =
         (depth buffer, r, g, b), RGB on the 0..255 scale, flat per object or (shaded=True) times ambient + diffuse of TinyRenderer's
@@ -236,30 +263,44 @@ class PihVecEnv:
             raise ValueError("render: fmt must be one of %s, got %r" % (sorted(self._RENDER_FMT), fmt))
         if not fly and fmt != "float4":
             raise ValueError("render: the peg-in-hole wrist camera has the one format 'float4'; 'rgba8' / 'depth' belong to the random-fly task")
-        fmt_flag, dtype, tail = self._RENDER_FMT[fmt]
-        cam, cam_flag = None, 0
-        if camera is not None and (camera.ndim if hasattr(camera, "ndim") else np.ndim(camera)) >= 2:
-            if not (torch.is_tensor(camera) and camera.dtype == torch.float32 and self._here(camera) and camera.is_contiguous()):
-                camera = torch.as_tensor(np.asarray(camera.cpu() if torch.is_tensor(camera) else camera, dtype=np.float32)).to(self.device).contiguous()
-            if tuple(camera.shape) != (count, _lib.CAM_WORDS):
-                raise ValueError("render: per-env cameras must have shape [%d, %d] (one row per env of the call), got %s" % (count, _lib.CAM_WORDS, tuple(camera.shape)))
-            cam, cam_flag = C.c_void_p(camera.data_ptr()), _lib.RENDER_CAM_DEVICE
-        elif camera is not None:
-            vals = [float(x) for x in camera]
-            if len(vals) != _lib.CAM_WORDS:
-                raise ValueError("render: camera must have %d numbers (eye, target, up, fov, aspect, near, far), got %d" % (_lib.CAM_WORDS, len(vals)))
-            cam = (C.c_float * _lib.CAM_WORDS)(*vals)
-        shape = (count, height, width) + tail
-        if out is None:
-            out = torch.empty(shape, dtype=dtype, device=self.device)
-        elif fmt != "float4" and not (torch.is_tensor(out) and out.dtype == dtype and tuple(out.shape) == shape and self._here(out) and out.is_contiguous()):
-            raise ValueError("render: out must be a contiguous %s tensor of shape %s on %s for fmt=%r" % (dtype, shape, self.device, fmt))
+        cam, cam_flag = self._camera_arg("render", camera, count)
+        out, fmt_flag = self._out_arg("render", out, fmt, count, height, width)
         with torch.cuda.device(self.device):
             if fly:
                 flags = (_lib.RENDER_SHADED if shaded else 0) | (_lib.RENDER_CAM_EE if ee_frame else 0) | fmt_flag | cam_flag
                 self._chk(self.L.pih_render_cam(self.h, out.data_ptr(), cam, width, height, env_begin, count, flags, self._stream()), "pih_render_cam")
             else:
                 self._chk(self.L.pih_render_ex(self.h, out.data_ptr(), width, height, env_begin, count, 1 if shaded else 0, self._stream()), "pih_render_ex")
+        return out
+
+    _VIEW_FRAME = {"env": 0, "ee": _lib.RENDER_CAM_EE, "ee_pos": _lib.RENDER_CAM_EE_POS}
+
+    def render_view(self, width=300, height=300, env_begin=0, env_count=None, out=None, shaded=False, camera=None, frame="env", fmt="float4"):
+        """peg-in-hole from any viewpoint (pih_render_view): the scene of render() -- table, pipe, hole, finger pads -- plus a stand-in
+        arm (one capsule per link, the hand's spheres), at the current state; nothing of the state changes.
+        camera = 13 numbers as in render() of the random-fly task, one camera for all envs of the call; None = the wrist preset
+            (_lib.VIEW_CAM_WRIST in the "ee_pos" frame: the camera of render(), whatever `frame` says); _lib.VIEW_CAM_OVERVIEW shows the
+            whole arm from the side.  camera of shape [count, 13]: one camera per env of the call, read by the kernel from device memory
+            (a float32 tensor on this handle's device is used in place); such cameras are not validated on the host: an env whose row
+            is degenerate gets the background image.  Following each env's peg tip without a host round trip:
+                render_view(camera=tracking_cameras(env.tip_pose()[:, :3], eye))
+        frame: "env" = the env-local frame; "ee" = the grasp-target frame (pybullet link 11): the camera turns with the hand;
+            "ee_pos" = eye and target offset by the grasp-target's position, axes env-local: it follows the hand and does not turn.
+        fmt: "float4" float32 [count, height, width, 4] (depth buffer, r, g, b); "rgba8" uint8 [count, height, width, 4] (r, g, b, seg),
+            seg = arm link 0..6 (the hand is 6), fingers 7 and 8, _lib.VIEW_SEG_HOLE, _lib.VIEW_SEG_TABLE, _lib.VIEW_SEG_PIPE0 + pipe
+            capsule 0..23, _lib.SEG_NONE; "depth" float32 [count, height, width].  out: as in render()."""
+        count = self.n - env_begin if env_count is None else env_count
+        if self.task_id != _lib.TASK_PEG_IN_HOLE:
+            raise ValueError("render_view: this camera belongs to the peg-in-hole task (random-fly: render(camera=...))")
+        if fmt not in self._RENDER_FMT:
+            raise ValueError("render_view: fmt must be one of %s, got %r" % (sorted(self._RENDER_FMT), fmt))
+        if frame not in self._VIEW_FRAME:
+            raise ValueError("render_view: frame must be one of %s, got %r" % (sorted(self._VIEW_FRAME), frame))
+        cam, cam_flag = self._camera_arg("render_view", camera, count)
+        out, fmt_flag = self._out_arg("render_view", out, fmt, count, height, width)
+        flags = (_lib.RENDER_SHADED if shaded else 0) | self._VIEW_FRAME[frame] | fmt_flag | cam_flag
+        with torch.cuda.device(self.device):
+            self._chk(self.L.pih_render_view(self.h, out.data_ptr(), cam, width, height, env_begin, count, flags, self._stream()), "pih_render_view")
         return out
 
     def tracking_cameras(self, eye, up=(0.0, 0.0, 1.0), fov=60.0, aspect=1.0, near=0.01, far=100.0):

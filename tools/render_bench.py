@@ -5,7 +5,11 @@ usage: render_bench.py [n]
            the free camera of the random-fly task (pih_render_cam, default camera): float4 flat and shaded, rgba8 flat and shaded, depth,
            float4 and rgba8 with per-env cameras in device memory, alternating with the peg-in-hole wrist camera at the same n and size as
            the yardstick of the same run; stores = 16, 4 and 4 bytes per pixel against the 6.3 TB/s of HBM bandwidth a kernel can reach
-           on the MI355X; the last lines compare rgba8 and depth with float4 of the same run"""
+           on the MI355X; the last lines compare rgba8 and depth with float4 of the same run
+       render_bench.py --task peg-view [--n N] --width W --height H [--repeats K]
+           the free camera of the peg-in-hole task (pih_render_view): the wrist preset in float4, rgba8 and depth, the overview camera in
+           float4 and rgba8, per-env cameras (the overview in every row) in rgba8, alternating with the unchanged pih_render float4 of
+           the same handle as the yardstick of the same run; ms, Mpixel/s and GB/s written for each case"""
 import sys, os, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -58,10 +62,44 @@ def fly_bench():
         print("%-40s median %.3f ms vs float4 flat %.3f ms + its spread %.3f ms: %s" % (name, med, ref[K // 2], spread, "within" if med <= ref[K // 2] + spread else "SLOWER"))
 
 
+def peg_view_bench():
+    n, W, H, K = _arg("--n", 1024), _arg("--width", 300), _arg("--height", 300), max(5, _arg("--repeats", 5))
+    peg = PihVecEnv(n, mode=1, dv=0.05)
+    peg.step_n(540)                              # grippers hovering above their pipes, as in the default timing
+    out = torch.empty(n, H, W, 4, device="cuda")
+    out8 = torch.empty(n, H, W, 4, dtype=torch.uint8, device="cuda")
+    outd = torch.empty(n, H, W, device="cuda")
+    over = _lib.VIEW_CAM_OVERVIEW
+    cams = torch.tensor([over] * n, device="cuda")      # per-env cameras in device memory: the overview in every row, so the pixels are the same work
+    cases = (("pih_render float4 (wrist, yardstick)", 16, lambda: peg.render(W, H, out=out)),
+             ("view wrist float4", 16, lambda: peg.render_view(W, H, out=out)),
+             ("view wrist rgba8", 4, lambda: peg.render_view(W, H, out=out8, fmt="rgba8")),
+             ("view wrist depth", 4, lambda: peg.render_view(W, H, out=outd, fmt="depth")),
+             ("view overview float4", 16, lambda: peg.render_view(W, H, out=out, camera=over)),
+             ("view overview rgba8", 4, lambda: peg.render_view(W, H, out=out8, camera=over, fmt="rgba8")),
+             ("view overview rgba8, per-env cameras", 4, lambda: peg.render_view(W, H, out=out8, camera=cams, fmt="rgba8")))
+    for _, _, f in cases:                        # warm-up
+        for _ in range(2):
+            f()
+    torch.cuda.synchronize()
+    ms = {name: [] for name, _, _ in cases}
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+    for _ in range(K):                           # alternating: every repeat times each case once
+        for name, _, f in cases:
+            ev[0].record(); f(); ev[1].record(); ev[1].synchronize()
+            ms[name].append(ev[0].elapsed_time(ev[1]))
+    ref = sorted(ms[cases[0][0]])[K // 2]
+    for name, bpp, _ in cases:
+        v = sorted(ms[name]); med = v[len(v) // 2]
+        print("%-40s %d envs x %dx%d: median %.3f ms (min %.3f, max %.3f, %d repeats) = %.0f Mpixel/s, %d B/pixel stored: %.1f GB/s written, %.2f x the yardstick's time"
+              % (name, n, W, H, med, v[0], v[-1], K, n * W * H / med / 1e3, bpp, n * W * H * bpp / med / 1e6, med / ref))
+
+
 if "--task" in sys.argv:
-    if _arg("--task", "") != "random-fly":
-        sys.exit("render_bench.py: --task takes random-fly (the peg-in-hole timing is the default: render_bench.py [n])")
-    fly_bench()
+    task = _arg("--task", "")
+    if task not in ("random-fly", "peg-view"):
+        sys.exit("render_bench.py: --task takes random-fly or peg-view (the peg-in-hole wrist camera timing is the default: render_bench.py [n])")
+    fly_bench() if task == "random-fly" else peg_view_bench()
     sys.exit(0)
 
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 1024
