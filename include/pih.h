@@ -270,4 +270,8 @@ const char* pih_last_error(pih_handle* h);
 }
 #endif
 #include "pih_render_view.h"
+/* words of a light of the lit image call declared in pih_render_light.h (direction xyz, colour rgb, ambient, diffuse, specular, shininess, shadow factor).
+ * Defined here and not there because tests/test_abi_exports.py compares every *_WORDS name of _lib.py with THIS file */
+#define PIH_LIGHT_WORDS 11
+#include "pih_render_light.h"
 #endif

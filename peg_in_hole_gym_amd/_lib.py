@@ -20,6 +20,10 @@ RENDER_CAM_EE_POS = 32                             # eye and target offset by th
 VIEW_SEG_HOLE, VIEW_SEG_TABLE, VIEW_SEG_PIPE0 = 9, 10, 32     # arm links are 0 .. 6 (the hand is 6), fingers 7 and 8, pipe capsule s is VIEW_SEG_PIPE0 + s
 VIEW_CAM_WRIST = (0.0, 0.0, 0.0, 0.0, 0.0, -10.0, 0.0, 1.0, 0.0, 60.0, 1.0, 0.001, 1000.0)     # PIH_VIEW_CAM_WRIST, with RENDER_CAM_EE_POS: PegInHole.render's camera
 VIEW_CAM_OVERVIEW = (1.33, -0.02, 1.05, 0.05, -0.25, 0.3, 0.0, 0.0, 1.0, 40.0, 1.0, 0.01, 100.0)  # PIH_VIEW_CAM_OVERVIEW
+# pih_render_lit (include/pih_render_light.h): both free cameras under a caller-given light, with a specular term and cast shadows
+LIGHT_WORDS = 11   # direction xyz (towards the light, env-local), colour rgb, ambient, diffuse, specular, shininess, shadow factor (1 = no shadows)
+LIGHT_DEFAULT = (-50.0, 30.0, 100.0, 1.0, 1.0, 1.0, 0.6, 0.35, 0.05, 2.0, 0.8)     # PIH_LIGHT_DEFAULT
+RENDER_LIGHT_DEVICE = 64                           # the light argument is a device pointer float[env_count, LIGHT_WORDS], one light per env
 FIELD_STATE, FIELD_TIP_POSE, FIELD_CONTACT_FORCE, FIELD_DEBUG, FIELD_EE_POS = 0, 1, 2, 3, 4
 TASK_PEG_IN_HOLE, TASK_RANDOM_FLY = 0, 1
 # state record word offsets (PIH_S_*)
@@ -37,6 +41,7 @@ DBG_CYCLES, DBG_T_START, DBG_T_END, DBG_HW_ID, DBG_XCC_ID = 900, 940, 943, 946, 
 
 EXPORTS = ["pih_default_config", "pih_abi_version", "pih_task_dims", "pih_object_name", "pih_create", "pih_destroy", "pih_reset", "pih_reseed", "pih_step", "pih_step_n",
            "pih_get_state", "pih_set_state", "pih_ik", "pih_ik_ur5", "pih_render", "pih_render_ex", "pih_render_cam", "pih_grasp_labels", "pih_timing", "pih_timing2", "pih_set_timing", "pih_last_error"]
+LIGHT_EXPORTS = ["pih_render_lit"]      # what include/pih_render_light.h declares (tests/test_render_lit.py compares it with that header)
 VIEW_EXPORTS = ["pih_render_view"]      # what include/pih_render_view.h declares on top of that (tests/test_peg_view.py compares it with that header)
 
 
@@ -90,6 +95,7 @@ def load():
     L.pih_render_cam.argtypes = [vp, vp, vp,      # (camera: a (c_float * CAM_WORDS) array, None, or with RENDER_CAM_DEVICE a device address)
                                   C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]
     L.pih_render_view.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]      # (camera: as pih_render_cam; None = the wrist preset)
+    L.pih_render_lit.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]      # (camera as above; light: a (c_float * LIGHT_WORDS) array, None = LIGHT_DEFAULT, or with RENDER_LIGHT_DEVICE a device address)
     L.pih_grasp_labels.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp]
     L.pih_reseed.argtypes = [vp, C.c_uint64]
     L.pih_timing.argtypes = [vp, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int64)]

@@ -21,6 +21,10 @@ void fly_image_launch(int fmt, dim3 grid, hipStream_t stream, const float* state
 // pih_view.hip: the free camera of the peg-in-hole task
 void view_launch(int fmt, dim3 grid, hipStream_t stream, const float* state, void* out, const fly::FlyCam& cam, const float* cam_dev,
                  int env_begin, int W, int H, int rows_per_strip, int flags);
+// pih_lit.hip: both cameras under a caller-given light, with a specular term and cast shadows
+int lit_light_check(const float* words, const char** what);
+void lit_launch(bool fly_task, int fmt, dim3 grid, hipStream_t stream, const float* state, void* out, const fly::FlyCam& cam, const float* cam_dev,
+                const float* light, const float* light_dev, int n, int object, int env_begin, int W, int H, int rows_per_strip, int flags);
 }
 
 // ------------------------------------------------------------------------------------------------ kernels
@@ -953,6 +957,51 @@ int pih_render_view(pih_handle* h, void* out_dev, const float* cam_ptr, int widt
   PIH_ENTER(h);
   int rows; const int strips = render_strips(height, env_count, &rows);
   view_launch(fmt, dim3(strips, env_count), (hipStream_t)stream, h->state, out_dev, cam, cam_on_device ? cam_ptr : nullptr, env_begin, width, height, rows, flags);
+  HIPCHK(h, hipGetLastError());
+  return 0;
+}
+
+int pih_render_lit(pih_handle* h, void* out_dev, const float* cam_ptr, const float* light_ptr, int width, int height, int env_begin, int env_count, int flags, void* stream) {
+  const int fmt = flags & (PIH_RENDER_OUT_RGBA8 | PIH_RENDER_OUT_DEPTH);
+  const bool cam_on_device = (flags & PIH_RENDER_CAM_DEVICE) != 0, light_on_device = (flags & PIH_RENDER_LIGHT_DEVICE) != 0;
+  if (!h || !out_dev || width <= 0 || height <= 0 || env_begin < 0 || env_count <= 0 || env_begin + env_count > h->cfg.n_envs) {
+    if (h) h->err = "pih_render_lit: bad arguments";
+    return -2;
+  }
+  // the flags of the handle's free camera (pih_render_cam / pih_render_view), plus the device light
+  const int known = PIH_RENDER_SHADED | PIH_RENDER_CAM_EE | PIH_RENDER_OUT_RGBA8 | PIH_RENDER_OUT_DEPTH | PIH_RENDER_CAM_DEVICE | PIH_RENDER_LIGHT_DEVICE | (h->fly ? 0 : PIH_RENDER_CAM_EE_POS);
+  if ((flags & ~known) != 0) { h->err = "pih_render_lit: unknown flag"; return -2; }
+  if (fmt == (PIH_RENDER_OUT_RGBA8 | PIH_RENDER_OUT_DEPTH)) { h->err = "pih_render_lit: PIH_RENDER_OUT_RGBA8 and PIH_RENDER_OUT_DEPTH exclude each other"; return -2; }
+  if ((flags & PIH_RENDER_CAM_EE) && (flags & PIH_RENDER_CAM_EE_POS)) { h->err = "pih_render_lit: PIH_RENDER_CAM_EE and PIH_RENDER_CAM_EE_POS exclude each other"; return -2; }
+  if (cam_on_device && !cam_ptr) { h->err = "pih_render_lit: PIH_RENDER_CAM_DEVICE needs a camera array (NULL = the preset is for a host camera)"; return -2; }
+  if (light_on_device && !light_ptr) { h->err = "pih_render_lit: PIH_RENDER_LIGHT_DEVICE needs a light array (NULL = PIH_LIGHT_DEFAULT is for a host light)"; return -2; }
+  if ((reinterpret_cast<uintptr_t>(out_dev) & 15) != 0) { h->err = "pih_render_lit: out_dev must be 16-byte aligned"; return -2; }
+  if (env_count > 65535) { h->err = "pih_render_lit: env_count > 65535 per call"; return -2; }
+  fly::FlyCam cam = {PIH_FLY_CAM_DEFAULT};
+  if (!h->fly) cam = fly::FlyCam{PIH_VIEW_CAM_WRIST};
+  if (!cam_on_device) {
+    if (cam_ptr) memcpy(cam.w, cam_ptr, sizeof cam.w);
+    else if (!h->fly) flags = (flags & ~PIH_RENDER_CAM_EE) | PIH_RENDER_CAM_EE_POS;      // the wrist preset, whatever frame flag was passed
+    static const char* const what[] = {nullptr, "eye == target (or not finite)", "up is zero or parallel to the view axis target - eye", "fov outside (0, 180) degrees",
+                                       "aspect <= 0", "near <= 0", "far <= near"};
+    // (a NaN or an infinity is looked for in the words' bits, as integers, as pih_render_view does: this code is built with -ffast-math)
+    static const char* const word[] = {"eye", "eye", "eye", "target", "target", "target", "up", "up", "up", "fov", "aspect", "near", "far"};
+    uint32_t bits[PIH_CAM_WORDS]; memcpy(bits, cam.w, sizeof bits);
+    for (int i = 0; i < PIH_CAM_WORDS; i++)
+      if ((bits[i] & 0x7f800000u) == 0x7f800000u) { h->err = std::string("pih_render_lit: degenerate camera: ") + word[i] + " is not finite"; return -2; }
+    const int code = fly::cam_degenerate(cam.w);
+    if (code != fly::CAM_OK) { h->err = std::string("pih_render_lit: degenerate camera: ") + what[code]; return -2; }
+  }
+  float light[PIH_LIGHT_WORDS] = PIH_LIGHT_DEFAULT;
+  if (!light_on_device) {
+    if (light_ptr) memcpy(light, light_ptr, sizeof light);
+    const char* what = nullptr;
+    if (lit_light_check(light, &what) != 0) { h->err = std::string("pih_render_lit: degenerate light: ") + what; return -2; }
+  }
+  PIH_ENTER(h);
+  int rows; const int strips = render_strips(height, env_count, &rows);
+  lit_launch(h->fly, fmt, dim3(strips, env_count), (hipStream_t)stream, h->state, out_dev, cam, cam_on_device ? cam_ptr : nullptr, light, light_on_device ? light_ptr : nullptr,
+             h->cfg.n_envs, h->P.object, env_begin, width, height, rows, flags);
   HIPCHK(h, hipGetLastError());
   return 0;
 }

@@ -9,8 +9,8 @@ constexpr int RENDER_THREADS = 256;
 #define PIH_COL_BG ((real)255)
 #define PIH_COL_TABLE ((real)153)
 // TinyRenderer defaults as driven by getCameraImage without light arguments [UNVERIFIED restatement; pybullet is absent: parity
-// unpinned]: light direction (-50, 30, 100) normalised (z-up world), ambient 0.6, diffuse 0.35; the specular term (0.05) and the
-// shadow map are not reproduced
+// unpinned]: light direction (-50, 30, 100) normalised (z-up world), ambient 0.6, diffuse 0.35.  The cameras that use these constants
+// stop there; the specular term (0.05), cast shadows and a caller-given light are pih_render_lit's (pih_lit.h)
 #define PIH_LIGHT_X ((real)-0.43193421279068006)
 #define PIH_LIGHT_Y ((real)0.25916052767440806)
 #define PIH_LIGHT_Z ((real)0.86386842558136012)

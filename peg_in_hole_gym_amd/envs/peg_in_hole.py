@@ -148,8 +148,10 @@ class RandomFly(MetaEnv):
             kw["dt"] = float(args[1])
         return kw
 
-    def render(self, mode="rgb_array", camera=None, ee_frame=False):
+    def render(self, mode="rgb_array", camera=None, ee_frame=False, light=None):
         """[300,300,4] = depth, r, g, b (shaded) like PegInHole.render, from `camera` (13 numbers: eye, target, up, fov, aspect, near,
-        far; None = CAMERA) in the env-local frame, or with ee_frame=True in the UR5's ee_link frame (eye-in-hand)"""
-        img = self._backend.render(300, 300, shaded=True, camera=camera, ee_frame=ee_frame)
+        far; None = CAMERA) in the env-local frame, or with ee_frame=True in the UR5's ee_link frame (eye-in-hand).  light: None, or what
+        PihVecEnv.render takes ("default", 11 numbers): the image under that light, with a specular term and cast shadows"""
+        kw = {} if light is None else {"light": light}
+        img = self._backend.render(300, 300, shaded=True, camera=camera, ee_frame=ee_frame, **kw)
         return (img.detach().cpu().numpy() if hasattr(img, "detach") else np.asarray(img))[0].astype(np.float64)

@@ -25,6 +25,19 @@ def tracking_cameras(opos, eye, up=(0.0, 0.0, 1.0), fov=60.0, aspect=1.0, near=0
     return cam
 
 
+def random_lights(n, device, generator=None, elevation=(20.0, 80.0)):
+    """float32 [n, 11] on `device`: _lib.LIGHT_DEFAULT with a unit direction of uniformly drawn azimuth and elevation (degrees) per row.  Pure
+    torch on the device."""
+    lo, hi = float(elevation[0]), float(elevation[1])
+    if not (-90.0 <= lo <= hi <= 90.0):
+        raise ValueError("random_lights: elevation must be a range within [-90, 90] degrees, got %r" % (elevation,))
+    u = torch.rand(n, 2, device=device, generator=generator, dtype=torch.float32)
+    az = u[:, 0] * (2.0 * np.pi); el = torch.deg2rad(lo + (hi - lo) * u[:, 1])
+    light = torch.tensor(_lib.LIGHT_DEFAULT, dtype=torch.float32, device=device).repeat(n, 1)
+    light[:, 0] = torch.cos(el) * torch.cos(az); light[:, 1] = torch.cos(el) * torch.sin(az); light[:, 2] = torch.sin(el)
+    return light
+
+
 class PihVecEnv:
     """N independent worlds of one task on one MI355X.
 
@@ -226,6 +239,28 @@ class PihVecEnv:
             raise ValueError("%s: camera must have %d numbers (eye, target, up, fov, aspect, near, far), got %d" % (what, _lib.CAM_WORDS, len(vals)))
         return (C.c_float * _lib.CAM_WORDS)(*vals), 0
 
+    def _light_arg(self, what, light, count):
+        """light argument of render / render_view (never None) -> (ctypes argument, flag): "default" -> (None, 0) = _lib.LIGHT_DEFAULT;
+        11 numbers -> a host array; [count, 11] -> the device address of a float32 tensor on this handle's device (used in place, or
+        converted and moved there; never read back) with RENDER_LIGHT_DEVICE"""
+        if isinstance(light, str):
+            if light != "default":
+                raise ValueError("%s: light must be None, \"default\", %d numbers or a [count, %d] array, got %r" % (what, _lib.LIGHT_WORDS, _lib.LIGHT_WORDS, light))
+            return None, 0
+        if (light.ndim if hasattr(light, "ndim") else np.ndim(light)) >= 2:
+            if torch.is_tensor(light):
+                light = light.to(device=self.device, dtype=torch.float32).contiguous()
+            else:
+                light = torch.as_tensor(np.asarray(light, dtype=np.float32)).to(self.device).contiguous()
+            if tuple(light.shape) != (count, _lib.LIGHT_WORDS):
+                raise ValueError("%s: per-env lights must have shape [%d, %d] (one row per env of the call), got %s" % (what, count, _lib.LIGHT_WORDS, tuple(light.shape)))
+            self._light_keep = light         # (lives until the next call: the launch is asynchronous)
+            return C.c_void_p(light.data_ptr()), _lib.RENDER_LIGHT_DEVICE
+        vals = [float(x) for x in light]
+        if len(vals) != _lib.LIGHT_WORDS:
+            raise ValueError("%s: light must have %d numbers (direction xyz, colour rgb, ambient, diffuse, specular, shininess, shadow factor), got %d" % (what, _lib.LIGHT_WORDS, len(vals)))
+        return (C.c_float * _lib.LIGHT_WORDS)(*vals), 0
+
     def _out_arg(self, what, out, fmt, count, height, width):
         """output tensor of render / render_view for format `fmt` -> (tensor, format flag)"""
         fmt_flag, dtype, tail = self._RENDER_FMT[fmt]
@@ -236,7 +271,7 @@ class PihVecEnv:
             raise ValueError("%s: out must be a contiguous %s tensor of shape %s on %s for fmt=%r" % (what, dtype, shape, self.device, fmt))
         return out, fmt_flag
 
-    def render(self, width=300, height=300, env_begin=0, env_count=None, out=None, shaded=False, camera=None, ee_frame=False, fmt="float4"):
+    def render(self, width=300, height=300, env_begin=0, env_count=None, out=None, shaded=False, camera=None, ee_frame=False, fmt="float4", light=None):
         """Camera image of a block of envs at the current state (analytic ray caster): float32 [count, height, width, 4] =
         (depth buffer, r, g, b), RGB on the 0..255 scale, flat per object or (shaded=True) times ambient + diffuse of TinyRenderer's
         default light.
@@ -254,9 +289,16 @@ class PihVecEnv:
               "rgba8"   uint8   [count, height, width, 4]   (r, g, b, seg): the colours rounded half up to bytes; seg = link index 0..5,
                                                             _lib.SEG_OBJECT, _lib.SEG_TABLE or _lib.SEG_NONE
               "depth"   float32 [count, height, width]      the depth buffer alone
-            out: for "rgba8" / "depth" it must be a contiguous tensor of that dtype and shape on this handle's device (ValueError)."""
+            out: for "rgba8" / "depth" it must be a contiguous tensor of that dtype and shape on this handle's device (ValueError).
+            light: None = the calls above.  Anything else draws the image under a caller-given light, with a specular term and cast
+            shadows (pih_render_lit, include/pih_render_light.h states the model; always shaded): "default" = _lib.LIGHT_DEFAULT; 11 numbers
+            (direction towards the light in the env-local frame, colour rgb, ambient, diffuse, specular, shininess, shadow factor: 1 = no
+            shadows), one light for all envs; shape [count, 11]: one light per env of the call in device memory (random_lights()), tested by
+            the kernel: an env whose row is degenerate gets the background.  Fewer or more than 11 numbers: ValueError."""
         count = self.n - env_begin if env_count is None else env_count
         fly = self.task_id == _lib.TASK_RANDOM_FLY
+        if light is not None and not fly:
+            raise ValueError("render: the peg-in-hole wrist camera of render() takes no light; render_view(light=...) does (camera=None is the same camera)")
         if not fly and (camera is not None or ee_frame):
             raise ValueError("render: the peg-in-hole task has a fixed wrist camera; camera / ee_frame belong to the random-fly task")
         if fmt not in self._RENDER_FMT:
@@ -265,6 +307,12 @@ class PihVecEnv:
             raise ValueError("render: the peg-in-hole wrist camera has the one format 'float4'; 'rgba8' / 'depth' belong to the random-fly task")
         cam, cam_flag = self._camera_arg("render", camera, count)
         out, fmt_flag = self._out_arg("render", out, fmt, count, height, width)
+        if light is not None:
+            lgt, light_flag = self._light_arg("render", light, count)
+            flags = _lib.RENDER_SHADED | (_lib.RENDER_CAM_EE if ee_frame else 0) | fmt_flag | cam_flag | light_flag
+            with torch.cuda.device(self.device):
+                self._chk(self.L.pih_render_lit(self.h, out.data_ptr(), cam, lgt, width, height, env_begin, count, flags, self._stream()), "pih_render_lit")
+            return out
         with torch.cuda.device(self.device):
             if fly:
                 flags = (_lib.RENDER_SHADED if shaded else 0) | (_lib.RENDER_CAM_EE if ee_frame else 0) | fmt_flag | cam_flag
@@ -275,7 +323,7 @@ class PihVecEnv:
 
     _VIEW_FRAME = {"env": 0, "ee": _lib.RENDER_CAM_EE, "ee_pos": _lib.RENDER_CAM_EE_POS}
 
-    def render_view(self, width=300, height=300, env_begin=0, env_count=None, out=None, shaded=False, camera=None, frame="env", fmt="float4"):
+    def render_view(self, width=300, height=300, env_begin=0, env_count=None, out=None, shaded=False, camera=None, frame="env", fmt="float4", light=None):
         """peg-in-hole from any viewpoint (pih_render_view): the scene of render() -- table, pipe, hole, finger pads -- plus a stand-in
         arm (one capsule per link, the hand's spheres), at the current state; nothing of the state changes.
         camera = 13 numbers as in render() of the random-fly task, one camera for all envs of the call; None = the wrist preset
@@ -288,7 +336,9 @@ class PihVecEnv:
             "ee_pos" = eye and target offset by the grasp-target's position, axes env-local: it follows the hand and does not turn.
         fmt: "float4" float32 [count, height, width, 4] (depth buffer, r, g, b); "rgba8" uint8 [count, height, width, 4] (r, g, b, seg),
             seg = arm link 0..6 (the hand is 6), fingers 7 and 8, _lib.VIEW_SEG_HOLE, _lib.VIEW_SEG_TABLE, _lib.VIEW_SEG_PIPE0 + pipe
-            capsule 0..23, _lib.SEG_NONE; "depth" float32 [count, height, width].  out: as in render()."""
+            capsule 0..23, _lib.SEG_NONE; "depth" float32 [count, height, width].  out: as in render().
+        light: as in render(): None = pih_render_view; "default", 11 numbers or [count, 11] = the image under that light, with a specular
+            term and the shadows of arm, hand, pipe and hole (pih_render_lit; always shaded)."""
         count = self.n - env_begin if env_count is None else env_count
         if self.task_id != _lib.TASK_PEG_IN_HOLE:
             raise ValueError("render_view: this camera belongs to the peg-in-hole task (random-fly: render(camera=...))")
@@ -299,6 +349,11 @@ class PihVecEnv:
         cam, cam_flag = self._camera_arg("render_view", camera, count)
         out, fmt_flag = self._out_arg("render_view", out, fmt, count, height, width)
         flags = (_lib.RENDER_SHADED if shaded else 0) | self._VIEW_FRAME[frame] | fmt_flag | cam_flag
+        if light is not None:
+            lgt, light_flag = self._light_arg("render_view", light, count)
+            with torch.cuda.device(self.device):
+                self._chk(self.L.pih_render_lit(self.h, out.data_ptr(), cam, lgt, width, height, env_begin, count, flags | _lib.RENDER_SHADED | light_flag, self._stream()), "pih_render_lit")
+            return out
         with torch.cuda.device(self.device):
             self._chk(self.L.pih_render_view(self.h, out.data_ptr(), cam, width, height, env_begin, count, flags, self._stream()), "pih_render_view")
         return out
@@ -309,6 +364,12 @@ class PihVecEnv:
         if self.task_id != _lib.TASK_RANDOM_FLY:
             raise ValueError("tracking_cameras: the object to follow belongs to the random-fly task")
         return tracking_cameras(self.state()[:, _lib.F_OPOS:_lib.F_OPOS + 3], eye, up, fov, aspect, near, far)
+
+    def random_lights(self, generator=None, elevation=(20.0, 80.0)):
+        """float32 [n, 11] device tensor of _lib.LIGHT_DEFAULT lights whose direction is drawn per env: azimuth uniform in [0, 360), elevation
+        uniform in `elevation` (degrees above the table).  Built on the device, no host round trip -- feed it to render(light=...) /
+        render_view(light=...); the companion of tracking_cameras.  generator: a torch.Generator on this handle's device, or None."""
+        return random_lights(self.n, self.device, generator, elevation)
 
     def grasp_labels(self, size=300, env_begin=0, env_count=None):
         """Label images + [x, y, angle_deg, width, length] of random_grasp (envs/peg_in_hole.py:72-99,116):

@@ -1,0 +1,198 @@
+"""Lit camera images on the GPU: pih_render_lit / PihVecEnv.render(light=...) / render_view(light=...) against the numpy fp64 reference of
+tests/test_render_lit.py -- same scenes, cameras, sizes, lights and rules: the class share of the task's module, the shadow state equal on
+every decided pixel, the undecided cap (on the reference), and that module's colour bar: the project's bar for shaded colours (p99 < 0.05,
+median < 1e-3 grey levels) times 1 + specular shininess / diffuse of the light.  The fp32 host build meets that bar with p99 <= 2.8e-3 and
+median <= 4.8e-6 (light `low` / `shiny`); it is a bar on percentiles, and the GPU takes it as it stands."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from peg_in_hole_gym_amd import _lib
+
+
+@pytest.fixture(scope="module")
+def torch_mod():
+    import torch
+    assert torch.cuda.is_available(), "GPU tests need a ROCm device"
+    return torch
+
+
+def _peg(n, **kw):
+    from peg_in_hole_gym_amd.vec_env import PihVecEnv
+    return PihVecEnv(n, **kw)
+
+
+def _fly(n, **kw):
+    from tests import test_gpu_fly_render as G
+    return G._gpu(n, **kw)
+
+
+def _render(g, case, light, fmt="float4", **kw):
+    """the handle's lit image of all its envs for a case's camera and size"""
+    W, H = case["size"]
+    if case["task"] == "peg":
+        return g.render_view(W, H, camera=case["cam"], frame=case["frame"], fmt=fmt, light=light, **kw)
+    return g.render(W, H, camera=case["cam"], ee_frame=case["frame"] == "ee", fmt=fmt, light=light, **kw)
+
+
+def _parity(T, g, cases):
+    """every case x the four lights under the rules of T.check_image; the images of all envs are rendered once per (camera, size, light)"""
+    images = {}
+
+    def gpu(case, lw):
+        key = (tuple(case["cam"]), case["size"], tuple(lw))
+        if key not in images:
+            images[key] = (_render(g, case, lw).cpu().numpy(), _render(g, case, lw, fmt="rgba8").cpu().numpy()[..., 3])
+        img, seg = images[key]
+        return img[case["env"]], seg[case["env"]]
+
+    for ln in T.LIGHT_NAMES:
+        light = T.LIGHTS[ln]; errs = []; worst = 0.0; und = 0.0
+        for key, case in cases.items():
+            ref = T.case_reference(case, light)
+            und = max(und, (~ref["decided"]).mean())
+            assert (~ref["decided"]).mean() <= T.UNDECIDED_CAP, (key, ln)
+            try:
+                err, share = T.check_image(ref, case["task"], lambda lw: gpu(case, lw), light, exact=False)
+            except AssertionError as ex:
+                raise AssertionError("%s, light %s: %s" % (key, ln, ex)) from None
+            errs.append(err); worst = max(worst, share)
+        errs = np.concatenate(errs); f = T.colour_factor(light)
+        print("light %-8s: colour error max %.3e, p99 %.3e (bound %.3e), median %.3e (bound %.3e); worst class share %.4f; largest undecided share %.4f"
+              % (ln, errs.max(), np.percentile(errs, 99), T.SHADED_P99 * f, np.median(errs), T.SHADED_MEDIAN * f, worst, und))
+        assert np.percentile(errs, 99) < T.SHADED_P99 * f and np.median(errs) < T.SHADED_MEDIAN * f
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ["wrist", "overview", "hole close-up", "eye-in-hand", "horizon"])
+def test_parity_peg_in_hole(torch_mod, oracle_mod, name):
+    """the six state slots (eight envs: T.PEG_STATE_FOR) x the three sizes x the four lights under one camera, float4 plus the seg of rgba8,
+    every env against the reference fed with the handle's own state()"""
+    from tests import test_render_lit as T
+    g = _peg(8)
+    g.set_state(torch_mod.tensor(T.make_peg_states(oracle_mod)))
+    _parity(T, g, T.peg_cases(oracle_mod, g.state().cpu().numpy(), (name,)))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ["overview", "close-up", "horizon", "eye-in-hand"])
+@pytest.mark.parametrize("obj", [0, 1])
+def test_parity_random_fly(torch_mod, oracle_mod, obj, name):
+    """six envs (the scenes of tests/test_gpu_fly_render.py) x the three sizes x the four lights under one camera"""
+    from tests import test_fly_render as FR
+    from tests import test_gpu_fly_render as G
+    from tests import test_render_lit as T
+    g = _fly(6, object_id=obj)
+    g.set_state(torch_mod.tensor(FR.make_states(oracle_mod, obj, 6, seed=G.SCENE_SEED[(obj, name)], eye_in_hand=name == "eye-in-hand")))
+    _parity(T, g, T.fly_cases(oracle_mod, obj, name, g.state().cpu().numpy()))
+
+
+def _handles(torch_mod, O):
+    """one handle per task with the scenes of the parity tests, and a case (camera, size) for each"""
+    from tests import test_fly_render as FR
+    from tests import test_gpu_fly_render as G
+    from tests import test_render_lit as T
+    peg = _peg(8); peg.set_state(torch_mod.tensor(T.make_peg_states(O)))
+    fly = _fly(6, object_id=0); fly.set_state(torch_mod.tensor(FR.make_states(O, 0, 6, seed=G.SCENE_SEED[(0, "overview")])))
+    pc = T.peg_cases(O, peg.state().cpu().numpy(), ("overview", "wrist", "eye-in-hand"))
+    fc = T.fly_cases(O, 0, "overview", fly.state().cpu().numpy()[:1])
+    fe = T.fly_cases(O, 0, "eye-in-hand", fly.state().cpu().numpy()[:1])
+    return [(peg, pc[("peg", n, (97, 61), 0)]) for n in ("overview", "wrist", "eye-in-hand")] + [(fly, fc[("fly0", "overview", (97, 61), 0)]), (fly, fe[("fly0", "eye-in-hand", (97, 61), 0)])]
+
+
+@pytest.mark.gpu
+def test_switch_off_identity(torch_mod, oracle_mod):
+    """default direction, specular 0, shadow factor 1: the depth channel is bit-equal to the shaded image of render_view / render, colours
+    within 1e-3 grey levels (ten times 255 x a few fp32 roundings: the kernel normalises the direction the unlit kernels hold as constants);
+    the seg bytes and the depth-only image are the unlit call's bit for bit, under any light"""
+    from tests import test_render_lit as T
+    off = list(_lib.LIGHT_DEFAULT); off[T.L_SPEC] = 0.0; off[T.L_SHADOW] = 1.0
+    hs = _handles(torch_mod, oracle_mod)
+    for g, case in hs:
+        for (W, H) in T.SIZES:
+            c = dict(case, size=(W, H))
+            lit = _render(g, c, off).cpu().numpy()
+            kw = dict(frame=case["frame"]) if case["task"] == "peg" else dict(ee_frame=case["frame"] == "ee")
+            f = g.render_view if case["task"] == "peg" else g.render
+            shaded = f(W, H, camera=case["cam"], shaded=True, **kw).cpu().numpy()
+            assert np.array_equal(lit[..., 0], shaded[..., 0]), (case["name"], W, H)
+            d = np.abs(lit[..., 1:].astype(np.float64) - shaded[..., 1:])
+            print("%s %s %dx%d: max colour difference to the shaded image %.3e" % (case["task"], case["name"], W, H, d.max()))
+            assert d.max() <= 1e-3
+            for light in ("default", T.LIGHTS["low"]):
+                assert np.array_equal(_render(g, c, light, fmt="rgba8").cpu().numpy()[..., 3], f(W, H, camera=case["cam"], fmt="rgba8", **kw).cpu().numpy()[..., 3])
+                assert np.array_equal(_render(g, c, light, fmt="depth").cpu().numpy(), shaded[..., 0])
+    # no camera: the task's preset
+    peg, fly = hs[0][0], hs[3][0]
+    assert np.array_equal(peg.render_view(64, 64, light="default").cpu().numpy(), peg.render_view(64, 64, camera=_lib.VIEW_CAM_WRIST, frame="ee_pos", light=list(_lib.LIGHT_DEFAULT)).cpu().numpy())
+    assert np.array_equal(fly.render(64, 64, light="default").cpu().numpy(), fly.render(64, 64, camera=_lib.FLY_CAM_DEFAULT, light=list(_lib.LIGHT_DEFAULT)).cpu().numpy())
+
+
+@pytest.mark.gpu
+def test_per_env_device_lights(torch_mod, oracle_mod):
+    """six different rows == six single-light calls bit for bit, in float4 and rgba8; a [3, 11] tensor with env_begin = 2 == the matching
+    slices; a degenerate row and one with a NaN give their envs the background and the call returns 0; random_lights"""
+    from tests import test_render_lit as T
+    rng = np.random.default_rng(7)
+    for g, case in _handles(torch_mod, oracle_mod)[::3]:
+        n = 6
+        rows = np.array([T.LIGHTS["default"], T.LIGHTS["low"], T.LIGHTS["below"], T.LIGHTS["shiny"], T.LIGHTS["low"], T.LIGHTS["shiny"]], dtype=np.float32)
+        rows[4, :3] = [-0.3, 0.8, 0.4]; rows[5, 10] = 0.3
+        for fmt in ("float4", "rgba8"):
+            per_env = _render(g, case, torch_mod.tensor(rows, device=g.device), fmt=fmt, env_count=n).cpu().numpy()
+            for e in range(n):
+                single = _render(g, case, [float(x) for x in rows[e]], fmt=fmt, env_begin=e, env_count=1).cpu().numpy()
+                assert np.array_equal(per_env[e], single[0]), (case["task"], fmt, e)
+            part = _render(g, case, rows[2:5], fmt=fmt, env_begin=2, env_count=3).cpu().numpy()          # (a numpy array is moved to the device)
+            assert np.array_equal(part, per_env[2:5])
+        bad = rows.copy(); bad[1, 9] = 0.0; bad[3, 4] = np.nan          # (shininess 0; a NaN colour)
+        img = _render(g, case, bad, env_count=n).cpu().numpy(); rgba = _render(g, case, bad, fmt="rgba8", env_count=n).cpu().numpy(); dep = _render(g, case, bad, fmt="depth", env_count=n).cpu().numpy()
+        good = _render(g, case, rows, env_count=n).cpu().numpy()
+        for e in range(n):
+            if e in (1, 3):
+                assert (img[e, ..., 0] == 1).all() and (img[e, ..., 1:] == 255).all() and (dep[e] == 1).all(), (case["task"], e)
+                assert (rgba[e, ..., :3] == 255).all() and (rgba[e, ..., 3] == _lib.SEG_NONE).all(), (case["task"], e)
+            else:
+                assert np.array_equal(img[e], good[e]) and (dep[e] < 1).any()
+        lights = g.random_lights(generator=torch_mod.Generator(device=g.device).manual_seed(5))
+        assert tuple(lights.shape) == (g.n, 11) and lights.dtype == torch_mod.float32 and lights.device.type == "cuda"
+        lw = lights.cpu().numpy()
+        assert np.allclose(np.linalg.norm(lw[:, :3], axis=1), 1, atol=1e-6) and (lw[:, 2] >= np.sin(np.radians(20)) - 1e-6).all() and (lw[:, 2] <= np.sin(np.radians(80)) + 1e-6).all()
+        assert np.array_equal(lw[:, 3:], np.tile(np.array(_lib.LIGHT_DEFAULT[3:], dtype=np.float32), (g.n, 1)))
+        imgs = _render(g, case, lights).cpu().numpy()
+        assert (imgs[..., 0] < 1).any() and all((imgs[e] != imgs[0]).any() for e in range(1, g.n))
+
+
+@pytest.mark.gpu
+def test_errors(torch_mod, oracle_mod):
+    """each degenerate host light returns -2 and the message names the field; both formats, an unknown bit, a misaligned pointer and a NULL
+    device light return -2; the old entry points still refuse bit 64"""
+    from tests import test_render_lit as T
+    for g, case in _handles(torch_mod, oracle_mod)[::3]:
+        L, h = g.L, g.h
+        W, H = 40, 30
+        out = torch_mod.empty(g.n * H * W * 4 + 4, dtype=torch_mod.float32, device=g.device)
+        light = (C.c_float * 11)(*_lib.LIGHT_DEFAULT)
+        call = lambda ptr, lgt, flags, count=g.n: L.pih_render_lit(h, ptr, None, lgt, W, H, 0, count, flags, None)
+        assert call(out.data_ptr(), light, 0) == 0 and call(out.data_ptr(), None, _lib.RENDER_SHADED) == 0
+        for field, _, words in T.BAD_LIGHTS:
+            assert call(out.data_ptr(), (C.c_float * 11)(*words), 0) == -2
+            msg = L.pih_last_error(h).decode()
+            assert "degenerate light: " + field in msg, (field, msg)
+            with pytest.raises(_lib.PihError):
+                _render(g, dict(case, size=(W, H)), words)
+        assert call(out.data_ptr(), light, _lib.RENDER_OUT_RGBA8 | _lib.RENDER_OUT_DEPTH) == -2 and "exclude each other" in L.pih_last_error(h).decode()
+        assert call(out.data_ptr(), light, 128) == -2 and "unknown flag" in L.pih_last_error(h).decode()
+        assert call(out.data_ptr() + 4, light, 0) == -2 and "aligned" in L.pih_last_error(h).decode()
+        assert call(out.data_ptr(), None, _lib.RENDER_LIGHT_DEVICE) == -2 and "PIH_RENDER_LIGHT_DEVICE" in L.pih_last_error(h).decode()
+        assert call(out.data_ptr(), light, 0, count=g.n + 1) == -2
+        cam = list(case["cam"]); cam[9] = float("nan")          # a host camera with a NaN is refused as by the unlit calls
+        assert L.pih_render_lit(h, out.data_ptr(), (C.c_float * 13)(*cam), light, W, H, 0, g.n, 0, None) == -2 and "degenerate camera" in L.pih_last_error(h).decode()
+        if case["task"] == "peg":
+            assert call(out.data_ptr(), light, _lib.RENDER_CAM_EE | _lib.RENDER_CAM_EE_POS) == -2
+            assert L.pih_render_view(h, out.data_ptr(), None, W, H, 0, g.n, _lib.RENDER_LIGHT_DEVICE, None) == -2
+        else:
+            assert call(out.data_ptr(), light, _lib.RENDER_CAM_EE_POS) == -2          # the fly camera has no such frame
+            assert L.pih_render_cam(h, out.data_ptr(), None, W, H, 0, g.n, _lib.RENDER_LIGHT_DEVICE, None) == -2
+        torch_mod.cuda.synchronize()

@@ -9,7 +9,12 @@ usage: render_bench.py [n]
        render_bench.py --task peg-view [--n N] --width W --height H [--repeats K]
            the free camera of the peg-in-hole task (pih_render_view): the wrist preset in float4, rgba8 and depth, the overview camera in
            float4 and rgba8, per-env cameras (the overview in every row) in rgba8, alternating with the unchanged pih_render float4 of
-           the same handle as the yardstick of the same run; ms, Mpixel/s and GB/s written for each case"""
+           the same handle as the yardstick of the same run; ms, Mpixel/s and GB/s written for each case
+       render_bench.py --task lit [--width W --height H --repeats K]
+           the lit images (pih_render_lit) at 1024 and 4096 envs: for each of three shaded yardsticks of the same run -- pih_render_view
+           overview, pih_render_view wrist, pih_render_cam default -- the lit call with specular 0 and shadow factor 1 (no shadow ray, no
+           highlight), with PIH_LIGHT_DEFAULT but specular 0 (the shadow ray alone), with PIH_LIGHT_DEFAULT, and with PIH_LIGHT_DEFAULT in every row of per-env device lights, in float4 and rgba8; the
+           last lines state the cost of the shadow ray + specular term as ratios to the yardstick"""
 import sys, os, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -95,11 +100,59 @@ def peg_view_bench():
               % (name, n, W, H, med, v[0], v[-1], K, n * W * H / med / 1e3, bpp, n * W * H * bpp / med / 1e6, med / ref))
 
 
+def lit_bench():
+    W, H, K = _arg("--width", 300), _arg("--height", 300), max(5, _arg("--repeats", 5))
+    off = list(_lib.LIGHT_DEFAULT); off[8] = 0.0; off[10] = 1.0          # specular 0, shadow factor 1
+    matt = list(_lib.LIGHT_DEFAULT); matt[8] = 0.0                        # specular 0: the shadow ray alone
+    for n in (1024, 4096):
+        peg = PihVecEnv(n, mode=1, dv=0.05)
+        peg.step_n(540)                          # grippers hovering above their pipes, as in the default timing
+        fly = PihVecEnv(n, task_id=1, max_episode_steps=480, contact_margin=0.02, dt=1.0 / 120.0, seed=1)
+        act = torch.zeros(n, 6, device="cuda"); act[:, 0] = 0.4; act[:, 2] = 0.5
+        fly.step_n(20, act)                      # objects in flight, arms off their rest pose
+        out = torch.empty(n, H, W, 4, device="cuda")
+        out8 = torch.empty(n, H, W, 4, dtype=torch.uint8, device="cuda")
+        lights = torch.tensor([_lib.LIGHT_DEFAULT] * n, device="cuda")      # per-env lights in device memory: the default in every row, so the pixels are the same work
+        scenes = (("view overview", lambda **kw: peg.render_view(W, H, camera=_lib.VIEW_CAM_OVERVIEW, **kw)),
+                  ("view wrist", lambda **kw: peg.render_view(W, H, **kw)),
+                  ("fly default", lambda **kw: fly.render(W, H, **kw)))
+        cases = []
+        for sname, f in scenes:
+            for fmt, o, bpp in (("float4", out, 16), ("rgba8", out8, 4)):
+                cases.append((sname, fmt, "shaded (yardstick)", bpp, lambda f=f, fmt=fmt, o=o: f(out=o, fmt=fmt, shaded=True)))
+                cases.append((sname, fmt, "lit, specular 0, shadow 1", bpp, lambda f=f, fmt=fmt, o=o: f(out=o, fmt=fmt, light=off)))
+                cases.append((sname, fmt, "lit, default but specular 0", bpp, lambda f=f, fmt=fmt, o=o: f(out=o, fmt=fmt, light=matt)))
+                cases.append((sname, fmt, "lit, default light", bpp, lambda f=f, fmt=fmt, o=o: f(out=o, fmt=fmt, light="default")))
+                cases.append((sname, fmt, "lit, default, per-env lights", bpp, lambda f=f, fmt=fmt, o=o: f(out=o, fmt=fmt, light=lights)))
+        for c in cases:                          # warm-up
+            for _ in range(2):
+                c[4]()
+        torch.cuda.synchronize()
+        ms = {c[:3]: [] for c in cases}
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+        for _ in range(K):                       # alternating: every repeat times each case once
+            for c in cases:
+                ev[0].record(); c[4](); ev[1].record(); ev[1].synchronize()
+                ms[c[:3]].append(ev[0].elapsed_time(ev[1]))
+        med = {k: sorted(v)[len(v) // 2] for k, v in ms.items()}
+        for sname, fmt, what, bpp, _ in cases:
+            v = sorted(ms[(sname, fmt, what)]); m = med[(sname, fmt, what)]
+            print("%-14s %-6s %-30s %d envs x %dx%d: median %.3f ms (min %.3f, max %.3f, %d repeats) = %.0f Mpixel/s, %.1f GB/s written, %.2f x the yardstick's time"
+                  % (sname, fmt, what, n, W, H, m, v[0], v[-1], K, n * W * H / m / 1e3, n * W * H * bpp / m / 1e6, m / med[(sname, fmt, "shaded (yardstick)")]))
+        for sname, _ in scenes:
+            for fmt in ("float4", "rgba8"):
+                y, a, b = med[(sname, fmt, "shaded (yardstick)")], med[(sname, fmt, "lit, specular 0, shadow 1")], med[(sname, fmt, "lit, default light")]
+                m = med[(sname, fmt, "lit, default but specular 0")]
+                print("%-14s %-6s %d envs: lit kernel without shadow ray and highlight %.2f x the shaded yardstick; the shadow ray adds %.2f x, the specular term %.2f x the yardstick"
+                      % (sname, fmt, n, a / y, (m - a) / y, (b - m) / y))
+        del peg, fly
+
+
 if "--task" in sys.argv:
     task = _arg("--task", "")
-    if task not in ("random-fly", "peg-view"):
-        sys.exit("render_bench.py: --task takes random-fly or peg-view (the peg-in-hole wrist camera timing is the default: render_bench.py [n])")
-    fly_bench() if task == "random-fly" else peg_view_bench()
+    if task not in ("random-fly", "peg-view", "lit"):
+        sys.exit("render_bench.py: --task takes random-fly, peg-view or lit (the peg-in-hole wrist camera timing is the default: render_bench.py [n])")
+    {"random-fly": fly_bench, "peg-view": peg_view_bench, "lit": lit_bench}[task]()
     sys.exit(0)
 
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 1024
