@@ -86,8 +86,10 @@ enum {
   PIH_S_ATTACH_QZ = 113,   /* scripted mode: z component of the grasped link's quaternion when the state machine entered state 4 (the
                               reference passes it as targetOrn[2] into childFrameOrientation, envs/peg_in_hole.py:101) */
   PIH_S_SOLVER = 114,      /* which PGS variant solved the last step: 0 DOF space, 1 / 2 row space without / with the limit rows of arm joints
-                              0..6, 4 row space re-run with all limit rows after an arm motor row clamped, 5 row space with two rows per lane
-                              (11..32 contacts) */
+                              0..6, 4 row space re-run with all limit rows and every motor row clamped, after an arm motor row clamped or the
+                              verification of the residual-form motor rows failed (a pipe or arm motor multiplier came within 2^-7 of its
+                              bound, or turned non-finite), 5 row space with two rows per lane (11..32 contacts).  Variants 1 and 2 run the
+                              pipe motor rows (1: also arm motor rows 0..6) unclamped in residual form, unless schedule + 64 */
   PIH_S_INVALID = 112,     /* 1: the state became non-finite while auto_reset = 0; the env was re-initialised, marked done and stays frozen until pih_reset */
   PIH_S_CACHE_N = 128, PIH_S_CACHE_KEY = 129, PIH_S_CACHE_LAMBDA = 129 + 48
 };
@@ -141,7 +143,10 @@ typedef struct pih_config {
                                  wavefront, the PGS sweep split over the quad; fused with the IK controller wavefronts while all workgroups
                                  are resident together, n <= 13 104 on 256 CUs); +64 (random-fly): every joint-limit row in every sweep
                                  (default: limit rows of joints farther than 0.25 rad from their limits are skipped and verified -- same
-                                 results bit for bit) (measurement switches).
+                                 results bit for bit); +64 (peg-in-hole): no residual-form motor rows in the one-row-per-lane PGS, every
+                                 motor row is clamped in every sweep (default: the pipe motor rows and, without limit rows, arm motor rows
+                                 0..6 run unclamped and are verified after the solve -- the same solve in another rounding, a failed
+                                 verification re-runs it clamped: PIH_S_SOLVER = 4) (measurement switches).
                                  pih_create rejects every other value (-2), among them the retired 2 / 3 and + 16 */
   int32_t enable_arm_collision; /* arm collision spheres (pih_model.h PIH_ARM_SPH_*): bit 0 vs the table plane, bit 1 vs the pipe (hand /
                                    flange / wrist spheres against the pipe's sample spheres); default 3 */

@@ -459,8 +459,9 @@ PIH_HD int pgs_rows(Wave& w, Shared& sh, const Params& P) {
   // motors and the contacts need no wave-uniform registers.  The arm joints keep their uniform chain (motor, lower, upper limit
   // share one lane): their lanes hold z = -dinv (J du).
   w.sync();
-  real di = 0, rhs = 0, thr = PIH_BIG, lbv = 0, ubv = 0, cmu = 0, cfl = 0, lam0 = 0;
-  if (lane < 9) di = sh.mrec[lane][MR_DINV];
+  real di = 0, rhs = 0, thr = PIH_BIG, lbv = 0, ubv = 0, cmu = 0, cfl = 0, lam0 = 0, rhsa = 0;
+  // (thr / rhsa of lanes 0..6: read by the residual form of the arm motor rows only; the clamped arm blocks take both from the record)
+  if (lane < 9) { di = sh.mrec[lane][MR_DINV]; if (lane < 7) { thr = sh.mrec[lane][MR_THRESH]; rhsa = sh.mrec[lane][MR_RHS]; } }
   else if (lane < NMOT) { di = sh.mrec[lane][MR_DINV]; rhs = sh.mrec[lane][MR_RHS]; thr = sh.mrec[lane][MR_THRESH]; ubv = sh.mrec[lane][MR_IMP]; lbv = -ubv; }
   else {
     const int row = lane - NMOT, c = row / 3, k = row - 3 * c;
@@ -505,13 +506,46 @@ PIH_HD int pgs_rows(Wave& w, Shared& sh, const Params& P) {
   for (int j = 1; j < 7; j++) armlim = sh.mrec[j][MR_IMP] < armlim ? sh.mrec[j][MR_IMP] : armlim;
   if (lane < 9) sh.lrec[lane][LR_JWDINV] = sh.lrec[lane][LR_JW] * sh.mrec[lane][MR_DINV];          // (J W) dinv of the arm joint (1 up to rounding)
   w.sync();
+  // ---- residual rows.  A motor row whose clamp never acts takes  dl = z_g - lambda_g  in every update, so its lane carries the
+  // residual r = z - lambda instead of z: the step is the lane's own value (ONE v_readlane, no clamp, no subtraction), every lane adds
+  // Bn[g] * dl exactly as before -- for the other lanes r and z receive the same increment, the contact lanes keep holding z in the same
+  // register -- and only the row's own lane differs: its coefficient is Bn[g][g] - 1 = -dinv A[g][g], so r_g falls to about 0.  The
+  // multiplier is accumulated off the chain in the row's own lane (lam += [lane == g] dl: one v_fmac with an indicator register, where
+  // the clamped row spends one v_add on its wave-uniform lamr[g]).  A residual row is v_readlane, v_fmac, v_fmac: three instructions
+  // against the clamped row's five.  Inside a residual solve's iterations the 30 indicators are live and lamr[] is not -- it is filled
+  // once after the verification (23 v_readlane), because the tail reads the motor multipliers as wave-uniform values.  Such rows are
+  //   - the 23 pipe motor rows (PyBullet's load-time velocity motor: target 0, max impulse MR_IMP = 1), in both instantiations;
+  //   - the arm motor rows 0..6 where their limit rows are left out (FULL == false): r_j = rhs_j + za_j, rhs_j folded in once.
+  // That the clamp never acts is SPECULATED and VERIFIED: one v_max per iteration keeps the largest |lambda| every lane has held, and
+  // after the solve each residual lane compares it with its own bound (verify below); if any fails the whole solve is run again with
+  // the clamped rows and every arm limit row (PIH_S_SOLVER = 4), which is the arithmetic of the z form bit for bit.
+  // pih_config.schedule + 64 (P.nospec): no residual rows at all, every env takes the clamped rows (A/B switch).
+  real ind[NMOT];                            // [lane == g]: multiplier accumulation of residual row g (0..6: read by variant 1 only)
+  real bown = 0;                             // Bn[lane] of a pipe motor lane in the z form (what the fallback puts back)
+  const bool spec = __builtin_amdgcn_readfirstlane((int)P.nospec) == 0;
+  if (spec) {
+#pragma unroll
+    for (int g = 0; g < NMOT; g++) {
+      if (g == 7 || g == 8) { ind[g] = 0; continue; }
+      const bool own = lane == g;
+      ind[g] = own ? (real)1 : (real)0;
+      if (g >= 9) { bown = own ? Bn[g] : bown; Bn[g] -= ind[g]; }      // own lane: (1 - dinv A_gg) - 1; every other lane: - 0
+      __asm__ volatile("" : "+v"(ind[g]));     // a register, not a compare + select inside the loop
+    }
+  } else {
+#pragma unroll
+    for (int g = 0; g < NMOT; g++) ind[g] = 0;
+  }
   // ---- multipliers: arm rows wave-uniform in VGPRs, every other row in its own lane
-  real lam_a[9], lam_lo[9], lam_hi[9], lamr[NMOT];     // pipe motor rows: wave-uniform multipliers (lam[g] += step: one issue slot)
+  real lam_a[9], lam_lo[9], lam_hi[9], lamr[NMOT];     // clamped pipe motor rows: wave-uniform multipliers (lam[g] += step: one issue slot)
   real lam = 0, z = 0;
   int it = 0;
-  // commit one lane of a per-lane register: x[g] = y[g] (the lane mask is a compile-time constant in an SGPR pair)
-  auto solve = [&](auto FULLTAG) __attribute__((always_inline)) -> bool {     // returns true if an arm motor row clamped
+  // FULL: every arm limit row; RES: pipe motor rows (and, without FULL, arm motor rows 0..6) in residual form.
+  // Returns true if the solve has to be run again: an arm motor row clamped (!RES, !FULL) or the verification failed (RES).
+  auto solve = [&](auto FULLTAG, auto RESTAG) __attribute__((always_inline)) -> bool {
     constexpr bool FULL = decltype(FULLTAG)::value;
+    constexpr bool RES = decltype(RESTAG)::value;
+    constexpr bool RESARM = RES && !FULL;
 #pragma unroll
     for (int j = 0; j < 9; j++) { lam_a[j] = 0; lam_lo[j] = 0; lam_hi[j] = 0; }
 #pragma unroll
@@ -523,8 +557,10 @@ PIH_HD int pgs_rows(Wave& w, Shared& sh, const Params& P) {
       for (int c = 0; c < MERGED_CONTACTS; c++)
         if (c < nc) v += Bn[NMOT + 3 * c] * sh.r_lam[3 * c];
       z = rhs + v;                         // (Bn = [own] - dinv A: the sum is  [own normal row] lam0 - dinv (J du))
+      if (RESARM) z += rhsa;               // residual of arm motor rows 0..6 (lambda = 0)
     }
     real amax = 0;                           // largest |multiplier| any arm motor row 0..6 took during the solve (limit rows left out)
+    real wmax = 0;                           // RES: largest |lam| this lane has held after any iteration
     auto iterate = [&](auto CHECKTAG, auto WELDTAG) __attribute__((always_inline)) -> bool {
       constexpr bool CHECK = decltype(CHECKTAG)::value;     // evaluate the early-exit test in this iteration? (see pgs_iteration_loop)
       constexpr bool WELD = decltype(WELDTAG)::value;       // attach / weld rows present (scripted mode): see pgs_rows2
@@ -536,47 +572,66 @@ PIH_HD int pgs_rows(Wave& w, Shared& sh, const Params& P) {
       for (int k = 0; k < PF; k++) { pa4[k] = *reinterpret_cast<const real4*>(sh.mrec[k]); pl4[k] = *reinterpret_cast<const real4*>(sh.lrec[k]); }
       // the arm rows and the pipe motor rows do not see each other (A[arm row][pipe motor row] = 0): two accumulators, two chains
       real za = z, zp = z;
-      // The 9 arm joint blocks are spread evenly over the 23 pipe motor rows (block k in front of row 23 k / 9): a pipe row is
-      // med3, sub, <1 wait state>, v_readlane, <2 wait states>, fmac, and the instructions of an arm block are what fills those slots
-      // (with all arm blocks up front the last 14 pipe rows ran with three s_nop slots each).  The two chains commute exactly.
+      // The 9 arm joint blocks are spread evenly over the 23 pipe motor rows (block k in front of row 23 k / 9): a clamped pipe row is
+      // med3, sub, <1 wait state>, v_readlane, <2 wait states>, fmac, a residual one v_readlane, <2 wait states>, fmac, and the
+      // instructions of an arm block are what fills those slots (with all arm blocks up front the last 14 pipe rows ran with three
+      // s_nop slots each).  The two chains commute exactly.
 #pragma unroll
       for (int jp = 0; jp < PIH_OBJ_NJ; jp++) {
         const int j = (jp * 9 + PIH_OBJ_NJ - 1) / PIH_OBJ_NJ;         // the arm block in front of pipe row jp, if 23 j / 9 == jp
         if (j < 9 && (PIH_OBJ_NJ * j) / 9 == jp) {   // arm joint block: motor, lower limit, upper limit; y = dinv (J du) of the joint
-          const real4 ca = pa4[j % PF], cl = pl4[j % PF];
-          if (j + PF < 9) { pa4[j % PF] = *reinterpret_cast<const real4*>(sh.mrec[j + PF]); pl4[j % PF] = *reinterpret_cast<const real4*>(sh.lrec[j + PF]); }
-          const real rh = rec4<MR_RHS>(&ca), th = rec4<MR_THRESH>(&ca), lim = rec4<MR_IMP>(&ca);
-          const real lor = rec4<LR_LO>(&cl), hir = rec4<LR_HI>(&cl), wd = rec4<LR_JWDINV>(&cl);
-          real y = -rdlane(za, j);
-          real sum = lam_a[j] + (rh - y);
-          sum = med3_(sum, -lim, lim);
-          const real dl = sum - lam_a[j]; lam_a[j] = sum;
-          if (CHECK) busy |= __ballot(absr(dl) > th);
-          if (FULL || j >= 7) {
-            y += dl * wd;
-            real s2 = lam_lo[j] + (lor - y); s2 = max_(s2, (real)0);
-            const real d2 = s2 - lam_lo[j]; lam_lo[j] = s2;
-            if (CHECK) busy |= __ballot(absr(d2) > th);
-            y += d2 * wd;
-            real s3 = lam_hi[j] + (hir + y); s3 = max_(s3, (real)0);
-            const real d3 = s3 - lam_hi[j]; lam_hi[j] = s3;
-            if (CHECK) busy |= __ballot(absr(d3) > th);
-            za += Bn[j] * (dl + d2 - d3);
-          } else {
-            amax = max_(amax, absr(sum));                         // watched in EVERY iteration (one v_max): a multiplier may touch its bound and leave it again
+          if (RESARM && j < 7) {
+            // residual arm motor row: the step is the lane's own value (the record ring still turns: joints 7, 8 read their slots)
+            if (j + PF < 9) { pa4[j % PF] = *reinterpret_cast<const real4*>(sh.mrec[j + PF]); pl4[j % PF] = *reinterpret_cast<const real4*>(sh.lrec[j + PF]); }
+            const real dl = rdlane(za, j);
+            if (CHECK) busy |= __ballot(absr(za) > thr) & (1ull << j);
+            lam += ind[j] * dl;
             za += Bn[j] * dl;
+          } else {
+            const real4 ca = pa4[j % PF], cl = pl4[j % PF];
+            if (j + PF < 9) { pa4[j % PF] = *reinterpret_cast<const real4*>(sh.mrec[j + PF]); pl4[j % PF] = *reinterpret_cast<const real4*>(sh.lrec[j + PF]); }
+            const real rh = rec4<MR_RHS>(&ca), th = rec4<MR_THRESH>(&ca), lim = rec4<MR_IMP>(&ca);
+            const real lor = rec4<LR_LO>(&cl), hir = rec4<LR_HI>(&cl), wd = rec4<LR_JWDINV>(&cl);
+            real y = -rdlane(za, j);
+            real sum = lam_a[j] + (rh - y);
+            sum = med3_(sum, -lim, lim);
+            const real dl = sum - lam_a[j]; lam_a[j] = sum;
+            if (CHECK) busy |= __ballot(absr(dl) > th);
+            if (FULL || j >= 7) {
+              y += dl * wd;
+              real s2 = lam_lo[j] + (lor - y); s2 = max_(s2, (real)0);
+              const real d2 = s2 - lam_lo[j]; lam_lo[j] = s2;
+              if (CHECK) busy |= __ballot(absr(d2) > th);
+              y += d2 * wd;
+              real s3 = lam_hi[j] + (hir + y); s3 = max_(s3, (real)0);
+              const real d3 = s3 - lam_hi[j]; lam_hi[j] = s3;
+              if (CHECK) busy |= __ballot(absr(d3) > th);
+              za += Bn[j] * (dl + d2 - d3);
+            } else {
+              amax = max_(amax, absr(sum));                         // watched in EVERY iteration (one v_max): a multiplier may touch its bound and leave it again
+              za += Bn[j] * dl;
+            }
           }
         }
-        // pipe motor row 9 + jp: every lane clamps its own z, the row's lane supplies the step
         const int g = 9 + jp;
-        const real cand = med3_(zp, -ubv, ubv);              // (the motor rows' bounds are symmetric; two vector sources, see gs_row2_normal)
-        const real dlv = cand - lamr[g];
-        const real sdl = rdlane(dlv, g);
-        if (CHECK) busy |= __ballot(absr(dlv) > thr) & (1ull << g);
-        lamr[g] += sdl;
-        zp += Bn[g] * sdl;
+        if (RES) {
+          // residual pipe motor row 9 + jp: the row's lane supplies the step, |r_g| before the update is the |dl| of the exit test
+          const real sdl = rdlane(zp, g);
+          if (CHECK) busy |= __ballot(absr(zp) > thr) & (1ull << g);
+          lam += ind[g] * sdl;
+          zp += Bn[g] * sdl;
+        } else {
+          // pipe motor row 9 + jp: every lane clamps its own z, the row's lane supplies the step
+          const real cand = med3_(zp, -ubv, ubv);              // (the motor rows' bounds are symmetric; two vector sources, see gs_row2_normal)
+          const real dlv = cand - lamr[g];
+          const real sdl = rdlane(dlv, g);
+          if (CHECK) busy |= __ballot(absr(dlv) > thr) & (1ull << g);
+          lamr[g] += sdl;
+          zp += Bn[g] * sdl;
+        }
       }
       z = (za + zp) - z;
+      if (RES) wmax = max_(wmax, absr(lam));   // (every lane: the contact lanes' values are never looked at)
       // contacts: normal, dir1, dir2 -- the friction bounds follow the normal multiplier; Bullet leaves the friction rows of an
       // unloaded contact alone: a wave-uniform branch (half of the listed contacts are unloaded; collapsing their bounds onto the
       // current multiplier instead -- branch-free, step 0 -- costs the 14 VALU of two rows for nothing: 263 k vs 247 k cycles at 8-10)
@@ -603,13 +658,48 @@ PIH_HD int pgs_rows(Wave& w, Shared& sh, const Params& P) {
       }
       return CHECK && busy == 0;
     };
-    if (angmask != 0) it = pgs_iteration_loop(P.iters, P.checkstride, [&]() __attribute__((always_inline)) { return iterate(std::true_type{}, std::true_type{}); }, [&]() __attribute__((always_inline)) { return iterate(std::false_type{}, std::true_type{}); });
-    else it = pgs_iteration_loop(P.iters, P.checkstride, [&]() __attribute__((always_inline)) { return iterate(std::true_type{}, std::false_type{}); }, [&]() __attribute__((always_inline)) { return iterate(std::false_type{}, std::false_type{}); });
-    return __builtin_amdgcn_readfirstlane(amax >= armlim ? 1 : 0) != 0;   // (armlim = the smallest bound of rows 0..6: conservative if they differ, exact if equal)
+    // (the speculating instantiations carry the doubled unchecked body; the clamped ones -- the fallback, fewer than 1 in 10^4 env-steps,
+    //  and the A/B switch -- a single copy, which holds the code size)
+    if (angmask != 0) it = pgs_iteration_loop<RES>(P.iters, P.checkstride, [&]() __attribute__((always_inline)) { return iterate(std::true_type{}, std::true_type{}); }, [&]() __attribute__((always_inline)) { return iterate(std::false_type{}, std::true_type{}); });
+    else it = pgs_iteration_loop<RES>(P.iters, P.checkstride, [&]() __attribute__((always_inline)) { return iterate(std::true_type{}, std::false_type{}); }, [&]() __attribute__((always_inline)) { return iterate(std::false_type{}, std::false_type{}); });
+    if (RES) {
+      // ---- verification.  A residual row is the clamped row as long as its multiplier stays inside (-bound, bound).  The two forms round
+      // differently: each accumulates at most 50 x 30 increments, every one rounded to 2^-24 relative, so their multipliers can part by
+      // about 1 500 x 2^-24 ~ 1e-4 of their size.  The test asks for |lambda| < bound (1 - 2^-7) at every iteration's end -- eighty times
+      // that -- so a row that passes is not clamped in the z form either.  (Measured multipliers stay an order of magnitude below the
+      // bound: DESIGN 6.2.)  Compared as bit patterns -- for non-negative floats the integer order is the float order, NaN and Inf
+      // lie above every finite value -- so that a non-finite multiplier, bound or maximum fails the test whatever -ffast-math assumes;
+      // v_max may drop a NaN operand, hence the final lam is tested as well (a non-finite multiplier stays non-finite).
+      const bool resrow = (lane >= 9 && lane < NMOT) || (RESARM && lane < 7);
+      const real bound = lane < 7 ? armlim : ubv;
+      const unsigned lb = __builtin_bit_cast(unsigned, bound * (real)0.9921875);
+      const unsigned wb = __builtin_bit_cast(unsigned, wmax), fb = __builtin_bit_cast(unsigned, lam) & 0x7fffffffu;
+      const bool ok = lb < 0x7f800000u && wb < lb && fb < lb;
+      if (__ballot(resrow && !ok) != 0) return true;
+      // the tail below reads the multipliers of the motor rows as wave-uniform values
+#pragma unroll
+      for (int g = 9; g < NMOT; g++) lamr[g] = rdlane(lam, g);
+      if (RESARM) {
+#pragma unroll
+        for (int j = 0; j < 7; j++) lam_a[j] = rdlane(lam, j);
+      }
+      return false;
+    }
+    return !FULL && __builtin_amdgcn_readfirstlane(amax >= armlim ? 1 : 0) != 0;   // (armlim = the smallest bound of rows 0..6: conservative if they differ, exact if equal)
   };
-  int variant = 1;
-  if (!skip7) { solve(std::true_type{}); variant = 2; }
-  else if (solve(std::false_type{})) { solve(std::true_type{}); variant = 4; }
+  // one call site per instantiation (each is some 10^4 instructions)
+  int variant = skip7 ? 1 : 2;
+  bool again;
+  if (spec) again = skip7 ? solve(std::false_type{}, std::true_type{}) : solve(std::true_type{}, std::true_type{});
+  else again = skip7 ? solve(std::false_type{}, std::false_type{}) : true;
+  if (again) {
+    if (spec) {                              // back to the z form: the own-lane coefficients of the pipe motor rows
+#pragma unroll
+      for (int g = 9; g < NMOT; g++) Bn[g] = lane == g ? bown : Bn[g];
+    }
+    solve(std::true_type{}, std::false_type{});
+    if (spec || skip7) variant = 4;
+  }
   if (lane == 0) sh.S[PIH_S_SOLVER] = (real)variant;
   // multipliers back to LDS: contacts -> r_lam, pipe motors -> MR_LAM of their (now unused) constant record
   if (lane >= NMOT && lane < NMOT + 3 * nc) sh.r_lam[lane - NMOT] = lam;

@@ -148,7 +148,7 @@ class PihVecEnv:
     # --- checkpoint / resume: everything a handle owns is its per-env state record -- the 98 physical words incl. the
     # RNG draw counters and step counters, the derived outputs, the warm-start contact cache -- plus the base seed; the config rides
     # along so that a checkpoint is only loaded into a handle that simulates the same thing.
-    # Every field of pih_config has to agree but these: `schedule` and `debug` do not change results, `seed` is checked on its own,
+    # Every field of pih_config has to agree but these: `schedule` and `debug` do not change what is simulated (schedule + 64 selects another rounding of the same PGS solve), `seed` is checked on its own,
     # `reserved_f` is unused.  (A new field is compared unless it is excluded here.)
     _CFG_KEYS = tuple(f for f, _ in _lib.PihConfig._fields_ if f not in ("schedule", "debug", "seed", "reserved_f"))
 
