@@ -279,4 +279,8 @@ const char* pih_last_error(pih_handle* h);
  * Defined here and not there because tests/test_abi_exports.py compares every *_WORDS name of _lib.py with THIS file */
 #define PIH_LIGHT_WORDS 11
 #include "pih_render_light.h"
+/* words of a link state of the robot-model queries declared in pih_robot.h: pos (3), quat xyzw (4), linear velocity of the frame origin (3),
+ * angular velocity (3).  Defined here for the same reason */
+#define PIH_LINK_STATE_WORDS 13
+#include "pih_robot.h"
 #endif

@@ -1,0 +1,69 @@
+/* pih_robot.h -- C ABI of the batched robot-model queries (libpih_hip.so); an addition to pih.h, which includes this file: include pih.h.
+ * The ABI version stays PIH_ABI_VERSION (the change is additive).  Declared here and not in pih.h for the reason pih_render_view.h
+ * states: tests pin the list of functions pih.h itself declares; tests/test_robot_query.py compares _lib.ROBOT_EXPORTS with THIS file.
+ *
+ * What replaces what (pybullet, per env and on the host -> one call for n problems on the device):
+ *   pih_robot_fk / pih_link_states     p.getLinkState(s)(computeLinkVelocity=1): [4:6] = the URDF link frame, [6:8] = its velocity
+ *   pih_robot_jacobian                 p.calculateJacobian(body, link, localPosition, q, ...)
+ *   pih_robot_mass_matrix              p.calculateMassMatrix(body, q)
+ *   pih_robot_inverse_dynamics         p.calculateInverseDynamics(body, q, qd, qdd)  -- see the damping note below
+ *
+ * Conventions: n problems, independent of the handle's env count (as pih_ik); both robots work on a handle of either task (as pih_ik /
+ * pih_ik_ur5).  Every pointer is a DEVICE pointer to float32, row-major, contiguous.  Nothing synchronises: the work is enqueued on the
+ * caller's stream.  n == 0 returns 0 without a launch.  Errors: -2, and pih_last_error names the argument, for an unknown robot, a frame
+ * out of range, n < 0, n > 2^30 or a NULL required pointer (pih_last_error(NULL) when the handle itself is NULL).
+ *
+ * Frames: the URDF link frames (not the centres of mass), indexed as the oracle's fk_arm / fk_ur5 index them:
+ *   PIH_ROBOT_PANDA  0 .. 8 = the merged links of pih_model.h (joints 1 .. 7, the two fingers), 9 = grasp-target (pybullet link 11)
+ *   PIH_ROBOT_UR5    0 .. 5 = the links of joints 1 .. 6, 6 = ee_link
+ * Positions are robot-base-local = env-local (the frame pih_ik's targets live in; no env offset).
+ *
+ * Joint values are caller data: the trigonometry is the full-range sincosf.  The accuracy figures of DESIGN.md 6.6 hold for |q| <= 2 pi;
+ * beyond that the outputs stay finite and lose accuracy as fp32 sin / cos of a large argument do (about |q| x 6e-8 in the rotation
+ * entries).  A NaN / Inf input gives non-finite outputs for THAT problem only: no table is indexed by anything derived from q.
+ */
+#ifndef PIH_ROBOT_H
+#define PIH_ROBOT_H
+#include "pih.h"
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define PIH_ROBOT_PANDA 0   /* 9 DOF (7 revolute + 2 finger prismatic); frames 0..8 = the merged links of pih_model.h, 9 = grasp-target (pybullet link 11) */
+#define PIH_ROBOT_UR5   1   /* 6 DOF; frames 0..5 = links, 6 = ee_link */
+
+/* out[0] = ndof, out[1] = nframes of a robot */
+int pih_robot_dims(int robot, int32_t out[2]);
+/* frames per env that pih_link_states writes for a task: peg-in-hole 10 Panda frames + PIH_OBJ_NL (24) pipe links = 34; random-fly 7 UR5
+ * frames + the object = 8; < 0 for an unknown task.  (pih_task_dims keeps its three outputs.) */
+int pih_link_states_frames(int task_id);
+
+/* link states: out_dev float[n, nframes, PIH_LINK_STATE_WORDS] = pos (3), quat xyzw (4), linear velocity of the frame ORIGIN (3), angular
+ * velocity (3), all in the base-local frame's axes.  qd_dev float[n, ndof] or NULL: the velocity words are 0. */
+int pih_robot_fk(pih_handle* h, int robot, int n, const float* q_dev, const float* qd_dev, float* out_dev, void* stream);
+/* out_dev float[n, 6, ndof]: rows 0..2 linear, 3..5 angular, for the point local_pos (in the frame's coordinates; local_pos_dev float[n, 3]
+ * or NULL = the frame's origin) of frame `frame`.  Columns of joints that are not ancestors of the frame are 0; a finger column is
+ * (axis, 0).  J qd = the velocity words of pih_robot_fk. */
+int pih_robot_jacobian(pih_handle* h, int robot, int n, const float* q_dev, int frame, const float* local_pos_dev, float* out_dev, void* stream);
+/* out_dev float[n, ndof, ndof]: the arm's joint-space inertia (Panda: 9 x 9, the two finger DOF on the hand's branch included).  Both
+ * triangles are written from the same value: the output is bitwise symmetric. */
+int pih_robot_mass_matrix(pih_handle* h, int robot, int n, const float* q_dev, float* out_dev, void* stream);
+/* tau_dev float[n, ndof] = M(q) qdd + Coriolis / centrifugal + gravity (PIH_GRAVITY_Z) + damping: the exact inverse of the FREE dynamics of
+ * pih_step, tau(q, qd, the step's free acceleration at (q, qd)) = 0.  Damping is what the step applies: the joint damping
+ * PIH_LINK_DAMPING / PIH_UR5_DAMPING x qd, and Bullet's per-link damping (every link's m v (k + k |v|) at its centre of mass and
+ * I w (k + k |w|), k = 0.04), which the step's free dynamics contain for both robots.
+ * PyBullet's calculateInverseDynamics leaves BOTH out.  PIH_LINK_DAMPING is all zero for the Panda; for the UR5 the caller subtracts
+ * PIH_UR5_DAMPING x qd for the joint part.  The link part has no closed form in qd; it is the odd part of tau in qd minus the joint part:
+ * (tau(q, qd, qdd) - tau(q, -qd, qdd)) / 2 - PIH_UR5_DAMPING x qd, so PyBullet's value is (tau(q, qd, qdd) + tau(q, -qd, qdd)) / 2. */
+int pih_robot_inverse_dynamics(pih_handle* h, int robot, int n, const float* q_dev, const float* qd_dev, const float* qdd_dev, float* tau_dev, void* stream);
+/* every frame of the envs' CURRENT state in WORLD coordinates (env offset added, as PIH_S_EE / PIH_F_EE are):
+ * out_dev float[env_count, pih_link_states_frames(task), PIH_LINK_STATE_WORDS] for envs env_begin .. env_begin + env_count - 1.
+ *   peg-in-hole: the 10 Panda frames, then the 24 pipe links (pipe link 0 = the state's base pose; velocities from the joint rates and the
+ *                base twist of the state)
+ *   random-fly:  the 7 UR5 frames, then the object
+ * env_begin < 0, env_count <= 0 or env_begin + env_count > n_envs: -2, as pih_render_cam. */
+int pih_link_states(pih_handle* h, float* out_dev, int env_begin, int env_count, void* stream);
+#ifdef __cplusplus
+}
+#endif
+#endif

@@ -24,6 +24,9 @@ VIEW_CAM_OVERVIEW = (1.33, -0.02, 1.05, 0.05, -0.25, 0.3, 0.0, 0.0, 1.0, 40.0, 1
 LIGHT_WORDS = 11   # direction xyz (towards the light, env-local), colour rgb, ambient, diffuse, specular, shininess, shadow factor (1 = no shadows)
 LIGHT_DEFAULT = (-50.0, 30.0, 100.0, 1.0, 1.0, 1.0, 0.6, 0.35, 0.05, 2.0, 0.8)     # PIH_LIGHT_DEFAULT
 RENDER_LIGHT_DEVICE = 64                           # the light argument is a device pointer float[env_count, LIGHT_WORDS], one light per env
+# batched robot-model queries (include/pih_robot.h): link states, Jacobians, mass matrix, inverse dynamics
+LINK_STATE_WORDS = 13   # pos xyz, quat xyzw, linear velocity of the frame origin, angular velocity
+ROBOT_PANDA, ROBOT_UR5 = 0, 1                      # PIH_ROBOT_*: 9 DOF / 10 frames (9 = grasp-target), 6 DOF / 7 frames (6 = ee_link)
 FIELD_STATE, FIELD_TIP_POSE, FIELD_CONTACT_FORCE, FIELD_DEBUG, FIELD_EE_POS = 0, 1, 2, 3, 4
 TASK_PEG_IN_HOLE, TASK_RANDOM_FLY = 0, 1
 # state record word offsets (PIH_S_*)
@@ -42,6 +45,8 @@ DBG_CYCLES, DBG_T_START, DBG_T_END, DBG_HW_ID, DBG_XCC_ID = 900, 940, 943, 946, 
 EXPORTS = ["pih_default_config", "pih_abi_version", "pih_task_dims", "pih_object_name", "pih_create", "pih_destroy", "pih_reset", "pih_reseed", "pih_step", "pih_step_n",
            "pih_get_state", "pih_set_state", "pih_ik", "pih_ik_ur5", "pih_render", "pih_render_ex", "pih_render_cam", "pih_grasp_labels", "pih_timing", "pih_timing2", "pih_set_timing", "pih_last_error"]
 LIGHT_EXPORTS = ["pih_render_lit"]      # what include/pih_render_light.h declares (tests/test_render_lit.py compares it with that header)
+ROBOT_EXPORTS = ["pih_robot_dims", "pih_link_states_frames", "pih_robot_fk", "pih_robot_jacobian", "pih_robot_mass_matrix", "pih_robot_inverse_dynamics",
+                 "pih_link_states"]      # what include/pih_robot.h declares (tests/test_robot_query.py compares it with that header)
 VIEW_EXPORTS = ["pih_render_view"]      # what include/pih_render_view.h declares on top of that (tests/test_peg_view.py compares it with that header)
 
 
@@ -96,6 +101,13 @@ def load():
                                   C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]
     L.pih_render_view.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]      # (camera: as pih_render_cam; None = the wrist preset)
     L.pih_render_lit.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]      # (camera as above; light: a (c_float * LIGHT_WORDS) array, None = LIGHT_DEFAULT, or with RENDER_LIGHT_DEVICE a device address)
+    L.pih_robot_dims.argtypes = [C.c_int, C.POINTER(C.c_int32 * 2)]
+    L.pih_link_states_frames.argtypes = [C.c_int]
+    L.pih_robot_fk.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, vp]                      # (h, robot, n, q, qd or None, out, stream)
+    L.pih_robot_jacobian.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp]       # (h, robot, n, q, frame, local_pos or None, out, stream)
+    L.pih_robot_mass_matrix.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp]
+    L.pih_robot_inverse_dynamics.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, vp, vp]
+    L.pih_link_states.argtypes = [vp, vp, C.c_int, C.c_int, vp]
     L.pih_grasp_labels.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp]
     L.pih_reseed.argtypes = [vp, C.c_uint64]
     L.pih_timing.argtypes = [vp, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
@@ -115,6 +127,22 @@ def task_dims(task_id):
     if load().pih_task_dims(int(task_id), C.byref(out)) != 0:
         raise PihError("unknown task_id %r" % (task_id,))
     return int(out[0]), int(out[1]), int(out[2])
+
+
+def robot_dims(robot):
+    """(ndof, nframes) of a robot (ROBOT_PANDA / ROBOT_UR5), from the library"""
+    out = (C.c_int32 * 2)()
+    if load().pih_robot_dims(int(robot), C.byref(out)) != 0:
+        raise PihError("unknown robot %r" % (robot,))
+    return int(out[0]), int(out[1])
+
+
+def link_states_frames(task_id):
+    """frames per env of PihVecEnv.link_states for a task (peg-in-hole: 10 Panda frames + 24 pipe links; random-fly: 7 UR5 frames + the object)"""
+    k = load().pih_link_states_frames(int(task_id))
+    if k < 0:
+        raise PihError("unknown task_id %r" % (task_id,))
+    return k
 
 
 def object_names(task_id):

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -25,6 +26,14 @@ void view_launch(int fmt, dim3 grid, hipStream_t stream, const float* state, voi
 int lit_light_check(const float* words, const char** what);
 void lit_launch(bool fly_task, int fmt, dim3 grid, hipStream_t stream, const float* state, void* out, const fly::FlyCam& cam, const float* cam_dev,
                 const float* light, const float* light_dev, int n, int object, int env_begin, int W, int H, int rows_per_strip, int flags);
+// pih_robot.hip: the batched robot-model queries of include/pih_robot.h
+void robot_fk_launch(int robot, bool staged, hipStream_t stream, int n, const float* q, const float* qd, float* out);
+void robot_jacobian_launch(int robot, bool staged, hipStream_t stream, int n, const float* q, int frame, const float* local_pos, float* out);
+void robot_mass_launch(int robot, bool staged, hipStream_t stream, int n, const float* q, float* out);
+void robot_invdyn_launch(int robot, hipStream_t stream, int n, const float* q, const float* qd, const float* qdd, float* tau);
+void link_states_launch(bool fly_task, hipStream_t stream, const float* state, float* out, int n_envs, int env_begin, int env_count);
+int robot_dims(int robot, int* ndof, int* nframes);
+int link_states_frames(int task_id);
 }
 
 // ------------------------------------------------------------------------------------------------ kernels
@@ -1038,6 +1047,106 @@ int pih_timing(pih_handle* h, int reset, double* avg_ms_out, int64_t* launches_o
   int r = pih_timing2(h, reset, &a, &b, launches_out);
   if (r == 0 && avg_ms_out) *avg_ms_out = a + b;
   return r;
+}
+
+// ---- batched robot-model queries (include/pih_robot.h; kernels in pih_robot.hip).  Every argument is checked before the device is touched.
+static int robot_bad(pih_handle* h, const char* call, const char* arg, const char* why) {
+  const std::string m = std::string(call) + ": " + arg + " " + why;
+  if (h) h->err = m;
+  g_err = m;
+  return -2;
+}
+// the checks the four queries share; *ndof / *nframes of the robot.  -> 0, -2, or 1 for n == 0 (nothing to do)
+static int robot_check(pih_handle* h, const char* call, int robot, int n, int* ndof, int* nframes) {
+  if (!h) return robot_bad(h, call, "h", "is NULL");
+  if (robot_dims(robot, ndof, nframes) != 0) return robot_bad(h, call, "robot", "is neither PIH_ROBOT_PANDA nor PIH_ROBOT_UR5");
+  if (n < 0) return robot_bad(h, call, "n", "is negative");
+  if (n > (1 << 30)) return robot_bad(h, call, "n", "is larger than 2^30");
+  return n == 0 ? 1 : 0;
+}
+// Which store variant of pih_robot.hip a call of n problems uses: every lane stores its own rows below `threshold` problems, the wavefront's
+// rows go through LDS from there on.  The thresholds are where the staged variant became the faster one on the MI355X (DESIGN.md 6.6:
+// below them a call is launch-bound and the barrier and the copy loop only add latency; inverse dynamics, 6 .. 9 words per problem, never
+// gains).  PIH_ROBOT_STORE = direct | staged in the environment overrides the rule: the measurement switch of tools/robot_query_bench.py,
+// not part of the ABI.  Same values either way.
+constexpr int ROBOT_FK_STAGED_FROM = 32768, ROBOT_JACOBIAN_STAGED_FROM = 16384, ROBOT_MASS_STAGED_FROM = 24576;
+static bool robot_staged(int n, int threshold) {
+  const char* e = getenv("PIH_ROBOT_STORE");
+  if (e && !strcmp(e, "direct")) return false;
+  if (e && !strcmp(e, "staged")) return true;
+  return n >= threshold;
+}
+
+int pih_robot_dims(int robot, int32_t out[2]) {
+  int nd, nf;
+  if (!out) return robot_bad(nullptr, "pih_robot_dims", "out", "is NULL");
+  if (robot_dims(robot, &nd, &nf) != 0) return robot_bad(nullptr, "pih_robot_dims", "robot", "is neither PIH_ROBOT_PANDA nor PIH_ROBOT_UR5");
+  out[0] = nd; out[1] = nf;
+  return 0;
+}
+int pih_link_states_frames(int task_id) { return link_states_frames(task_id); }
+
+int pih_robot_fk(pih_handle* h, int robot, int n, const float* q_dev, const float* qd_dev, float* out_dev, void* stream) {
+  int nd, nf;
+  const int c = robot_check(h, "pih_robot_fk", robot, n, &nd, &nf);
+  if (c) return c < 0 ? c : 0;
+  if (!q_dev) return robot_bad(h, "pih_robot_fk", "q_dev", "is NULL");
+  if (!out_dev) return robot_bad(h, "pih_robot_fk", "out_dev", "is NULL");
+  PIH_ENTER(h);
+  robot_fk_launch(robot, robot_staged(n, ROBOT_FK_STAGED_FROM), (hipStream_t)stream, n, q_dev, qd_dev, out_dev);
+  HIPCHK(h, hipGetLastError());
+  return 0;
+}
+
+int pih_robot_jacobian(pih_handle* h, int robot, int n, const float* q_dev, int frame, const float* local_pos_dev, float* out_dev, void* stream) {
+  int nd, nf;
+  const int c = robot_check(h, "pih_robot_jacobian", robot, n, &nd, &nf);
+  if (c < 0) return c;
+  if (frame < 0 || frame >= nf) return robot_bad(h, "pih_robot_jacobian", "frame", "is outside the robot's frames");
+  if (c) return 0;
+  if (!q_dev) return robot_bad(h, "pih_robot_jacobian", "q_dev", "is NULL");
+  if (!out_dev) return robot_bad(h, "pih_robot_jacobian", "out_dev", "is NULL");
+  PIH_ENTER(h);
+  robot_jacobian_launch(robot, robot_staged(n, ROBOT_JACOBIAN_STAGED_FROM), (hipStream_t)stream, n, q_dev, frame, local_pos_dev, out_dev);
+  HIPCHK(h, hipGetLastError());
+  return 0;
+}
+
+int pih_robot_mass_matrix(pih_handle* h, int robot, int n, const float* q_dev, float* out_dev, void* stream) {
+  int nd, nf;
+  const int c = robot_check(h, "pih_robot_mass_matrix", robot, n, &nd, &nf);
+  if (c) return c < 0 ? c : 0;
+  if (!q_dev) return robot_bad(h, "pih_robot_mass_matrix", "q_dev", "is NULL");
+  if (!out_dev) return robot_bad(h, "pih_robot_mass_matrix", "out_dev", "is NULL");
+  PIH_ENTER(h);
+  robot_mass_launch(robot, robot_staged(n, ROBOT_MASS_STAGED_FROM), (hipStream_t)stream, n, q_dev, out_dev);
+  HIPCHK(h, hipGetLastError());
+  return 0;
+}
+
+int pih_robot_inverse_dynamics(pih_handle* h, int robot, int n, const float* q_dev, const float* qd_dev, const float* qdd_dev, float* tau_dev, void* stream) {
+  int nd, nf;
+  const int c = robot_check(h, "pih_robot_inverse_dynamics", robot, n, &nd, &nf);
+  if (c) return c < 0 ? c : 0;
+  if (!q_dev) return robot_bad(h, "pih_robot_inverse_dynamics", "q_dev", "is NULL");
+  if (!qd_dev) return robot_bad(h, "pih_robot_inverse_dynamics", "qd_dev", "is NULL");
+  if (!qdd_dev) return robot_bad(h, "pih_robot_inverse_dynamics", "qdd_dev", "is NULL");
+  if (!tau_dev) return robot_bad(h, "pih_robot_inverse_dynamics", "tau_dev", "is NULL");
+  PIH_ENTER(h);
+  robot_invdyn_launch(robot, (hipStream_t)stream, n, q_dev, qd_dev, qdd_dev, tau_dev);
+  HIPCHK(h, hipGetLastError());
+  return 0;
+}
+
+int pih_link_states(pih_handle* h, float* out_dev, int env_begin, int env_count, void* stream) {
+  if (!h) return robot_bad(h, "pih_link_states", "h", "is NULL");
+  if (!out_dev) return robot_bad(h, "pih_link_states", "out_dev", "is NULL");
+  if (env_begin < 0 || env_count <= 0 || env_begin > h->cfg.n_envs || env_count > h->cfg.n_envs - env_begin)
+    return robot_bad(h, "pih_link_states", "env_begin / env_count", "is outside the handle's envs");
+  PIH_ENTER(h);
+  link_states_launch(h->fly, (hipStream_t)stream, h->state, out_dev, h->cfg.n_envs, env_begin, env_count);
+  HIPCHK(h, hipGetLastError());
+  return 0;
 }
 
 const char* pih_last_error(pih_handle* h) { return h ? h->err.c_str() : g_err.c_str(); }

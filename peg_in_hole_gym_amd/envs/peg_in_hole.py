@@ -119,6 +119,11 @@ class PegInHole(MetaEnv):
         backend's image tensor for all its envs"""
         return self._backend.render_view(**kw)
 
+    def link_states(self, **kw):
+        """getLinkStates(computeLinkVelocity=1) of the Panda's 10 frames and the pipe's 24 links in world coordinates
+        (PihVecEnv.link_states) -> the backend's [envs, 34, 13] tensor"""
+        return self._backend.link_states(**kw)
+
 
 class RandomFly(MetaEnv):
     """'random-fly' (README.md:38: task='random-fly', args=['Banana', 1/120.]): the UR5 of assets/urdf/ur5.urdf driven by
@@ -155,3 +160,8 @@ class RandomFly(MetaEnv):
         kw = {} if light is None else {"light": light}
         img = self._backend.render(300, 300, shaded=True, camera=camera, ee_frame=ee_frame, **kw)
         return (img.detach().cpu().numpy() if hasattr(img, "detach") else np.asarray(img))[0].astype(np.float64)
+
+    def link_states(self, **kw):
+        """getLinkStates(computeLinkVelocity=1) of the UR5's 7 frames and the object in world coordinates (PihVecEnv.link_states) -> the
+        backend's [envs, 8, 13] tensor"""
+        return self._backend.link_states(**kw)

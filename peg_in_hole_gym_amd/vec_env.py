@@ -216,6 +216,79 @@ class PihVecEnv:
             self._chk(self.L.pih_ik_ur5(self.h, n, q0.data_ptr(), tpos.data_ptr(), tquat.data_ptr(), out.data_ptr(), self._stream()), "pih_ik_ur5")
         return out
 
+    # --- batched robot-model queries (include/pih_robot.h): what a controller or a reward asks pybullet per env -- getLinkStates,
+    # calculateJacobian, calculateMassMatrix, calculateInverseDynamics -- for n problems at once on the device.  n is independent of the
+    # handle's env count; robot = _lib.ROBOT_PANDA / _lib.ROBOT_UR5, None = the robot of the handle's task.  Inputs of any float dtype /
+    # device are brought to float32 on the handle's device, as ik() does; nothing synchronises.
+    def _robot(self, robot):
+        if robot is None:
+            robot = _lib.ROBOT_UR5 if self.task_id == _lib.TASK_RANDOM_FLY else _lib.ROBOT_PANDA
+        ndof, nframes = _lib.robot_dims(robot)         # (PihError for an unknown robot)
+        return int(robot), ndof, nframes
+
+    def _rows(self, what, t, n, width):
+        t = torch.as_tensor(t).to(device=self.device, dtype=torch.float32).contiguous()
+        if t.ndim != 2 or t.shape[1] != width or (n is not None and t.shape[0] != n):
+            raise ValueError("%s must have shape [%s, %d], got %s" % (what, "n" if n is None else n, width, tuple(t.shape)))
+        return t
+
+    def robot_fk(self, q, qd=None, robot=None):
+        """getLinkStates(computeLinkVelocity=1): q [n, ndof] (qd [n, ndof] or None: zero velocities) -> float32 [n, nframes, 13] = pos,
+        quat xyzw, linear velocity of the frame origin, angular velocity of every URDF link frame (Panda: 0..8 links, 9 grasp-target;
+        UR5: 0..5 links, 6 ee_link), robot-base-local like ik()'s targets (no env offset)."""
+        robot, ndof, nframes = self._robot(robot)
+        q = self._rows("robot_fk: q", q, None, ndof); n = q.shape[0]
+        qd = None if qd is None else self._rows("robot_fk: qd", qd, n, ndof)
+        out = torch.empty(n, nframes, _lib.LINK_STATE_WORDS, device=self.device)
+        with torch.cuda.device(self.device):
+            self._chk(self.L.pih_robot_fk(self.h, robot, n, q.data_ptr(), qd.data_ptr() if qd is not None else None, out.data_ptr(), self._stream()), "pih_robot_fk")
+        return out
+
+    def jacobian(self, q, frame=None, local_pos=None, robot=None):
+        """calculateJacobian: float32 [n, 6, ndof], rows 0..2 linear and 3..5 angular, for the point local_pos ([n, 3] in the frame's
+        coordinates; None = its origin) of frame `frame` (None = the end-effector frame)."""
+        robot, ndof, nframes = self._robot(robot)
+        q = self._rows("jacobian: q", q, None, ndof); n = q.shape[0]
+        lp = None if local_pos is None else self._rows("jacobian: local_pos", local_pos, n, 3)
+        out = torch.empty(n, 6, ndof, device=self.device)
+        with torch.cuda.device(self.device):
+            self._chk(self.L.pih_robot_jacobian(self.h, robot, n, q.data_ptr(), nframes - 1 if frame is None else int(frame),
+                                                lp.data_ptr() if lp is not None else None, out.data_ptr(), self._stream()), "pih_robot_jacobian")
+        return out
+
+    def mass_matrix(self, q, robot=None):
+        """calculateMassMatrix: float32 [n, ndof, ndof], bitwise symmetric (Panda: 9 x 9 with the two finger DOF)."""
+        robot, ndof, _ = self._robot(robot)
+        q = self._rows("mass_matrix: q", q, None, ndof); n = q.shape[0]
+        out = torch.empty(n, ndof, ndof, device=self.device)
+        with torch.cuda.device(self.device):
+            self._chk(self.L.pih_robot_mass_matrix(self.h, robot, n, q.data_ptr(), out.data_ptr(), self._stream()), "pih_robot_mass_matrix")
+        return out
+
+    def inverse_dynamics(self, q, qd, qdd, robot=None):
+        """float32 [n, ndof]: tau = M(q) qdd + Coriolis + gravity + the step's damping -- the inverse of the step's FREE dynamics.
+        pybullet's calculateInverseDynamics has no damping: include/pih_robot.h says how to take it out."""
+        robot, ndof, _ = self._robot(robot)
+        q = self._rows("inverse_dynamics: q", q, None, ndof); n = q.shape[0]
+        qd = self._rows("inverse_dynamics: qd", qd, n, ndof); qdd = self._rows("inverse_dynamics: qdd", qdd, n, ndof)
+        out = torch.empty(n, ndof, device=self.device)
+        with torch.cuda.device(self.device):
+            self._chk(self.L.pih_robot_inverse_dynamics(self.h, robot, n, q.data_ptr(), qd.data_ptr(), qdd.data_ptr(), out.data_ptr(), self._stream()), "pih_robot_inverse_dynamics")
+        return out
+
+    def link_states(self, env_begin=0, env_count=None, out=None):
+        """Every frame of the envs' CURRENT state in world coordinates (env offset added): float32 [count, frames, 13].  peg-in-hole: the
+        10 Panda frames, then the 24 pipe links (34); random-fly: the 7 UR5 frames, then the object (8)."""
+        count = self.n - env_begin if env_count is None else env_count
+        shape = (count, _lib.link_states_frames(self.task_id), _lib.LINK_STATE_WORDS)
+        if out is None:
+            out = torch.empty(shape, device=self.device)
+        elif not (torch.is_tensor(out) and out.dtype == torch.float32 and tuple(out.shape) == shape and self._here(out) and out.is_contiguous()):
+            raise ValueError("link_states: out must be a contiguous float32 tensor of shape %s on %s" % (shape, self.device))
+        with torch.cuda.device(self.device):
+            self._chk(self.L.pih_link_states(self.h, out.data_ptr(), int(env_begin), int(count), self._stream()), "pih_link_states")
+        return out
+
     def _here(self, t):
         """is the tensor on this handle's device? (a handle made with device="cuda" has no index)"""
         return t.device.type == self.device.type and (self.device.index is None or t.device.index == self.device.index)

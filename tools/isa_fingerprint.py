@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Fingerprint of the gfx950 code of every kernel of the library (pih_hip.hip, pih_fly_image.hip, pih_view.hip, pih_lit.hip), without a GPU: one line per kernel with a hash of its instruction
+"""Fingerprint of the gfx950 code of every kernel of the library (pih_hip.hip, pih_fly_image.hip, pih_view.hip, pih_lit.hip, pih_robot.hip), without a GPU: one line per kernel with a hash of its instruction
 stream, the instruction count and the VGPR / AGPR / SGPR / LDS / scratch numbers of the code object metadata.  A refactor that leaves
 the lines of the hot kernels unchanged leaves their speed unchanged (the step kernels sit at the 256-register limit).
 usage: python tools/isa_fingerprint.py [SOURCE_TREE]    (default: this checkout; e.g. a `git worktree add` of another commit)"""
@@ -17,7 +17,7 @@ from peg_in_hole_gym_amd.csrc.build import FLAGS  # noqa: E402
 META = ("vgpr_count", "agpr_count", "sgpr_count", "group_segment_fixed_size", "private_segment_fixed_size")
 
 
-SOURCES = ("pih_hip.hip", "pih_fly_image.hip", "pih_view.hip", "pih_lit.hip")       # the library's translation units (a tree from before one existed is read without it)
+SOURCES = ("pih_hip.hip", "pih_fly_image.hip", "pih_view.hip", "pih_lit.hip", "pih_robot.hip")       # the library's translation units (a tree from before one existed is read without it)
 
 
 def assembly(tree, name="pih_hip.hip"):
