@@ -24,9 +24,17 @@
 // is the union of its two end spheres' bounds; a sphere that reaches the eye plane keeps its primitive on for every tile) against the
 // tile, the ballot is the tile's primitive list, one tile row is one coalesced 1 KB store.
 // Everything here is PIH_HD on `real`: the host build of tests/emul compiles the same per-scene and per-pixel code in fp64 and fp32.
+//
+// This header is also the home of what ALL camera kernels share (the wrist camera of pih_render.h, this camera, pih_view.h, pih_lit.h), each
+// piece once: FlyGrid (pixel grid), camera_or_preset, load_row, load_fly_pose, Pixels / NoLight (with lit::LitPixels / lit::LightHook)
+// -- these also in the host build -- and, device only, render_strip (THE tile walk), render_image (the walk in an output format),
+// camera_setup (this task's scene set-up; view::camera_setup is the peg-in-hole one) and dispatch_fmt (format -> kernel instance).
 #pragma once
 #include "pih_common.h"
 #include "pih_raycast.h"
+#ifndef PIH_PLATFORM_DEFINED
+#include <type_traits>
+#endif
 
 namespace pih {
 namespace fly {
@@ -247,16 +255,124 @@ PIH_HHD int cam_degenerate(const float* c) {
   return CAM_OK;
 }
 
+// The camera a kernel (or the host build) uses: `cam` if it passes cam_degenerate, else `preset` -- so that the scene stays finite; the env
+// then gets the background.  -> the code of cam_degenerate.  flags != nullptr: `preset` is the peg-in-hole wrist preset, which is given in
+// the PIH_RENDER_CAM_EE_POS frame whatever frame flag the call carries.
+PIH_HHD int camera_or_preset(FlyCam& cam, const FlyCam& preset, int* flags = nullptr) {
+  const int code = cam_degenerate(cam.w);
+  if (code != CAM_OK) {
+    cam = preset;
+    if (flags) *flags = (*flags & ~PIH_RENDER_CAM_EE) | PIH_RENDER_CAM_EE_POS;
+  }
+  return code;
+}
+// row `e` of a [count, N] array of per-env cameras (floats) or lights (words as integers: pih_lit.h), if there is one: N wave-uniform loads
+template <class T, int N> PIH_HD void load_row(T (&dst)[N], const T* rows, int e) {
+  if (rows) {
+#pragma unroll
+    for (int i = 0; i < N; i++) dst[i] = rows[(size_t)e * N + i];
+  }
+}
+// the words of env `env`'s state record the camera needs; word k of the env is state[k * n + env] (the library's structure-of-arrays state:
+// 13 wave-uniform loads; an env-major record of the host build: env = 0, n = 1)
+template <class T> PIH_HD FlyPose load_fly_pose(const T* state, int env, int n) {
+  FlyPose ps;
+  const T* rec = state + env;
+#pragma unroll
+  for (int i = 0; i < RCAP; i++) ps.q[i] = (real)rec[(size_t)(PIH_F_Q + i) * n];
+#pragma unroll
+  for (int i = 0; i < 3; i++) ps.opos[i] = (real)rec[(size_t)(PIH_F_OPOS + i) * n];
+#pragma unroll
+  for (int i = 0; i < 4; i++) ps.oquat[i] = (real)rec[(size_t)(PIH_F_OQUAT + i) * n];
+  return ps;
+}
+
 // The pixel grid, shared by the kernel and the host build: pixel-centre and tile-edge coordinates on the camera plane
 struct FlyGrid {
   real sx, sy, tx, ty;
-  template <class S /* FlyScene, view::ViewScene */> PIH_HD FlyGrid(const S& sc, int W, int H) : sx((real)2 / (real)W), sy((real)2 / (real)H), tx(sc.tx), ty(sc.ty) {}
+  PIH_HD FlyGrid(real tx_, real ty_, int W, int H) : sx((real)2 / (real)W), sy((real)2 / (real)H), tx(tx_), ty(ty_) {}      // (the wrist camera: constants)
+  template <class S /* FlyScene, view::ViewScene */> PIH_HD FlyGrid(const S& sc, int W, int H) : FlyGrid(sc.tx, sc.ty, W, H) {}
   PIH_HD real xc(int j) const { return (sx * ((real)j + (real)0.5) - (real)1) * tx; }
   PIH_HD real yc(int i) const { return ((real)1 - sy * ((real)i + (real)0.5)) * ty; }
   PIH_HD real xedge(int j) const { return (sx * (real)j - (real)1) * tx; }
   PIH_HD real yedge(int i) const { return ((real)1 - sy * (real)i) * ty; }
 };
 constexpr int TILE_ROWS = 16, TILE_COLS = 64;        // one row of a tile per wave instruction
+
+// the three formats of one pixel of an unlit free camera, as render_image takes them: pixel_* of the scene's namespace (fly, view)
+template <class S, class MASK> struct Pixels {
+  const S& sc; int flags; bool bad;
+  PIH_HD unsigned as_rgba8(MASK prims, real xc, real yc) const { return pixel_rgba8(sc, prims, xc, yc, flags, bad); }
+  PIH_HD real as_depth(MASK prims, real xc, real yc) const { return pixel_depth(sc, prims, xc, yc, bad); }
+  PIH_HD real4 as_float4(MASK prims, real xc, real yc) const { return pixel_float4(sc, prims, xc, yc, flags, bad); }
+};
+// what a set-up hooks in for a camera without a caller-given light (pih_lit.h has the one with)
+struct NoLight {
+  static constexpr int LIGHT_THREAD = -1;      // no thread of the workgroup
+  PIH_HD void light_thread(unsigned long long) const {}
+  template <class S> PIH_HD void table(const S&, int) const {}
+  PIH_HD bool bad() const { return false; }
+};
+
+#ifndef PIH_PLATFORM_DEFINED      // ---------------------------------------------------------------- device only: the kernels' shared pieces
+// THE tile walk of the camera kernels (pih_lit_view_kernel alone keeps a copy: pih_lit.hip says why).  The workgroup renders rows r0 .. r1 - 1 of its env's image (whose row 0 is row `row0` of out, W values a row: the index stays in size_t): each WAVE
+// walks 16-row x 64-column tiles; lane i tests primitive i against the tile (prim_on_tile of the scene's namespace), the ballot is the
+// tile's primitive list (MASK: unsigned for the scenes of <= 32 primitives, unsigned long long for view::ViewScene); then one pixel per
+// lane, pixel(prims, xc, yc) -> the stored value: one tile row is one coalesced store of 64 values.
+template <class MASK, class S, class PX, class F>
+PIH_HD void render_strip(const S& sc, const FlyGrid& g, PX* __restrict__ out, size_t row0, int W, int r0, int r1, int tid, const F& pixel) {
+  const int lane = tid & 63, wave = tid >> 6;
+  const int tcols = (W + TILE_COLS - 1) / TILE_COLS, trows = (r1 - r0 + TILE_ROWS - 1) / TILE_ROWS;
+  for (int tile = wave; tile < tcols * trows; tile += RENDER_THREADS / 64) {
+    const int ti = tile / tcols, tj = tile - ti * tcols;
+    const int i0 = r0 + ti * TILE_ROWS, i1 = min(r1, i0 + TILE_ROWS), j0 = tj * TILE_COLS, j1 = min(W, j0 + TILE_COLS);
+    // camera-plane rectangle of the tile's pixel edges (row 0 is the top of the image, v grows upwards)
+    const MASK prims = (MASK)__ballot(prim_on_tile(sc, lane, g.xedge(j0), g.xedge(j1), g.yedge(i1), g.yedge(i0)));
+    const int j = j0 + lane;
+    if (j < j1) {
+      const float xc = g.xc(j);
+      for (int i = i0; i < i1; i++) out[(row0 + (size_t)i) * W + j] = pixel(prims, xc, g.yc(i));
+    }
+  }
+}
+PIH_HD float4 to_float4(const real4& c) { return make_float4(c.x, c.y, c.z, c.w); }
+// the walk in the output format FMT (0: float4 (depth, r, g, b) | PIH_RENDER_OUT_RGBA8: one 32-bit word | PIH_RENDER_OUT_DEPTH: one float):
+// the format picks the pointer type and the pixel function of `px` (Pixels, lit::LitPixels) once, outside the loops
+template <int FMT, class MASK, class S, class P>
+PIH_HD void render_image(const S& sc, const FlyGrid& g, void* __restrict__ out, size_t row0, int W, int r0, int r1, int tid, const P& px) {
+  if constexpr (FMT == PIH_RENDER_OUT_RGBA8)
+    render_strip<MASK>(sc, g, static_cast<unsigned*>(out), row0, W, r0, r1, tid, [&](MASK prims, real xc, real yc) { return px.as_rgba8(prims, xc, yc); });
+  else if constexpr (FMT == PIH_RENDER_OUT_DEPTH)
+    render_strip<MASK>(sc, g, static_cast<float*>(out), row0, W, r0, r1, tid, [&](MASK prims, real xc, real yc) { return px.as_depth(prims, xc, yc); });
+  else
+    render_strip<MASK>(sc, g, static_cast<float4*>(out), row0, W, r0, r1, tid, [&](MASK prims, real xc, real yc) { return to_float4(px.as_float4(prims, xc, yc)); });
+}
+// The scene set-up of a random-fly camera kernel with per-env cameras (every thread of the workgroup calls it; two barriers): threads
+// 0 .. 15 read the env's pose and camera row, thread RCAP tests the camera (camera_or_preset) and leaves the code in cam_bad, `hook` adds
+// the light (NoLight, lit::LightHook), then the scene's two phases.  -> the env gets the background
+template <class Hook>
+PIH_HD bool camera_setup(FlyScene& sc, int& cam_bad, const Hook& hook, const float* __restrict__ state, FlyCam& cam, const float* __restrict__ cam_dev,
+                        int n, int object, int env, int e, int flags, int tid) {
+  if (tid < 16) {
+    const FlyPose ps = load_fly_pose(state, env, n);
+    load_row(cam.w, cam_dev, e);
+    if (tid == RCAP) cam_bad = camera_or_preset(cam, FlyCam{PIH_FLY_CAM_DEFAULT});
+    if (tid == Hook::LIGHT_THREAD) hook.light_thread(all_prims(object));
+    scene_setup_poses(sc, ps, cam, object, flags, tid);
+  }
+  __syncthreads();
+  scene_setup_bounds(sc, object, tid);
+  hook.table(sc, tid);
+  __syncthreads();
+  return cam_bad != CAM_OK || hook.bad();
+}
+// the instance of a kernel template for a call's output format: launch(std::integral_constant<int, FMT>) launches kernel<FMT>
+template <class F> inline void dispatch_fmt(int fmt, F&& launch) {
+  if (fmt == PIH_RENDER_OUT_RGBA8) launch(std::integral_constant<int, PIH_RENDER_OUT_RGBA8>());
+  else if (fmt == PIH_RENDER_OUT_DEPTH) launch(std::integral_constant<int, PIH_RENDER_OUT_DEPTH>());
+  else launch(std::integral_constant<int, 0>());
+}
+#endif
 
 }  // namespace fly
 }  // namespace pih

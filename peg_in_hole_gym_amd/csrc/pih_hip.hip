@@ -231,7 +231,8 @@ __global__ void __launch_bounds__(64) pih_ik_ur5_kernel(Params P, int n, const f
   ik_quad_problem<Ur5Chain>(P, n, 6, q0, tpos, tquat, qout);
 }
 
-// wrist camera (p12): grid = (strips, envs), 256 threads (4 waves); out float[count, H, W, 4] = depth, r, g, b
+// wrist camera (p12): grid = (strips, envs), 256 threads (4 waves); out float[count, H, W, 4] = depth, r, g, b.  The tile walk is the one
+// of every camera kernel (fly::render_strip, pih_fly_render.h) on a grid with the wrist camera's constant tan(fov / 2).
 __global__ void __launch_bounds__(RENDER_THREADS) pih_render_kernel(const float* __restrict__ state, float* __restrict__ out,
                                                                     int env_begin, int W, int H, int rows_per_strip, int flags) {
   __shared__ Shared sh;
@@ -243,68 +244,26 @@ __global__ void __launch_bounds__(RENDER_THREADS) pih_render_kernel(const float*
   for (int i = tid; i < PIH_STATE_WORDS; i += RENDER_THREADS) sh.S[i] = rec[i];
   __syncthreads();
   scene_setup(w, sh, sc, tid);
-  const float T = PIH_CAM_TANH2, sy = 2.0f / H, sx = 2.0f / W;
-  float4* img = reinterpret_cast<float4*>(out) + (size_t)e * H * W;
-  constexpr int TR = 16, TC = 64;                   // tile = 16 rows x 64 columns, one row of a tile per wave instruction
-  const int lane = tid & 63, wave = tid >> 6;
-  const int tcols = (W + TC - 1) / TC, trows = (r1 - r0 + TR - 1) / TR;
-  for (int tile = wave; tile < tcols * trows; tile += RENDER_THREADS / 64) {
-    const int ti = tile / tcols, tj = tile - ti * tcols;
-    const int i0 = r0 + ti * TR, i1 = min(r1, i0 + TR), j0 = tj * TC, j1 = min(W, j0 + TC);
-    // camera-plane rectangle of the tile's pixel edges (row 0 is the top of the image, v grows upwards)
-    const float tu0 = (sx * j0 - 1.0f) * T, tu1 = (sx * j1 - 1.0f) * T, tv0 = (1.0f - sy * i1) * T, tv1 = (1.0f - sy * i0) * T;
-    const unsigned prims = (unsigned)__ballot(prim_on_tile(sc, lane, tu0, tu1, tv0, tv1));
-    const int j = j0 + lane;
-    if (j < j1) {
-      const float xc = (sx * (j + 0.5f) - 1.0f) * T;
-      for (int i = i0; i < i1; i++) {
-        real4 c = shade(sc, prims, xc, (1.0f - sy * (i + 0.5f)) * T, flags);
-        img[i * W + j] = make_float4(c.x, c.y, c.z, c.w);
-      }
-    }
-  }
+  static_assert(fly::TILE_ROWS == 16 && fly::TILE_COLS == 64, "the tile of pih_render.h's mapping: 16 rows x 64 columns, one row of a tile per wave instruction");
+  fly::render_strip<unsigned>(sc, fly::FlyGrid(PIH_CAM_TANH2, PIH_CAM_TANH2, W, H), reinterpret_cast<float4*>(out), (size_t)e * H, W, r0, r1, tid,
+                              [&](unsigned prims, real xc, real yc) { return fly::to_float4(shade(sc, prims, xc, yc, flags)); });
 }
 
 // free camera of the random-fly task (pih_fly_render.h): grid = (strips, envs), 256 threads (4 waves); out float[count, H, W, 4] = depth,
-// r, g, b.  state is structure-of-arrays: the 13 words the scene needs are wave-uniform (scalar) loads.
+// r, g, b.  state is structure-of-arrays: the 13 words the scene needs are wave-uniform (scalar) loads (load_fly_pose).  One host camera,
+// validated by pih_render_cam: no camera test here (pih_fly_image_kernel has it); the tile walk is render_strip.
 __global__ void __launch_bounds__(RENDER_THREADS) pih_fly_render_kernel(const float* __restrict__ state, float* __restrict__ out, fly::FlyCam cam,
                                                                         int n, int object, int env_begin, int W, int H, int rows_per_strip, int flags) {
   using namespace fly;
   __shared__ FlyScene sc;
   const int tid = threadIdx.x, e = blockIdx.y, env = env_begin + e;
   const int r0 = blockIdx.x * rows_per_strip, r1 = min(H, r0 + rows_per_strip);
-  if (tid < 16) {
-    FlyPose ps;
-    const float* rec = state + env;
-#pragma unroll
-    for (int i = 0; i < 6; i++) ps.q[i] = rec[(size_t)(PIH_F_Q + i) * n];
-#pragma unroll
-    for (int i = 0; i < 3; i++) ps.opos[i] = rec[(size_t)(PIH_F_OPOS + i) * n];
-#pragma unroll
-    for (int i = 0; i < 4; i++) ps.oquat[i] = rec[(size_t)(PIH_F_OQUAT + i) * n];
-    scene_setup_poses(sc, ps, cam, object, flags, tid);
-  }
+  if (tid < 16) scene_setup_poses(sc, load_fly_pose(state, env, n), cam, object, flags, tid);
   __syncthreads();
   scene_setup_bounds(sc, object, tid);
   __syncthreads();
-  const FlyGrid g(sc, W, H);
-  float4* img = reinterpret_cast<float4*>(out) + (size_t)e * H * W;
-  const int lane = tid & 63, wave = tid >> 6;
-  const int tcols = (W + TILE_COLS - 1) / TILE_COLS, trows = (r1 - r0 + TILE_ROWS - 1) / TILE_ROWS;
-  for (int tile = wave; tile < tcols * trows; tile += RENDER_THREADS / 64) {
-    const int ti = tile / tcols, tj = tile - ti * tcols;
-    const int i0 = r0 + ti * TILE_ROWS, i1 = min(r1, i0 + TILE_ROWS), j0 = tj * TILE_COLS, j1 = min(W, j0 + TILE_COLS);
-    // camera-plane rectangle of the tile's pixel edges (row 0 is the top of the image, v grows upwards)
-    const unsigned prims = (unsigned)__ballot(prim_on_tile(sc, lane, g.xedge(j0), g.xedge(j1), g.yedge(i1), g.yedge(i0)));
-    const int j = j0 + lane;
-    if (j < j1) {
-      const float xc = g.xc(j);
-      for (int i = i0; i < i1; i++) {
-        real4 c = shade(sc, prims, xc, g.yc(i), flags);
-        img[(size_t)i * W + j] = make_float4(c.x, c.y, c.z, c.w);
-      }
-    }
-  }
+  render_strip<unsigned>(sc, FlyGrid(sc, W, H), reinterpret_cast<float4*>(out), (size_t)e * H, W, r0, r1, tid,
+                         [&](unsigned prims, real xc, real yc) { return to_float4(shade(sc, prims, xc, yc, flags)); });
 }
 
 // label images: grid = (ceil(S*S/256), envs); out[e][k][y][x], image index [cc][rr] of the reference = [x-like c][r]
@@ -884,45 +843,78 @@ int pih_render(pih_handle* h, float* out_dev, int width, int height, int env_beg
   return pih_render_ex(h, out_dev, width, height, env_begin, env_count, 0, stream);
 }
 
-int pih_render_ex(pih_handle* h, float* out_dev, int width, int height, int env_begin, int env_count, int flags, void* stream) {
-  if (!h || !out_dev || width <= 0 || height <= 0 || env_begin < 0 || env_count <= 0 || env_begin + env_count > h->cfg.n_envs) {
-    if (h) h->err = "pih_render: bad arguments";
-    return -2;
+// ---- what the camera entry points check, each piece once; an entry point calls them in ITS order (which of two simultaneous faults is
+// reported is part of its behaviour: tests/test_gpu_render_errors.py).  Each returns 0, or -2 with the handle's error text set.
+struct RenderCall {      // the arguments every camera entry point takes
+  pih_handle* h; const char* name; const void* out; int width, height, env_begin, env_count;
+  int fail(const std::string& what) const { h->err = std::string(name) + ": " + what; return -2; }
+  // handle, out, sizes, env range (`also`: what else an entry point files under "bad arguments")
+  int bad_arguments(bool also = false) const {
+    if (h && out && width > 0 && height > 0 && env_begin >= 0 && env_count > 0 && env_begin + env_count <= h->cfg.n_envs && !also) return 0;
+    return h ? fail("bad arguments") : -2;
   }
-  if (h->fly) { h->err = "pih_render: the wrist camera belongs to the peg-in-hole task"; return -2; }
-  if ((reinterpret_cast<uintptr_t>(out_dev) & 15) != 0) { h->err = "pih_render: out_dev must be 16-byte aligned"; return -2; }
+  int misaligned() const { return (reinterpret_cast<uintptr_t>(out) & 15) != 0 ? fail("out_dev must be 16-byte aligned") : 0; }
+  int too_many() const { return env_count > 65535 ? fail("env_count > 65535 per call") : 0; }
+  // unknown bits, both output formats, both camera frames, a device flag without its array (`preset`: what NULL would have meant)
+  int bad_flags(int flags, int known, const char* preset, const void* cam_ptr, const void* light_ptr = nullptr) const {
+    if ((flags & ~known) != 0) return fail("unknown flag");
+    if ((flags & PIH_RENDER_OUT_RGBA8) && (flags & PIH_RENDER_OUT_DEPTH)) return fail("PIH_RENDER_OUT_RGBA8 and PIH_RENDER_OUT_DEPTH exclude each other");
+    if ((flags & PIH_RENDER_CAM_EE) && (flags & PIH_RENDER_CAM_EE_POS)) return fail("PIH_RENDER_CAM_EE and PIH_RENDER_CAM_EE_POS exclude each other");
+    if ((flags & PIH_RENDER_CAM_DEVICE) && !cam_ptr) return fail(std::string("PIH_RENDER_CAM_DEVICE needs a camera array (NULL = ") + preset + " is for a host camera)");
+    if ((flags & PIH_RENDER_LIGHT_DEVICE) && !light_ptr) return fail("PIH_RENDER_LIGHT_DEVICE needs a light array (NULL = PIH_LIGHT_DEFAULT is for a host light)");
+    return 0;
+  }
+  // The camera the kernel gets by value: the caller's host camera, tested here, or `cam` as it comes in (the task's preset) for NULL and
+  // for per-env cameras in device memory, which the kernel tests.  name_word: say which word is not finite (pih_render_cam does not).
+  // wrist_flags != nullptr: NULL means the peg-in-hole wrist preset, which is in the PIH_RENDER_CAM_EE_POS frame whatever flag was passed.
+  int host_camera(fly::FlyCam& cam, const float* cam_ptr, int flags, bool name_word, int* wrist_flags) const {
+    if (flags & PIH_RENDER_CAM_DEVICE) return 0;
+    if (cam_ptr) memcpy(cam.w, cam_ptr, sizeof cam.w);
+    else if (wrist_flags) *wrist_flags = (flags & ~PIH_RENDER_CAM_EE) | PIH_RENDER_CAM_EE_POS;
+    static const char* const what[] = {nullptr, "eye == target (or not finite)", "up is zero or parallel to the view axis target - eye", "fov outside (0, 180) degrees",
+                                       "aspect <= 0", "near <= 0", "far <= near"};
+    if (name_word) {
+      // (a NaN or an infinity is looked for in the words' bits, as integers: the library's floating-point code is built with -ffast-math)
+      static const char* const word[] = {"eye", "eye", "eye", "target", "target", "target", "up", "up", "up", "fov", "aspect", "near", "far"};
+      uint32_t bits[PIH_CAM_WORDS]; memcpy(bits, cam.w, sizeof bits);
+      for (int i = 0; i < PIH_CAM_WORDS; i++)
+        if ((bits[i] & 0x7f800000u) == 0x7f800000u) return fail(std::string("degenerate camera: ") + word[i] + " is not finite");
+    }
+    const int code = fly::cam_degenerate(cam.w);
+    return code != fly::CAM_OK ? fail(std::string("degenerate camera: ") + what[code]) : 0;
+  }
+};
+#define PIH_RENDER_CHECK(x) do { if (const int _rc = (x)) return _rc; } while (0)
+static const int RENDER_FMT = PIH_RENDER_OUT_RGBA8 | PIH_RENDER_OUT_DEPTH;
+static const int RENDER_CAM_FLAGS = PIH_RENDER_SHADED | PIH_RENDER_CAM_EE | RENDER_FMT | PIH_RENDER_CAM_DEVICE;      // what pih_render_cam knows
+
+int pih_render_ex(pih_handle* h, float* out_dev, int width, int height, int env_begin, int env_count, int flags, void* stream) {
+  const RenderCall c = {h, "pih_render", out_dev, width, height, env_begin, env_count};
+  PIH_RENDER_CHECK(c.bad_arguments());
+  if (h->fly) return c.fail("the wrist camera belongs to the peg-in-hole task");
+  PIH_RENDER_CHECK(c.misaligned());
   // (the output formats and the device cameras of pih_render_cam do not exist here: out_dev is float[count, H, W, 4] whatever the flags say)
   if ((flags & ~PIH_RENDER_SHADED) != 0) { h->err = "pih_render_ex: unknown flag (the wrist camera takes PIH_RENDER_SHADED only)"; return -2; }
   PIH_ENTER(h);
   int rows; const int strips = render_strips(height, env_count, &rows);
-  if (env_count > 65535) { h->err = "pih_render: env_count > 65535 per call"; return -2; }
+  PIH_RENDER_CHECK(c.too_many());
   hipLaunchKernelGGL(pih_render_kernel, dim3(strips, env_count), dim3(RENDER_THREADS), 0, (hipStream_t)stream, h->state, out_dev, env_begin, width, height, rows, flags);
   HIPCHK(h, hipGetLastError());
   return 0;
 }
 
 int pih_render_cam(pih_handle* h, float* out_dev, const float* cam_ptr, int width, int height, int env_begin, int env_count, int flags, void* stream) {
-  const int fmt = flags & (PIH_RENDER_OUT_RGBA8 | PIH_RENDER_OUT_DEPTH);
-  const bool cam_on_device = (flags & PIH_RENDER_CAM_DEVICE) != 0;
-  if (!h || !out_dev || width <= 0 || height <= 0 || env_begin < 0 || env_count <= 0 || env_begin + env_count > h->cfg.n_envs ||
-      (flags & ~(PIH_RENDER_SHADED | PIH_RENDER_CAM_EE | PIH_RENDER_OUT_RGBA8 | PIH_RENDER_OUT_DEPTH | PIH_RENDER_CAM_DEVICE)) != 0) {
-    if (h) h->err = "pih_render_cam: bad arguments";
-    return -2;
-  }
-  if (!h->fly) { h->err = "pih_render_cam: the free camera belongs to the random-fly task (peg-in-hole: pih_render / pih_render_ex)"; return -2; }
-  if (fmt == (PIH_RENDER_OUT_RGBA8 | PIH_RENDER_OUT_DEPTH)) { h->err = "pih_render_cam: PIH_RENDER_OUT_RGBA8 and PIH_RENDER_OUT_DEPTH exclude each other"; return -2; }
-  if (cam_on_device && !cam_ptr) { h->err = "pih_render_cam: PIH_RENDER_CAM_DEVICE needs a camera array (NULL = default is for a host camera)"; return -2; }
-  if ((reinterpret_cast<uintptr_t>(out_dev) & 15) != 0) { h->err = "pih_render_cam: out_dev must be 16-byte aligned"; return -2; }
-  if (env_count > 65535) { h->err = "pih_render_cam: env_count > 65535 per call"; return -2; }
+  const RenderCall c = {h, "pih_render_cam", out_dev, width, height, env_begin, env_count};
+  PIH_RENDER_CHECK(c.bad_arguments((flags & ~RENDER_CAM_FLAGS) != 0));      // (an unknown flag is "bad arguments" here)
+  if (!h->fly) return c.fail("the free camera belongs to the random-fly task (peg-in-hole: pih_render / pih_render_ex)");
+  PIH_RENDER_CHECK(c.bad_flags(flags, RENDER_CAM_FLAGS, "default", cam_ptr));
+  PIH_RENDER_CHECK(c.misaligned());
+  PIH_RENDER_CHECK(c.too_many());
   fly::FlyCam cam = {PIH_FLY_CAM_DEFAULT};
-  if (!cam_on_device) {
-    if (cam_ptr) memcpy(cam.w, cam_ptr, sizeof cam.w);
-    static const char* const what[] = {nullptr, "eye == target (or not finite)", "up is zero or parallel to the view axis target - eye", "fov outside (0, 180) degrees",
-                                       "aspect <= 0", "near <= 0", "far <= near"};
-    const int code = fly::cam_degenerate(cam.w);
-    if (code != fly::CAM_OK) { h->err = std::string("pih_render_cam: degenerate camera: ") + what[code]; return -2; }
-  }
+  PIH_RENDER_CHECK(c.host_camera(cam, cam_ptr, flags, false, nullptr));
   PIH_ENTER(h);
+  const int fmt = flags & RENDER_FMT;
+  const bool cam_on_device = (flags & PIH_RENDER_CAM_DEVICE) != 0;
   int rows; const int strips = render_strips(height, env_count, &rows);
   if (fmt || cam_on_device)
     fly_image_launch(fmt, dim3(strips, env_count), (hipStream_t)stream, h->state, out_dev, cam, cam_on_device ? cam_ptr : nullptr, h->cfg.n_envs, h->P.object, env_begin, width, height, rows, flags);
@@ -934,83 +926,42 @@ int pih_render_cam(pih_handle* h, float* out_dev, const float* cam_ptr, int widt
 }
 
 int pih_render_view(pih_handle* h, void* out_dev, const float* cam_ptr, int width, int height, int env_begin, int env_count, int flags, void* stream) {
-  const int fmt = flags & (PIH_RENDER_OUT_RGBA8 | PIH_RENDER_OUT_DEPTH);
-  const bool cam_on_device = (flags & PIH_RENDER_CAM_DEVICE) != 0;
-  if (!h || !out_dev || width <= 0 || height <= 0 || env_begin < 0 || env_count <= 0 || env_begin + env_count > h->cfg.n_envs) {
-    if (h) h->err = "pih_render_view: bad arguments";
-    return -2;
-  }
-  if (h->fly) { h->err = "pih_render_view: this camera belongs to the peg-in-hole task (random-fly: pih_render_cam)"; return -2; }
-  if ((flags & ~(PIH_RENDER_SHADED | PIH_RENDER_CAM_EE | PIH_RENDER_CAM_EE_POS | PIH_RENDER_OUT_RGBA8 | PIH_RENDER_OUT_DEPTH | PIH_RENDER_CAM_DEVICE)) != 0) {
-    h->err = "pih_render_view: unknown flag"; return -2;
-  }
-  if (fmt == (PIH_RENDER_OUT_RGBA8 | PIH_RENDER_OUT_DEPTH)) { h->err = "pih_render_view: PIH_RENDER_OUT_RGBA8 and PIH_RENDER_OUT_DEPTH exclude each other"; return -2; }
-  if ((flags & PIH_RENDER_CAM_EE) && (flags & PIH_RENDER_CAM_EE_POS)) { h->err = "pih_render_view: PIH_RENDER_CAM_EE and PIH_RENDER_CAM_EE_POS exclude each other"; return -2; }
-  if (cam_on_device && !cam_ptr) { h->err = "pih_render_view: PIH_RENDER_CAM_DEVICE needs a camera array (NULL = the wrist preset is for a host camera)"; return -2; }
-  if ((reinterpret_cast<uintptr_t>(out_dev) & 15) != 0) { h->err = "pih_render_view: out_dev must be 16-byte aligned"; return -2; }
-  if (env_count > 65535) { h->err = "pih_render_view: env_count > 65535 per call"; return -2; }
+  const RenderCall c = {h, "pih_render_view", out_dev, width, height, env_begin, env_count};
+  PIH_RENDER_CHECK(c.bad_arguments());
+  if (h->fly) return c.fail("this camera belongs to the peg-in-hole task (random-fly: pih_render_cam)");
+  PIH_RENDER_CHECK(c.bad_flags(flags, RENDER_CAM_FLAGS | PIH_RENDER_CAM_EE_POS, "the wrist preset", cam_ptr));
+  PIH_RENDER_CHECK(c.misaligned());
+  PIH_RENDER_CHECK(c.too_many());
   fly::FlyCam cam = {PIH_VIEW_CAM_WRIST};
-  if (!cam_on_device) {
-    if (cam_ptr) memcpy(cam.w, cam_ptr, sizeof cam.w);
-    else flags = (flags & ~PIH_RENDER_CAM_EE) | PIH_RENDER_CAM_EE_POS;      // the wrist preset, whatever frame flag was passed
-    static const char* const what[] = {nullptr, "eye == target (or not finite)", "up is zero or parallel to the view axis target - eye", "fov outside (0, 180) degrees",
-                                       "aspect <= 0", "near <= 0", "far <= near"};
-    // (a NaN or an infinity is looked for in the words' bits, as integers: the library's floating-point code is built with -ffast-math)
-    static const char* const word[] = {"eye", "eye", "eye", "target", "target", "target", "up", "up", "up", "fov", "aspect", "near", "far"};
-    uint32_t bits[PIH_CAM_WORDS]; memcpy(bits, cam.w, sizeof bits);
-    for (int i = 0; i < PIH_CAM_WORDS; i++)
-      if ((bits[i] & 0x7f800000u) == 0x7f800000u) { h->err = std::string("pih_render_view: degenerate camera: ") + word[i] + " is not finite"; return -2; }
-    const int code = fly::cam_degenerate(cam.w);
-    if (code != fly::CAM_OK) { h->err = std::string("pih_render_view: degenerate camera: ") + what[code]; return -2; }
-  }
+  PIH_RENDER_CHECK(c.host_camera(cam, cam_ptr, flags, true, &flags));
   PIH_ENTER(h);
   int rows; const int strips = render_strips(height, env_count, &rows);
-  view_launch(fmt, dim3(strips, env_count), (hipStream_t)stream, h->state, out_dev, cam, cam_on_device ? cam_ptr : nullptr, env_begin, width, height, rows, flags);
+  view_launch(flags & RENDER_FMT, dim3(strips, env_count), (hipStream_t)stream, h->state, out_dev, cam, (flags & PIH_RENDER_CAM_DEVICE) ? cam_ptr : nullptr, env_begin, width, height, rows, flags);
   HIPCHK(h, hipGetLastError());
   return 0;
 }
 
 int pih_render_lit(pih_handle* h, void* out_dev, const float* cam_ptr, const float* light_ptr, int width, int height, int env_begin, int env_count, int flags, void* stream) {
-  const int fmt = flags & (PIH_RENDER_OUT_RGBA8 | PIH_RENDER_OUT_DEPTH);
-  const bool cam_on_device = (flags & PIH_RENDER_CAM_DEVICE) != 0, light_on_device = (flags & PIH_RENDER_LIGHT_DEVICE) != 0;
-  if (!h || !out_dev || width <= 0 || height <= 0 || env_begin < 0 || env_count <= 0 || env_begin + env_count > h->cfg.n_envs) {
-    if (h) h->err = "pih_render_lit: bad arguments";
-    return -2;
-  }
+  const RenderCall c = {h, "pih_render_lit", out_dev, width, height, env_begin, env_count};
+  PIH_RENDER_CHECK(c.bad_arguments());
   // the flags of the handle's free camera (pih_render_cam / pih_render_view), plus the device light
-  const int known = PIH_RENDER_SHADED | PIH_RENDER_CAM_EE | PIH_RENDER_OUT_RGBA8 | PIH_RENDER_OUT_DEPTH | PIH_RENDER_CAM_DEVICE | PIH_RENDER_LIGHT_DEVICE | (h->fly ? 0 : PIH_RENDER_CAM_EE_POS);
-  if ((flags & ~known) != 0) { h->err = "pih_render_lit: unknown flag"; return -2; }
-  if (fmt == (PIH_RENDER_OUT_RGBA8 | PIH_RENDER_OUT_DEPTH)) { h->err = "pih_render_lit: PIH_RENDER_OUT_RGBA8 and PIH_RENDER_OUT_DEPTH exclude each other"; return -2; }
-  if ((flags & PIH_RENDER_CAM_EE) && (flags & PIH_RENDER_CAM_EE_POS)) { h->err = "pih_render_lit: PIH_RENDER_CAM_EE and PIH_RENDER_CAM_EE_POS exclude each other"; return -2; }
-  if (cam_on_device && !cam_ptr) { h->err = "pih_render_lit: PIH_RENDER_CAM_DEVICE needs a camera array (NULL = the preset is for a host camera)"; return -2; }
-  if (light_on_device && !light_ptr) { h->err = "pih_render_lit: PIH_RENDER_LIGHT_DEVICE needs a light array (NULL = PIH_LIGHT_DEFAULT is for a host light)"; return -2; }
-  if ((reinterpret_cast<uintptr_t>(out_dev) & 15) != 0) { h->err = "pih_render_lit: out_dev must be 16-byte aligned"; return -2; }
-  if (env_count > 65535) { h->err = "pih_render_lit: env_count > 65535 per call"; return -2; }
+  PIH_RENDER_CHECK(c.bad_flags(flags, RENDER_CAM_FLAGS | PIH_RENDER_LIGHT_DEVICE | (h->fly ? 0 : PIH_RENDER_CAM_EE_POS), "the preset", cam_ptr, light_ptr));
+  PIH_RENDER_CHECK(c.misaligned());
+  PIH_RENDER_CHECK(c.too_many());
   fly::FlyCam cam = {PIH_FLY_CAM_DEFAULT};
   if (!h->fly) cam = fly::FlyCam{PIH_VIEW_CAM_WRIST};
-  if (!cam_on_device) {
-    if (cam_ptr) memcpy(cam.w, cam_ptr, sizeof cam.w);
-    else if (!h->fly) flags = (flags & ~PIH_RENDER_CAM_EE) | PIH_RENDER_CAM_EE_POS;      // the wrist preset, whatever frame flag was passed
-    static const char* const what[] = {nullptr, "eye == target (or not finite)", "up is zero or parallel to the view axis target - eye", "fov outside (0, 180) degrees",
-                                       "aspect <= 0", "near <= 0", "far <= near"};
-    // (a NaN or an infinity is looked for in the words' bits, as integers, as pih_render_view does: this code is built with -ffast-math)
-    static const char* const word[] = {"eye", "eye", "eye", "target", "target", "target", "up", "up", "up", "fov", "aspect", "near", "far"};
-    uint32_t bits[PIH_CAM_WORDS]; memcpy(bits, cam.w, sizeof bits);
-    for (int i = 0; i < PIH_CAM_WORDS; i++)
-      if ((bits[i] & 0x7f800000u) == 0x7f800000u) { h->err = std::string("pih_render_lit: degenerate camera: ") + word[i] + " is not finite"; return -2; }
-    const int code = fly::cam_degenerate(cam.w);
-    if (code != fly::CAM_OK) { h->err = std::string("pih_render_lit: degenerate camera: ") + what[code]; return -2; }
-  }
+  PIH_RENDER_CHECK(c.host_camera(cam, cam_ptr, flags, true, h->fly ? nullptr : &flags));
+  const bool light_on_device = (flags & PIH_RENDER_LIGHT_DEVICE) != 0;
   float light[PIH_LIGHT_WORDS] = PIH_LIGHT_DEFAULT;
   if (!light_on_device) {
     if (light_ptr) memcpy(light, light_ptr, sizeof light);
     const char* what = nullptr;
-    if (lit_light_check(light, &what) != 0) { h->err = std::string("pih_render_lit: degenerate light: ") + what; return -2; }
+    if (lit_light_check(light, &what) != 0) return c.fail(std::string("degenerate light: ") + what);
   }
   PIH_ENTER(h);
   int rows; const int strips = render_strips(height, env_count, &rows);
-  lit_launch(h->fly, fmt, dim3(strips, env_count), (hipStream_t)stream, h->state, out_dev, cam, cam_on_device ? cam_ptr : nullptr, light, light_on_device ? light_ptr : nullptr,
-             h->cfg.n_envs, h->P.object, env_begin, width, height, rows, flags);
+  lit_launch(h->fly, flags & RENDER_FMT, dim3(strips, env_count), (hipStream_t)stream, h->state, out_dev, cam, (flags & PIH_RENDER_CAM_DEVICE) ? cam_ptr : nullptr, light,
+             light_on_device ? light_ptr : nullptr, h->cfg.n_envs, h->P.object, env_begin, width, height, rows, flags);
   HIPCHK(h, hipGetLastError());
   return 0;
 }

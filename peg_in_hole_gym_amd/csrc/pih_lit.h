@@ -363,5 +363,27 @@ PIH_HD real pixel_depth(const ViewScene& sc, unsigned long long prims, real xc, 
   return bad ? (real)1 : depth_value(sc, trace_hit(sc, prims, xc, yc));
 }
 
+// ------------------------------------------------------------------------------------------------ both tasks
+// the three formats of one lit pixel, as fly::render_image takes them (`cull`: use the light-space table)
+template <class S, class L, class MASK> struct LitPixels {
+  const S& sc; const L& le; bool cull, bad;
+  PIH_HD unsigned as_rgba8(MASK prims, real xc, real yc) const { return pixel_rgba8(sc, le, prims, xc, yc, cull, bad); }
+  PIH_HD real as_depth(MASK prims, real xc, real yc) const { return lit::pixel_depth(sc, prims, xc, yc, bad); }      // (not view::pixel_depth)
+  PIH_HD real4 as_float4(MASK prims, real xc, real yc) const { return pixel_float4(sc, le, prims, xc, yc, cull, bad); }
+};
+// what a lit kernel hooks into its task's camera_setup (fly::NoLight is the unlit kernels'): thread 14 of the workgroup reads the env's row
+// of per-env lights, if there are any, and sets the light up (light_setup tests it); the threads that compute the screen bounds then fill
+// the light-space table; a degenerate light gives the env the background
+template <class L> struct LightHook {
+  L& le; LightWords& light; const float* light_dev; int e;
+  static constexpr int LIGHT_THREAD = 14;
+  PIH_HD void light_thread(unsigned long long occluders /* the mask of the scene's primitives */) const {
+    fly::load_row(light.w, reinterpret_cast<const unsigned*>(light_dev), e);      // (as integers: see LightWords)
+    light_setup(le, light, occluders);
+  }
+  template <class S> PIH_HD void table(const S& sc, int tid) const { light_table(sc, le, tid); }
+  PIH_HD bool bad() const { return le.bad != LIGHT_OK; }
+};
+
 }  // namespace lit
 }  // namespace pih

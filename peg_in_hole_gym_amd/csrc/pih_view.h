@@ -267,5 +267,33 @@ PIH_HD real pixel_depth(const ViewScene& sc, unsigned long long prims, real xc, 
   return bad ? (real)1 : shade_hit(sc, prims, xc, yc, 0, hit).x;
 }
 
+#ifndef PIH_PLATFORM_DEFINED      // ---------------------------------------------------------------- device only
+// The scene set-up of a peg-in-hole free-camera kernel (every thread of the workgroup calls it; four barriers): the env's state record
+// goes to LDS, fk_all runs once per workgroup, thread 15 reads the env's camera row and tests the camera (fly::camera_or_preset with the
+// wrist preset) and leaves the code in cam_bad, `hook` adds a light (fly::NoLight: none), then the scene's two phases.
+// -> the env gets the background
+template <class Hook>
+PIH_HD bool camera_setup(Shared& sh, ViewScene& sc, int& cam_bad, const Hook& hook, const float* __restrict__ state, FlyCam& cam,
+                         const float* __restrict__ cam_dev, int env, int e, int& flags, int tid) {
+  Wave w; w.l = tid; w.counter = 0;
+  const float* rec = state + (size_t)env * PIH_STATE_WORDS;
+  for (int i = tid; i < PIH_STATE_WORDS; i += RENDER_THREADS) sh.S[i] = rec[i];
+  __syncthreads();
+  fk_all(w, sh);
+  __syncthreads();
+  if (tid == 15) {
+    fly::load_row(cam.w, cam_dev, e);
+    cam_bad = fly::camera_or_preset(cam, FlyCam{PIH_VIEW_CAM_WRIST}, &flags);
+  }
+  if (tid == Hook::LIGHT_THREAD) hook.light_thread(all_prims());
+  scene_setup_poses(sh, sc, cam, flags, tid);
+  __syncthreads();
+  scene_setup_bounds(sc, tid);
+  hook.table(sc, tid);
+  __syncthreads();
+  return cam_bad != fly::CAM_OK || hook.bad();
+}
+#endif
+
 }  // namespace view
 }  // namespace pih

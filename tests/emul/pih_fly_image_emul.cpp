@@ -1,12 +1,14 @@
 // TEST-ONLY: host build of the packed output formats and the camera test of the random-fly camera (peg_in_hole_gym_amd/csrc/
 // pih_fly_render.h: pixel_rgba8, pixel_depth, pack_byte, seg_of_kind, cam_degenerate), real = PIH_REAL (double or float).
 // Renders ONE env's state record the way pih_fly_image_kernel (pih_fly_image.hip) does: the camera is tested first, a degenerate one is
-// replaced by the default camera and gives the background; then the product's per-pixel code over the product's 16 x 64 tiling, with
+// replaced by the default camera and gives the background (camera_or_preset); then the product's per-pixel code over the product's 16 x 64
+// tiling (pih_host_tiles.h), with
 // every primitive on for every tile (cull = 0) or with the tile lists of the product's screen-bound test (cull = 1).
 // tests/test_fly_image.py compiles it into a temporary directory (this file is not part of the Makefile's libraries).
 #include "pih_host_platform.h"
 #include "../../peg_in_hole_gym_amd/csrc/pih_common.h"
 #include "../../peg_in_hole_gym_amd/csrc/pih_fly_render.h"
+#include "pih_host_tiles.h"
 
 using namespace pih;
 using namespace pih::fly;
@@ -25,36 +27,13 @@ int pihfi_render(const double* rec, const float* cam_words, int object, int W, i
   if (!rec || !cam_words || W <= 0 || H <= 0 || object < 0 || object >= PIH_FLY_NOBJ) return -2;
   FlyCam cam;
   for (int i = 0; i < PIH_CAM_WORDS; i++) cam.w[i] = cam_words[i];
-  const int code = cam_degenerate(cam.w);
-  if (code != CAM_OK) cam = FlyCam{PIH_FLY_CAM_DEFAULT};
-  const bool bad = code != CAM_OK;
-  FlyPose ps;
-  for (int i = 0; i < RCAP; i++) ps.q[i] = (real)rec[PIH_F_Q + i];
-  for (int i = 0; i < 3; i++) ps.opos[i] = (real)rec[PIH_F_OPOS + i];
-  for (int i = 0; i < 4; i++) ps.oquat[i] = (real)rec[PIH_F_OQUAT + i];
+  const int code = camera_or_preset(cam, FlyCam{PIH_FLY_CAM_DEFAULT});
+  const FlyPose ps = load_fly_pose(rec, 0, 1);
   FlyScene sc;
   for (int tid = 0; tid < 16; tid++) scene_setup_poses(sc, ps, cam, object, flags, tid);
   for (int tid = 0; tid < RENDER_THREADS; tid++) scene_setup_bounds(sc, object, tid);
-  const FlyGrid g(sc, W, H);
-  for (int i0 = 0; i0 < H; i0 += TILE_ROWS)
-    for (int j0 = 0; j0 < W; j0 += TILE_COLS) {
-      const int i1 = i0 + TILE_ROWS < H ? i0 + TILE_ROWS : H, j1 = j0 + TILE_COLS < W ? j0 + TILE_COLS : W;
-      unsigned prims = all_prims(object);
-      if (cull) {
-        prims = 0;
-        for (int lane = 0; lane < 32; lane++)
-          if (prim_on_tile(sc, lane, g.xedge(j0), g.xedge(j1), g.yedge(i1), g.yedge(i0))) prims |= 1u << lane;
-      }
-      for (int i = i0; i < i1; i++)
-        for (int j = j0; j < j1; j++) {
-          const size_t px = (size_t)i * W + j;
-          if (rgba) {
-            const unsigned v = pixel_rgba8(sc, prims, g.xc(j), g.yc(i), flags, bad);
-            for (int k = 0; k < 4; k++) rgba[4 * px + k] = (unsigned char)((v >> (8 * k)) & 255u);
-          }
-          if (depth) depth[px] = (double)pixel_depth(sc, prims, g.xc(j), g.yc(i), bad);
-        }
-    }
+  const Pixels<FlyScene, unsigned> p = {sc, flags, code != CAM_OK};
+  host_tiles(sc, W, H, cull, all_prims(object), [&](unsigned prims, real xc, real yc, size_t px) { host_store(p, prims, xc, yc, px, nullptr, rgba, depth); });
   return code;
 }
 

@@ -1,12 +1,13 @@
 // TEST-ONLY: host build of the lit camera images of both tasks (peg_in_hole_gym_amd/csrc/pih_lit.h), real = PIH_REAL (double or float).
 // Renders ONE env's state record the way pih_lit_view_kernel / pih_lit_fly_kernel (pih_lit.hip) do: camera and light are tested first, a
 // degenerate one is replaced by its default and gives the background; then the product's per-scene and per-pixel code over the product's
-// 16 x 64 tiling, with the tile lists of the product's screen-bound test, and with the light-space table of the shadow ray on (lcull = 1)
+// 16 x 64 tiling (pih_host_tiles.h), with the tile lists of the product's screen-bound test, and with the light-space table of the shadow ray on (lcull = 1)
 // or off (lcull = 0: every occluder is intersected).
 // tests/test_render_lit.py compiles it into a temporary directory (this file is not part of the Makefile's libraries).
 #include "pih_host_platform.h"
 #include "pih_wave_host.h"
 #include "../../peg_in_hole_gym_amd/csrc/pih_lit.h"
+#include "pih_host_tiles.h"
 
 using namespace pih;
 
@@ -30,8 +31,7 @@ int pihl_view_render(const double* rec, const float* cam_words, const float* lig
   if (!rec || !cam_words || !light_words || W <= 0 || H <= 0) return -2;
   FlyCam cam;
   for (int i = 0; i < PIH_CAM_WORDS; i++) cam.w[i] = cam_words[i];
-  const int code = fly::cam_degenerate(cam.w);
-  if (code != fly::CAM_OK) { cam = FlyCam{PIH_VIEW_CAM_WRIST}; flags = (flags & ~PIH_RENDER_CAM_EE) | PIH_RENDER_CAM_EE_POS; }
+  const int code = fly::camera_or_preset(cam, FlyCam{PIH_VIEW_CAM_WRIST}, &flags);
   const lit::LightWords lw = lit::light_words(light_words);
   static Shared sh;
   static Wave w;
@@ -43,29 +43,8 @@ int pihl_view_render(const double* rec, const float* cam_words, const float* lig
   lit::light_setup(le, lw, all_prims());
   for (int tid = 0; tid < RENDER_THREADS; tid++) scene_setup_poses(sh, sc, cam, flags, tid);
   for (int tid = 0; tid < RENDER_THREADS; tid++) { scene_setup_bounds(sc, tid); lit::light_table(sc, le, tid); }
-  const bool bad = code != fly::CAM_OK || le.bad != lit::LIGHT_OK;
-  const FlyGrid g(sc, W, H);
-  for (int i0 = 0; i0 < H; i0 += TILE_ROWS)
-    for (int j0 = 0; j0 < W; j0 += TILE_COLS) {
-      const int i1 = i0 + TILE_ROWS < H ? i0 + TILE_ROWS : H, j1 = j0 + TILE_COLS < W ? j0 + TILE_COLS : W;
-      unsigned long long prims = 0;
-      for (int lane = 0; lane < 64; lane++)
-        if (prim_on_tile(sc, lane, g.xedge(j0), g.xedge(j1), g.yedge(i1), g.yedge(i0))) prims |= 1ull << lane;
-      for (int i = i0; i < i1; i++)
-        for (int j = j0; j < j1; j++) {
-          const size_t px = (size_t)i * W + j;
-          if (out) {
-            const real4 c = lit::pixel_float4(sc, le, prims, g.xc(j), g.yc(i), lcull != 0, bad);
-            double* o = out + px * 4;
-            o[0] = (double)c.x; o[1] = (double)c.y; o[2] = (double)c.z; o[3] = (double)c.w;
-          }
-          if (rgba) {
-            const unsigned v = lit::pixel_rgba8(sc, le, prims, g.xc(j), g.yc(i), lcull != 0, bad);
-            for (int k = 0; k < 4; k++) rgba[4 * px + k] = (unsigned char)((v >> (8 * k)) & 255u);
-          }
-          if (depth) depth[px] = (double)lit::pixel_depth(sc, prims, g.xc(j), g.yc(i), bad);
-        }
-    }
+  const lit::LitPixels<ViewScene, lit::ViewLit, unsigned long long> p = {sc, le, lcull != 0, code != fly::CAM_OK || le.bad != lit::LIGHT_OK};
+  host_tiles(sc, W, H, 1, 0ull, [&](unsigned long long prims, real xc, real yc, size_t px) { host_store(p, prims, xc, yc, px, out, rgba, depth); });
   return 16 * le.bad + code;
 }
 
@@ -75,41 +54,16 @@ int pihl_fly_render(const double* rec, const float* cam_words, const float* ligh
   if (!rec || !cam_words || !light_words || W <= 0 || H <= 0 || object < 0 || object >= PIH_FLY_NOBJ) return -2;
   FlyCam cam;
   for (int i = 0; i < PIH_CAM_WORDS; i++) cam.w[i] = cam_words[i];
-  const int code = cam_degenerate(cam.w);
-  if (code != CAM_OK) cam = FlyCam{PIH_FLY_CAM_DEFAULT};
+  const int code = camera_or_preset(cam, FlyCam{PIH_FLY_CAM_DEFAULT});
   const lit::LightWords lw = lit::light_words(light_words);
-  FlyPose ps;
-  for (int i = 0; i < RCAP; i++) ps.q[i] = (real)rec[PIH_F_Q + i];
-  for (int i = 0; i < 3; i++) ps.opos[i] = (real)rec[PIH_F_OPOS + i];
-  for (int i = 0; i < 4; i++) ps.oquat[i] = (real)rec[PIH_F_OQUAT + i];
+  const FlyPose ps = load_fly_pose(rec, 0, 1);
   FlyScene sc;
   lit::FlyLit le;
   lit::light_setup(le, lw, all_prims(object));
   for (int tid = 0; tid < 16; tid++) scene_setup_poses(sc, ps, cam, object, flags, tid);
   for (int tid = 0; tid < RENDER_THREADS; tid++) { scene_setup_bounds(sc, object, tid); lit::light_table(sc, le, tid); }
-  const bool bad = code != CAM_OK || le.bad != lit::LIGHT_OK;
-  const FlyGrid g(sc, W, H);
-  for (int i0 = 0; i0 < H; i0 += TILE_ROWS)
-    for (int j0 = 0; j0 < W; j0 += TILE_COLS) {
-      const int i1 = i0 + TILE_ROWS < H ? i0 + TILE_ROWS : H, j1 = j0 + TILE_COLS < W ? j0 + TILE_COLS : W;
-      unsigned prims = 0;
-      for (int lane = 0; lane < 32; lane++)
-        if (prim_on_tile(sc, lane, g.xedge(j0), g.xedge(j1), g.yedge(i1), g.yedge(i0))) prims |= 1u << lane;
-      for (int i = i0; i < i1; i++)
-        for (int j = j0; j < j1; j++) {
-          const size_t px = (size_t)i * W + j;
-          if (out) {
-            const real4 c = lit::pixel_float4(sc, le, prims, g.xc(j), g.yc(i), lcull != 0, bad);
-            double* o = out + px * 4;
-            o[0] = (double)c.x; o[1] = (double)c.y; o[2] = (double)c.z; o[3] = (double)c.w;
-          }
-          if (rgba) {
-            const unsigned v = lit::pixel_rgba8(sc, le, prims, g.xc(j), g.yc(i), lcull != 0, bad);
-            for (int k = 0; k < 4; k++) rgba[4 * px + k] = (unsigned char)((v >> (8 * k)) & 255u);
-          }
-          if (depth) depth[px] = (double)lit::pixel_depth(sc, prims, g.xc(j), g.yc(i), bad);
-        }
-    }
+  const lit::LitPixels<FlyScene, lit::FlyLit, unsigned> p = {sc, le, lcull != 0, code != CAM_OK || le.bad != lit::LIGHT_OK};
+  host_tiles(sc, W, H, 1, 0u, [&](unsigned prims, real xc, real yc, size_t px) { host_store(p, prims, xc, yc, px, out, rgba, depth); });
   return 16 * le.bad + code;
 }
 

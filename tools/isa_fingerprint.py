@@ -2,6 +2,12 @@
 """Fingerprint of the gfx950 code of every kernel of the library (pih_hip.hip, pih_fly_image.hip, pih_view.hip, pih_lit.hip, pih_robot.hip), without a GPU: one line per kernel with a hash of its instruction
 stream, the instruction count and the VGPR / AGPR / SGPR / LDS / scratch numbers of the code object metadata.  A refactor that leaves
 the lines of the hot kernels unchanged leaves their speed unchanged (the step kernels sit at the 256-register limit).
+Used that way for the camera kernels' shared pieces (one tile walk, one scene set-up per task: DESIGN.md 6.5): both listings are
+profiles/camera_refactor_fingerprint.txt.  The 33 other kernels' lines had to stay identical; for the 14 camera kernels the resource
+columns had to, and the listing decided between forms of the same code -- (row0 + i) * W + j against e * H * W + i * W + j for the pixel
+index, the light hook under a thread test outside or inside the hook -- that differ by up to 8 VGPRs.  A line whose hash alone moved was
+then checked on the GPU: outputs byte for byte against the parent's build, times against the parent's spread (which sent
+pih_lit_view_kernel back to its own copy of the walk: its three lines are the parent's again).
 usage: python tools/isa_fingerprint.py [SOURCE_TREE]    (default: this checkout; e.g. a `git worktree add` of another commit)"""
 import hashlib
 import os
