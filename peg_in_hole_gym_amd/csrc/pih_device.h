@@ -5,6 +5,8 @@
 //                 scans, ABA inward sweep, PGS); the env wavefront's side of the fused-launch handshake
 //   pih_mailbox.h the handshake of the fused launch (controller wavefronts -> mailbox -> step wavefronts), both tasks
 //   pih_step.h    articulated-body forward dynamics and the step itself
+// Included by the kernel translation units (pih_peg.hip, pih_fly.hip and, through pih_render.h, the cameras); the C ABI (pih_hip.hip)
+// includes none of it.
 // gfx950 only: there is no host path in the product (libpih_hip.so); the test harness in tests/emul brings its own wave layer.
 #pragma once
 #include "pih_common.h"

@@ -70,7 +70,7 @@ constexpr int CANDQ0 = 16, KWQ = CWQ;
 constexpr int LANE_WORDS_Q = CANDQ0 + NC * KWQ;
 static_assert(KW <= KWQ && CANDQ0 + KWQ > FQ_LAM + FK_DEPTH + 1 && 6 * NJ <= LANE_WORDS_Q, "candidate k must not be overwritten by record k");
 constexpr int KR = 8;              // quad layout: the records of the first KR contacts of an env stay in REGISTERS over the PGS iterations (72 per lane)
-// What step_env asks of the wavefront: on the GPU ballots over the active lanes (FlyWave, pih_hip.hip); here a "wavefront" of ONE env, the
+// What step_env asks of the wavefront: on the GPU ballots over the active lanes (FlyWave, pih_fly.hip); here a "wavefront" of ONE env, the
 // host build's, where the envs run one after the other
 struct OneEnvWave {
   PIH_HD int wave_or(int x) const { return x; }
@@ -202,7 +202,7 @@ template <> struct Layout<false> { static constexpr int RW = CW, LAMW = FC_LAM, 
 template <> struct Layout<true> { static constexpr int RW = CWQ, LAMW = FQ_LAM, CAND = CANDQ0, KS = KWQ; };
 
 // One dt of one env.  S: the env's state record (a per-lane local array); mem: this lane's contact-row scratch; ctl: InlineIk or the
-// mailbox reader of the fused launch (MailboxIk, pih_hip.hip).
+// mailbox reader of the fused launch (MailboxIk, pih_fly.hip).
 // Q: NoQuad (one env per lane) or the quad primitives (QuadDpp / the host's lockstep threads, pih_ikq.h) of the one-env-per-quad layout.
 template <class Ctl = InlineIk, class Q = NoQuad, class Mem>
 PIH_HD void step_env(real* S, const Params& P, int env_global, const real* action, real* obs, real* reward, unsigned char* done, Mem mem, real* dbg, Ctl ctl = Ctl(), Q quad = Q()) {

@@ -1,6 +1,6 @@
-// pih_fly_image.hip -- the free camera of the random-fly task (pih_fly_render.h) with the options pih_fly_render_kernel of pih_hip.hip
+// pih_fly_image.hip -- the free camera of the random-fly task (pih_fly_render.h) with the options pih_fly_render_kernel of pih_fly.hip
 // does not have; that kernel stays as it is (the float4 image of one host camera).  A translation unit of its own: with these kernels in
-// pih_hip.hip the compiler scheduled pih_fly_render_kernel differently (same instructions, another order), and tools/isa_fingerprint.py
+// its translation unit the compiler scheduled pih_fly_render_kernel differently (same instructions, another order), and tools/isa_fingerprint.py
 // is to show every older kernel unchanged.
 //   FMT       0: float4 (depth, r, g, b) | PIH_RENDER_OUT_RGBA8: one 32-bit word (r, g, b, seg) | PIH_RENDER_OUT_DEPTH: one float
 //   cam_dev   != nullptr (PIH_RENDER_CAM_DEVICE): float[count, PIH_CAM_WORDS], row blockIdx.y is this workgroup's camera -- 13 more
@@ -11,6 +11,7 @@
 // packed formats, 1 KB in float4); pih_lit_fly_kernel (pih_lit.hip) is the same two calls with the light hooked in.
 #include <hip/hip_runtime.h>
 #include "pih_fly_render.h"
+#include "pih_launch.h"
 
 using namespace pih;
 

@@ -17,7 +17,7 @@
 // Output formats: float4 (depth, r, g, b) as above; PIH_RENDER_OUT_RGBA8 = bytes (r, g, b, seg), seg = the hit's kind (link 0 .. 5,
 // PIH_SEG_OBJECT, PIH_SEG_TABLE, PIH_SEG_NONE); PIH_RENDER_OUT_DEPTH = the depth value alone.  PIH_RENDER_CAM_DEVICE: one camera per env,
 // read by the kernel, tested by the kernel (cam_degenerate): a degenerate one gives its env the background.  Kernels: pih_fly_render_kernel
-// (pih_hip.hip; float4, one host camera) and pih_fly_image_kernel (pih_fly_image.hip; everything else).
+// (pih_fly.hip; float4, one host camera) and pih_fly_image_kernel (pih_fly_image.hip; everything else).
 //
 // Mapping (as pih_render.h): one 256-thread workgroup per (env, strip of rows), the scene once per workgroup in LDS; each WAVE walks
 // 16-row x 64-column tiles; lane i < FLY_NPRIM tests the conservative screen bound of primitive i (camera coordinates; a capsule's bound

@@ -1,6 +1,8 @@
-// pih_hip.hip -- kernels + C ABI (include/pih.h) of the MI355X-native peg-in-hole environment.
-// gfx950 only; one wavefront (64 threads, one workgroup) per env; per-env scratch in LDS (struct pih::Shared).
-// Build: hipcc --offload-arch=gfx950 -O3 -shared -fPIC -o libpih_hip.so pih_hip.hip   (see build.py)
+// pih_hip.hip -- the C ABI (include/pih.h, include/pih_robot.h) of the MI355X-native peg-in-hole environment, and nothing else: the handle,
+// its allocations, the fused-launch state, timing, roctx ranges, and every entry point with its argument checks.  Host code only: every
+// kernel lives in a translation unit of its own kind (pih_peg.hip, pih_fly.hip, pih_fly_image.hip, pih_view.hip, pih_lit.hip,
+// pih_robot.hip) and is reached through the launch functions of pih_launch.h, so an edit here cannot appear in a kernel's code.
+// Build: build.py (one hipcc call over all translation units)
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
 #include <cstdio>
@@ -8,446 +10,12 @@
 #include <cstring>
 #include <string>
 #include <vector>
-#include "pih_device.h"
-#include "pih_render.h"
-#include "pih_fly.h"
-#include "pih_fly_render.h"
+#include "pih_common.h"            // Params, config_defaults, params_from_config, the overflow area's size
+#include "pih_fly_render.h"        // fly::FlyCam, fly::cam_degenerate
+#include "pih_launch.h"
 
 using namespace pih;
 
-// pih_fly_image.hip: the kernels of the packed output formats and of the per-env cameras in device memory
-namespace pih {
-void fly_image_launch(int fmt, dim3 grid, hipStream_t stream, const float* state, void* out, const fly::FlyCam& cam, const float* cam_dev,
-                      int n, int object, int env_begin, int W, int H, int rows_per_strip, int flags);
-// pih_view.hip: the free camera of the peg-in-hole task
-void view_launch(int fmt, dim3 grid, hipStream_t stream, const float* state, void* out, const fly::FlyCam& cam, const float* cam_dev,
-                 int env_begin, int W, int H, int rows_per_strip, int flags);
-// pih_lit.hip: both cameras under a caller-given light, with a specular term and cast shadows
-int lit_light_check(const float* words, const char** what);
-void lit_launch(bool fly_task, int fmt, dim3 grid, hipStream_t stream, const float* state, void* out, const fly::FlyCam& cam, const float* cam_dev,
-                const float* light, const float* light_dev, int n, int object, int env_begin, int W, int H, int rows_per_strip, int flags);
-// pih_robot.hip: the batched robot-model queries of include/pih_robot.h
-void robot_fk_launch(int robot, bool staged, hipStream_t stream, int n, const float* q, const float* qd, float* out);
-void robot_jacobian_launch(int robot, bool staged, hipStream_t stream, int n, const float* q, int frame, const float* local_pos, float* out);
-void robot_mass_launch(int robot, bool staged, hipStream_t stream, int n, const float* q, float* out);
-void robot_invdyn_launch(int robot, hipStream_t stream, int n, const float* q, const float* qd, const float* qdd, float* tau);
-void link_states_launch(bool fly_task, hipStream_t stream, const float* state, float* out, int n_envs, int env_begin, int env_count);
-int robot_dims(int robot, int* ndof, int* nframes);
-int link_states_frames(int task_id);
-}
-
-// ------------------------------------------------------------------------------------------------ kernels
-// state: float[n][256] (env-major records: the 64 lanes of the env's wave read/write consecutive words, so every
-// access is a fully coalesced 256 B segment).
-// Longest-job-first dispatch order.  The cost of an env-step grows ~linearly with its contact count (each contact is one
-// 3x3 PGS block per iteration), and at 4096 envs there are only two rounds of resident waves, so a heavy env that starts
-// late leaves most of the chip idle at the tail.  This single-workgroup counting sort orders the envs by the contact count
-// of their PREVIOUS step (descending); pih_step_kernel maps blockIdx through it.  Results do not depend on block order.
-constexpr int PRE_THREADS = 256;
-// the dispatch-order bin of an env with `ncontact` contacts in its previous step, of 64: bin 0 = most contacts (63 and more)
-__device__ __forceinline__ int contact_bin(float ncontact) {
-  const int k = (int)ncontact;
-  return 63 - (k < 0 ? 0 : (k > 63 ? 63 : k));
-}
-__device__ __forceinline__ void pre_sort_block(float* __restrict__ state, int* __restrict__ order, int n) {
-  const int t = threadIdx.x;
-  if (!order) return;
-  __shared__ int hist[64], base[64];
-  if (t < 64) hist[t] = 0;
-  __syncthreads();
-  for (int e = t; e < n; e += PRE_THREADS) {
-    atomicAdd(&hist[contact_bin(state[(size_t)e * PIH_STATE_WORDS + PIH_S_NCONTACT])], 1);
-  }
-  __syncthreads();
-  if (t == 0) { int acc = 0; for (int b = 0; b < 64; b++) { base[b] = acc; acc += hist[b]; } }
-  __syncthreads();
-  for (int e = t; e < n; e += PRE_THREADS) {
-    const int r = atomicAdd(&base[contact_bin(state[(size_t)e * PIH_STATE_WORDS + PIH_S_NCONTACT])], 1);
-    order[r] = e;
-  }
-}
-
-// Launch 1 of the two-launch step of rounds 1-3, kept as the reference of the fused launch (pih_config.schedule + 8; the only step a
-// hipGraph can capture).  Block 0: the dispatch order above.  Blocks 1..: the controller (action / state machine -> IK -> joint targets)
-// one env per LANE, 64 envs per block on the block's first wavefront (controller_targets: ik_chain).
-__global__ void __launch_bounds__(PRE_THREADS) pih_pre_kernel(Params P, float* __restrict__ state, const float* __restrict__ actions,
-                                                               int* __restrict__ order, int n) {
-  const int t = threadIdx.x;
-  if (blockIdx.x == 0) { pre_sort_block(state, order, n); return; }
-  if (t >= 64) return;
-  const int env = (blockIdx.x - 1) * 64 + t;
-  if (env >= n) return;
-  float* S = state + (size_t)env * PIH_STATE_WORDS;
-  if (!P.autoreset && S[PIH_S_DONE] != 0) return;      // finished envs keep their last values (envs/base_env.py:62,66)
-  float a[4] = {0, 0, 0, 0};
-  if (actions) { a[0] = actions[env * 4]; a[1] = actions[env * 4 + 1]; a[2] = actions[env * 4 + 2]; a[3] = actions[env * 4 + 3]; }
-  controller_targets(S, P, a);
-}
-
-// ---- the fused launch (round 4): ONE launch per step.
-// Rounds 1-3 ran two launches per step: pih_pre_kernel (dispatch-order sort + controller, 33 us of which ~10 us are the gap between two
-// dependent launches, on 64 of the chip's 1 024 SIMDs) and then pih_step_kernel (313 us at 4 096 envs).  Here the step kernel's grid is
-// G = ceil(n / 64) CONTROLLER wavefronts (blocks 0 .. G - 1, dispatched first) followed by the n env wavefronts:
-//   * a controller wavefront runs controller_compute for 64 envs, one per lane, from the envs' state records as the previous launch left
-//     them, writes each env's 13 controller words into its mailbox record and publishes the group with the launch's epoch
-//     (pih_mailbox.h); it never waits for anything;
-//   * an env wavefront does forward kinematics, collision detection and the articulated-body sweep (~22 us), then waits -- bounded,
-//     s_sleep between polls -- for its group's flag and takes the controller words from the mailbox (Wave::await_controller); the
-//     controller needs ~25 us, so the first round of env waves waits a few us and the second round not at all;
-//   * the dispatch order for the NEXT launch is built by the env wavefronts themselves: at its end an env takes a slot in the bin of its
-//     contact count (atomicAdd; bin 0 = most contacts) of the "next" bin buffer; at its start block b finds "its" env by a prefix sum
-//     over the 64 bin counts of the "current" buffer.  Three buffers rotate (current / next / being zeroed), so no launch ever reads a
-//     count another wave of the same launch is still changing.  Results do not depend on the order (tests/test_gpu_api.py).
-struct FusedArgs {
-  int G, n, epoch;               // G = 0: two-launch path (no controller role, no mailbox)
-  const int* bcur; int* bnext; int* bzero;   // bin buffers: [64 counts][64 x n slots]; nullptr: block b = env b (schedule 0) or `order`
-  float* mail; int* flags; int* err;
-};
-__device__ __forceinline__ int fused_lookup_env(const int* __restrict__ bcur, int b, int n, int lane) {
-  int p = bcur[lane];
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) { const int t = __shfl_up(p, d); if (lane >= d) p += t; }
-  const unsigned long long m = __ballot(p > b);
-  if (m == 0) return b;                                      // (inconsistent bins cannot happen; stay in range if they do)
-  const int k = __ffsll((long long)m) - 1;
-  const int base = k > 0 ? __shfl(p, k - 1) : 0;
-  const int e = bcur[64 + (size_t)k * n + (b - base)];
-  return e >= 0 && e < n ? e : b;
-}
-
-__global__ void __launch_bounds__(64, 2) pih_step_kernel(Params P, float* __restrict__ state, const float* __restrict__ actions,
-                                                      float* __restrict__ obs, float* __restrict__ reward,
-                                                      unsigned char* __restrict__ done, float* __restrict__ dbg,
-                                                      float* __restrict__ ovf, const int* __restrict__ order, FusedArgs F) {
-  const int lane = threadIdx.x;
-  if ((int)blockIdx.x < F.G) {
-    // ---- controller role: 64 envs, one per lane (controller_compute: the strictly sequential IK)
-    __builtin_amdgcn_s_setprio(3);                             // it shares its SIMD with an env wavefront that will be waiting for it
-    if (blockIdx.x == 0 && F.bzero) F.bzero[lane] = 0;
-    const int env = blockIdx.x * 64 + lane;
-    if (env < F.n) {
-      const float* S = state + (size_t)env * PIH_STATE_WORDS;
-      if (P.autoreset || S[PIH_S_DONE] == 0) {               // finished envs keep their last values (envs/base_env.py:62,66): their waves do not read the mailbox
-        float a[4] = {0, 0, 0, 0};
-        if (actions) { a[0] = actions[env * 4]; a[1] = actions[env * 4 + 1]; a[2] = actions[env * 4 + 2]; a[3] = actions[env * 4 + 3]; }
-        const CtrlOut o = controller_compute(S, P, a);
-        float* m = F.mail + (size_t)env * CTRL_WORDS;
-        const float ov[13] = {o.target[0], o.target[1], o.target[2], o.target[3], o.target[4], o.target[5], o.target[6], o.target[7], o.target[8], o.fsm, o.fsmt, o.grasp_angle, o.attach_qz};
-#pragma unroll
-        for (int i = 0; i < 13; i++) mail_store(m + i, ov[i]);
-      }
-    }
-    mailbox_publish(F.flags, F.epoch);
-    return;
-  }
-  __shared__ Shared sh;
-  const int b = blockIdx.x - F.G;
-  const int env = __builtin_amdgcn_readfirstlane(F.bcur ? fused_lookup_env(F.bcur, b, F.n, lane) : (order ? order[b] : b));   // (wave-uniform by construction; the scalar makes it so for the compiler)
-  Wave w; w.l = lane; w.counter = 0;
-  float* rec = state + (size_t)env * PIH_STATE_WORDS;
-#pragma unroll
-  for (int i = 0; i < PIH_STATE_WORDS / 64; i++) sh.S[lane + 64 * i] = rec[lane + 64 * i];
-  __syncthreads();
-  float o[5], r; unsigned char d;
-  Ovf ov; ov.base = ovf + (size_t)env * OVF_WORDS;
-  w.dbg = dbg ? dbg + (size_t)env * PIH_DEBUG_WORDS : nullptr; w.dbgmode = P.debug; w.prio_on = !P.noprio;
-  if (F.G > 0) { w.cflags = F.flags; w.cmail = F.mail; w.cerr = F.err; w.cepoch = F.epoch; w.cenv = env; }
-  step_env(w, sh, P, ov, env, nullptr, o, &r, &d, dbg ? dbg + (size_t)env * PIH_DEBUG_WORDS : nullptr);
-  __syncthreads();
-#pragma unroll
-  for (int i = 0; i < PIH_STATE_WORDS / 64; i++) rec[lane + 64 * i] = sh.S[lane + 64 * i];
-  if (lane < 5 && obs) obs[env * 5 + lane] = o[0] * (lane == 0) + o[1] * (lane == 1) + o[2] * (lane == 2) + o[3] * (lane == 3) + o[4] * (lane == 4);
-  if (lane == 0) {
-    if (reward) reward[env] = r; if (done) done[env] = d;
-    if (F.bnext) {                                           // a slot in the next launch's dispatch order
-      const int bin = contact_bin(sh.S[PIH_S_NCONTACT]);
-      const int rnk = atomicAdd(F.bnext + bin, 1);
-      if (rnk < F.n) F.bnext[64 + (size_t)bin * F.n + rnk] = env;
-    }
-  }
-}
-
-// first fill of a bin buffer (pih_create): the same counting sort, from the state records
-__global__ void __launch_bounds__(256) pih_bins_init_kernel(const float* __restrict__ state, int* __restrict__ bins, int n) {
-  for (int e = blockIdx.x * 256 + threadIdx.x; e < n; e += gridDim.x * 256) {
-    const int bin = contact_bin(state[(size_t)e * PIH_STATE_WORDS + PIH_S_NCONTACT]);
-    const int rnk = atomicAdd(bins + bin, 1);
-    bins[64 + (size_t)bin * n + rnk] = e;
-  }
-}
-
-// hard (resetSimulation, envs/base_env.py:85-86): a NEW scene like every reset (the reference keeps drawing from the global `random`); it
-// also clears the non-finite-reset count.  rewind (explicit replay, pih_reset(seed != 0) / pih_reseed): the env's draw counter restarts.
-__global__ void __launch_bounds__(64) pih_reset_kernel(Params P, float* __restrict__ state, const unsigned char* __restrict__ mask, int hard, int rewind) {
-  __shared__ Shared sh;
-  const int env = blockIdx.x, lane = threadIdx.x;
-  if (mask && !mask[env]) return;
-  Wave w; w.l = lane; w.counter = 0;
-  float* rec = state + (size_t)env * PIH_STATE_WORDS;
-  for (int i = 0; i < PIH_STATE_WORDS / 64; i++) sh.S[lane + 64 * i] = rec[lane + 64 * i];
-  __syncthreads();
-  if (hard) sh.S[PIH_S_SPARE] = 0;
-  if (rewind) { sh.S[PIH_S_RNG] = 0; sh.S[PIH_S_RNG_HI] = 0; }
-  __syncthreads();
-  reset_state(sh.S, P, P.env0 + env);
-  __syncthreads();
-  fk_all(w, sh);
-  float tip[7]; tip_pose(sh, tip);
-  for (int i = 0; i < 7; i++) sh.S[PIH_S_TIP + i] = tip[i];
-  V3 ee; M3 eR; ee_pose(sh, ee, eR);
-  sh.S[PIH_S_EE] = ee.x + sh.S[PIH_S_OFFSET]; sh.S[PIH_S_EE + 1] = ee.y + sh.S[PIH_S_OFFSET + 1]; sh.S[PIH_S_EE + 2] = ee.z + sh.S[PIH_S_OFFSET + 2];
-  __syncthreads();
-  for (int i = 0; i < PIH_STATE_WORDS / 64; i++) rec[lane + 64 * i] = sh.S[lane + 64 * i];
-}
-
-__global__ void __launch_bounds__(64) pih_init_offsets_kernel(float* __restrict__ state, const float* __restrict__ offsets, int n) {
-  int e = blockIdx.x * 64 + threadIdx.x;
-  if (e >= n) return;
-  float* rec = state + (size_t)e * PIH_STATE_WORDS;
-  for (int k = 0; k < 3; k++) rec[PIH_S_OFFSET + k] = offsets ? offsets[3 * e + k] : 0.f;
-}
-
-// stand-alone batched IK (envs/utils.py:67,79): one problem per QUAD of lanes (pih_ikq.h), 16 problems per wavefront
-template <class C> __device__ __forceinline__ void ik_quad_problem(const Params& P, int n, int stride, const float* q0, const float* tpos, const float* tquat, float* qout) {
-  const int i = blockIdx.x * 16 + (threadIdx.x >> 2);
-  if (i >= n) return;
-  QuadDpp qd; qd.l = threadIdx.x & 3;
-  const int j0 = 2 * qd.l, j1 = 2 * qd.l + 1;
-  const QuadSlots sl = ikq_slots<C>(qd);
-  float a = j0 < C::N ? q0[i * stride + j0] : 0.0f, b = j1 < C::N ? q0[i * stride + j1] : 0.0f;
-  Q4 tq; tq.x = tquat[4 * i]; tq.y = tquat[4 * i + 1]; tq.z = tquat[4 * i + 2]; tq.w = tquat[4 * i + 3];
-  ikq_solve(qd, sl, P, mk(tpos[3 * i], tpos[3 * i + 1], tpos[3 * i + 2]), tq, a, b);
-  if (j0 < C::N) qout[i * stride + j0] = a;
-  if (j1 < C::N) qout[i * stride + j1] = b;
-  for (int k = C::N + qd.l; k < stride; k += 4) qout[i * stride + k] = q0[i * stride + k];      // (Panda: the finger entries pass through)
-}
-__global__ void __launch_bounds__(64) pih_ik_kernel(Params P, int n, const float* __restrict__ q0, const float* __restrict__ tpos,
-                                                    const float* __restrict__ tquat, float* __restrict__ qout) {
-  ik_quad_problem<PandaChain>(P, n, 9, q0, tpos, tquat, qout);
-}
-// the same for the UR5 chain (envs/utils.py:79): q0 float[n,6] -> qout float[n,6]
-__global__ void __launch_bounds__(64) pih_ik_ur5_kernel(Params P, int n, const float* __restrict__ q0, const float* __restrict__ tpos,
-                                                        const float* __restrict__ tquat, float* __restrict__ qout) {
-  ik_quad_problem<Ur5Chain>(P, n, 6, q0, tpos, tquat, qout);
-}
-
-// wrist camera (p12): grid = (strips, envs), 256 threads (4 waves); out float[count, H, W, 4] = depth, r, g, b.  The tile walk is the one
-// of every camera kernel (fly::render_strip, pih_fly_render.h) on a grid with the wrist camera's constant tan(fov / 2).
-__global__ void __launch_bounds__(RENDER_THREADS) pih_render_kernel(const float* __restrict__ state, float* __restrict__ out,
-                                                                    int env_begin, int W, int H, int rows_per_strip, int flags) {
-  __shared__ Shared sh;
-  __shared__ Scene sc;
-  const int tid = threadIdx.x, e = blockIdx.y, env = env_begin + e;
-  const int r0 = blockIdx.x * rows_per_strip, r1 = min(H, r0 + rows_per_strip);
-  Wave w; w.l = tid; w.counter = 0;
-  const float* rec = state + (size_t)env * PIH_STATE_WORDS;
-  for (int i = tid; i < PIH_STATE_WORDS; i += RENDER_THREADS) sh.S[i] = rec[i];
-  __syncthreads();
-  scene_setup(w, sh, sc, tid);
-  static_assert(fly::TILE_ROWS == 16 && fly::TILE_COLS == 64, "the tile of pih_render.h's mapping: 16 rows x 64 columns, one row of a tile per wave instruction");
-  fly::render_strip<unsigned>(sc, fly::FlyGrid(PIH_CAM_TANH2, PIH_CAM_TANH2, W, H), reinterpret_cast<float4*>(out), (size_t)e * H, W, r0, r1, tid,
-                              [&](unsigned prims, real xc, real yc) { return fly::to_float4(shade(sc, prims, xc, yc, flags)); });
-}
-
-// free camera of the random-fly task (pih_fly_render.h): grid = (strips, envs), 256 threads (4 waves); out float[count, H, W, 4] = depth,
-// r, g, b.  state is structure-of-arrays: the 13 words the scene needs are wave-uniform (scalar) loads (load_fly_pose).  One host camera,
-// validated by pih_render_cam: no camera test here (pih_fly_image_kernel has it); the tile walk is render_strip.
-__global__ void __launch_bounds__(RENDER_THREADS) pih_fly_render_kernel(const float* __restrict__ state, float* __restrict__ out, fly::FlyCam cam,
-                                                                        int n, int object, int env_begin, int W, int H, int rows_per_strip, int flags) {
-  using namespace fly;
-  __shared__ FlyScene sc;
-  const int tid = threadIdx.x, e = blockIdx.y, env = env_begin + e;
-  const int r0 = blockIdx.x * rows_per_strip, r1 = min(H, r0 + rows_per_strip);
-  if (tid < 16) scene_setup_poses(sc, load_fly_pose(state, env, n), cam, object, flags, tid);
-  __syncthreads();
-  scene_setup_bounds(sc, object, tid);
-  __syncthreads();
-  render_strip<unsigned>(sc, FlyGrid(sc, W, H), reinterpret_cast<float4*>(out), (size_t)e * H, W, r0, r1, tid,
-                         [&](unsigned prims, real xc, real yc) { return to_float4(shade(sc, prims, xc, yc, flags)); });
-}
-
-// label images: grid = (ceil(S*S/256), envs); out[e][k][y][x], image index [cc][rr] of the reference = [x-like c][r]
-__global__ void __launch_bounds__(256) pih_labels_kernel(const float* __restrict__ state, float* __restrict__ out, float* __restrict__ meta,
-                                                         int env_begin, int S) {
-  const int e = blockIdx.y, env = env_begin + e;
-  const float angle = state[(size_t)env * PIH_STATE_WORDS + PIH_S_GRASP_ANGLE];
-  const LabelRect L = label_rect(angle, S);
-  // each thread owns 4 consecutive pixels and writes one 16-byte store per label plane (the kernel is pure HBM writes)
-  const int SS = S * S, i4 = (blockIdx.x * 256 + threadIdx.x) * 4;
-  float* o = out + (size_t)e * 4 * SS;
-  if (i4 < SS) {
-    float v[4][4];
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-      const int idx = i4 + k < SS ? i4 + k : SS - 1;
-      const int c = idx / S, r = idx - c * S;            // element [c][r] of the image
-      const bool in = label_inside(L, (float)c, (float)r);
-      v[0][k] = in ? 50.0f : 0.0f; v[1][k] = in ? L.s2 : 0.0f; v[2][k] = in ? L.c2 : 1.0f; v[3][k] = in ? L.wpx : 0.0f;
-    }
-    const bool vec = (i4 + 3 < SS) && ((SS & 3) == 0) && ((reinterpret_cast<uintptr_t>(out) & 15) == 0);
-#pragma unroll
-    for (int pl = 0; pl < 4; pl++) {
-      if (vec) *reinterpret_cast<float4*>(o + (size_t)pl * SS + i4) = make_float4(v[pl][0], v[pl][1], v[pl][2], v[pl][3]);
-      else for (int k = 0; k < 4 && i4 + k < SS; k++) o[(size_t)pl * SS + i4 + k] = v[pl][k];
-    }
-  }
-  if (meta && blockIdx.x == 0 && threadIdx.x == 0) {
-    float* m = meta + (size_t)e * 5;
-    m[0] = 0; m[1] = 0; m[2] = angle * (180.0f / 3.14159265358979f); m[3] = L.wpx; m[4] = L.lpx;
-  }
-}
-
-__global__ void pih_gather_kernel(const float* __restrict__ state, float* __restrict__ out, int n, int word0, int nwords) {
-  int idx = blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= n * nwords) return;
-  int e = idx / nwords, k = idx - e * nwords;
-  out[idx] = state[(size_t)e * PIH_STATE_WORDS + word0 + k];
-}
-
-// ------------------------------------------------------------------------------------------------ 'random-fly' task kernels
-// One env per LANE or per QUAD of lanes (pih_fly.h).  state: float[PIH_FLY_STATE_WORDS][n] (structure-of-arrays: word w of the envs of a
-// wave is one coalesced segment).  LDS: the per-lane contact rows, [word][lane]: 120 KB per wave in the lane layout (one wave per CU), 38 KB
-// in the quad layout (four per CU; the kernel needs 450 registers, i.e. one wave per SIMD, anyway).
-// (Round 3, profiles/r03_fly_envs_per_wave.txt: packing FEWER envs into a wave of the lane layout did not shorten the launch, and with 120 KB
-//  of LDS per wave it cost rounds.  The quad layout does not idle the other lanes: it gives them a share of the PGS sweep.)
-//
-// The fused random-fly launch (round 4, as the peg-in-hole one): the first G = ceil(n / 64) blocks are CONTROLLER wavefronts (the IK of 64
-// envs, one per lane, straight into a mailbox [group][word][lane], then the epoch into the block's flag), the following blocks the step
-// wavefronts (ceil(n / 16) in the quad layout, G in the lane layout), whose lanes read their targets from the mailbox right before the PGS
-// loop -- after forward kinematics, the articulated-body sweeps, collision detection and all response rows.  Every workgroup of the launch
-// carries the step's dynamic LDS, and a step wavefront spins on its controller's flag, so the layout is used only while ALL workgroups are
-// resident at once (pih_create: quad layout 4 per CU, lane layout 1 per CU); bigger batches run the IK inside the step wavefront
-// (FUSED = false).
-struct FlyFused { int G, epoch; float* mail; int* flags; int* err; };
-struct MailboxIk {
-  const int* flag; const float* mail; int* err; int epoch, env, n;
-  __device__ __forceinline__ void operator()(const float*, const float*, const float*, const Params&, float* qs) const {
-    mailbox_await(flag, epoch, err, true);
-#pragma unroll
-    for (int i = 0; i < fly::NJ; i++) qs[i] = mail_load(mail + ((size_t)(env >> 6) * fly::NJ + i) * 64 + (env & 63));
-  }
-};
-// QUAD: one env per quad of lanes (pih_fly.h): a step wavefront holds 16 envs, the PGS sweep is split over the quad; the controller
-// wavefronts stay one env per lane, so one flag covers four step wavefronts.
-struct FlyWave {           // what fly::step_env asks of the wavefront, as scalars over its active lanes
-  __device__ __forceinline__ int wave_or(int x) const {     // OR of a 6-bit mask
-    int m = 0;
-#pragma unroll
-    for (int k = 0; k < fly::NJ; k++) if (__builtin_amdgcn_ballot_w64((x >> k) & 1) != 0) m |= 1 << k;
-    return __builtin_amdgcn_readfirstlane(m);
-  }
-  __device__ __forceinline__ bool wave_any(bool x) const { return __builtin_amdgcn_ballot_w64(x) != 0; }
-};
-struct FlyLane : FlyWave { static constexpr bool QUAD = false; __device__ __forceinline__ explicit FlyLane(int) {} };
-struct FlyQuad : QuadDpp, FlyWave {
-  static constexpr bool QUAD = true;
-  __device__ __forceinline__ explicit FlyQuad(int lane) { l = lane & 3; }
-  __device__ __forceinline__ int wave_max(int x) const {     // the largest x (0 <= x <= fly::NC)
-    int m = 0;
-#pragma unroll
-    for (int k = 1; k <= fly::NC; k++) if (__builtin_amdgcn_ballot_w64(x >= k) != 0) m = k;
-    return __builtin_amdgcn_readfirstlane(m);
-  }
-};
-template <bool FUSED, bool QUAD>
-__global__ void __launch_bounds__(64, 1) pih_fly_step_kernel(Params P, float* __restrict__ state, const float* __restrict__ actions,
-                                                             float* __restrict__ obs, float* __restrict__ reward,
-                                                             unsigned char* __restrict__ done, float* __restrict__ dbg, int n, FlyFused F) {
-  extern __shared__ float lanemem[];
-  if (FUSED && (int)blockIdx.x < F.G) {
-    // ---- controller role
-    __builtin_amdgcn_s_setprio(3);
-    const int env = blockIdx.x * 64 + threadIdx.x;
-    if (env < n && (P.autoreset || state[(size_t)PIH_F_DONE * n + env] == 0)) {
-      float q[fly::NJ], S3[PIH_F_OFFSET + 3], a[PIH_FLY_ACTION_DIM], qs[fly::NJ];
-#pragma unroll
-      for (int i = 0; i < fly::NJ; i++) q[i] = state[(size_t)(PIH_F_Q + i) * n + env];
-#pragma unroll
-      for (int k = 0; k < 3; k++) S3[PIH_F_OFFSET + k] = state[(size_t)(PIH_F_OFFSET + k) * n + env];
-#pragma unroll
-      for (int k = 0; k < PIH_FLY_ACTION_DIM; k++) a[k] = actions[(size_t)env * PIH_FLY_ACTION_DIM + k];
-      fly::InlineIk()(q, S3, a, P, qs);
-#pragma unroll
-      for (int i = 0; i < fly::NJ; i++) mail_store(F.mail + ((size_t)blockIdx.x * fly::NJ + i) * 64 + threadIdx.x, qs[i]);
-    }
-    mailbox_publish(F.flags, F.epoch);
-    return;
-  }
-  const int blk = FUSED ? blockIdx.x - F.G : blockIdx.x;
-  const int env = QUAD ? blk * 16 + (int)(threadIdx.x >> 2) : blk * 64 + (int)threadIdx.x;
-  if (env >= n) return;
-  const bool writer = !QUAD || (threadIdx.x & 3) == 0;      // (the four lanes of a quad hold identical results)
-  // config.debug = 2: start / end of the wavefront on the chip-wide 100 MHz clock and where it ran (debug words PIH_DBG_T_START .. of the
-  // wave's first env; tools/fly_trace.py) -- never read by the kernel
-  const bool stamp = dbg && P.debug == 2 && threadIdx.x == 0;
-  long long ts0 = 0;
-  if (stamp) ts0 = (long long)__builtin_amdgcn_s_memrealtime();
-  float S[fly::SW];
-#pragma unroll
-  for (int w = 0; w < fly::SW; w++) S[w] = state[(size_t)w * n + env];
-  float a[PIH_FLY_ACTION_DIM] = {0, 0, 0, 0, 0, 0};
-  if (actions) {
-#pragma unroll
-    for (int k = 0; k < PIH_FLY_ACTION_DIM; k++) a[k] = actions[(size_t)env * PIH_FLY_ACTION_DIM + k];
-  }
-  float o[PIH_FLY_OBS_DIM], r; unsigned char d;
-  fly::LaneMem mem; mem.p = lanemem + threadIdx.x; mem.stride = 64;
-  float* dbge = dbg ? dbg + (size_t)env * PIH_DEBUG_WORDS : nullptr;
-  // the IK targets from the controller wavefront's mailbox (FUSED) or computed here
-  std::conditional_t<FUSED, MailboxIk, fly::InlineIk> ctl;
-  if constexpr (FUSED) { ctl.flag = F.flags + (env >> 6); ctl.mail = F.mail; ctl.err = F.err; ctl.epoch = F.epoch; ctl.env = env; ctl.n = n; }
-  fly::step_env(S, P, P.env0 + env, a, o, &r, &d, mem, dbge, ctl, std::conditional_t<QUAD, FlyQuad, FlyLane>((int)threadIdx.x));
-  if (writer) {
-#pragma unroll
-    for (int w = 0; w < fly::SW; w++) state[(size_t)w * n + env] = S[w];
-    if (obs) {
-#pragma unroll
-      for (int k = 0; k < PIH_FLY_OBS_DIM; k++) obs[(size_t)env * PIH_FLY_OBS_DIM + k] = o[k];
-    }
-    if (reward) reward[env] = r;
-    if (done) done[env] = d;
-  }
-  if (stamp) {
-    const long long ts1 = (long long)__builtin_amdgcn_s_memrealtime();
-    float* o2 = dbg + (size_t)env * PIH_DEBUG_WORDS;
-    debug_store_time(o2, PIH_DBG_T_START, ts0); debug_store_time(o2, PIH_DBG_T_END, ts1); debug_store_hw_id(o2);
-  }
-}
-
-__global__ void __launch_bounds__(64) pih_fly_reset_kernel(Params P, float* __restrict__ state, const unsigned char* __restrict__ mask, int hard, int rewind, int n) {
-  const int env = blockIdx.x * 64 + threadIdx.x;
-  if (env >= n || (mask && !mask[env])) return;
-  float S[fly::SW];
-#pragma unroll
-  for (int w = 0; w < fly::SW; w++) S[w] = state[(size_t)w * n + env];
-  if (hard) S[PIH_F_SPARE] = 0;
-  if (rewind) { S[PIH_F_RNG] = 0; S[PIH_F_RNG_HI] = 0; }
-  fly::reset_state(S, P, P.env0 + env);
-#pragma unroll
-  for (int w = 0; w < fly::SW; w++) state[(size_t)w * n + env] = S[w];
-}
-
-// env-major float[n, W]  <->  structure-of-arrays float[W][n]
-__global__ void pih_soa_to_aos_kernel(const float* __restrict__ soa, float* __restrict__ aos, int n, int W, int word0, int nwords) {
-  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= n * nwords) return;
-  const int e = idx / nwords, k = idx - e * nwords;
-  aos[idx] = soa[(size_t)(word0 + k) * n + e];
-  (void)W;
-}
-__global__ void pih_aos_to_soa_kernel(const float* __restrict__ aos, float* __restrict__ soa, int n, int W) {
-  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= n * W) return;
-  const int w = idx / n, e = idx - w * n;
-  soa[idx] = aos[(size_t)e * W + w];
-}
-__global__ void pih_fly_init_offsets_kernel(float* __restrict__ state, const float* __restrict__ offsets, int n) {
-  const int e = blockIdx.x * 64 + threadIdx.x;
-  if (e >= n) return;
-  for (int k = 0; k < 3; k++) state[(size_t)(PIH_F_OFFSET + k) * n + e] = offsets ? offsets[3 * e + k] : 0.f;
-}
-
-// ------------------------------------------------------------------------------------------------ host side
 // roctx ranges around the step / reset launches (tracing): only with pih_config.debug != 0, and through dlopen so
 // that the library has no link-time dependency on the profiler SDK -- without the roctx library the ranges are silently absent.
 struct Roctx {
@@ -584,20 +152,6 @@ static int next_epoch(pih_handle* h) {
   return ++h->epoch;
 }
 
-// The random-fly step launch of a handle in its layout (h->flyquad), fused or not: the instantiation of pih_fly_step_kernel, the grid (G
-// controller workgroups in front of the step workgroups when fused), the dynamic LDS of every workgroup, and how many of them a CU holds
-struct FlyLaunch { decltype(&pih_fly_step_kernel<false, false>) kernel; int G, grid, per_cu; size_t lds; };
-static_assert((size_t)fly::LANE_WORDS * 64 * sizeof(float) <= 160 * 1024 && (size_t)fly::LANE_WORDS_Q * 64 * sizeof(float) * 4 <= 160 * 1024, "the random-fly kernel's per-wave LDS exceeds its share of a CU's 160 KB");
-static FlyLaunch fly_launch(const pih_handle* h, bool fused) {
-  const int n = h->cfg.n_envs;
-  FlyLaunch L;
-  L.G = (n + 63) / 64;
-  if (h->flyquad) { L.kernel = fused ? pih_fly_step_kernel<true, true> : pih_fly_step_kernel<false, true>; L.grid = (n + 15) / 16; L.per_cu = 4; L.lds = (size_t)fly::LANE_WORDS_Q * 64 * sizeof(float); }
-  else { L.kernel = fused ? pih_fly_step_kernel<true, false> : pih_fly_step_kernel<false, false>; L.grid = L.G; L.per_cu = 1; L.lds = (size_t)fly::LANE_WORDS * 64 * sizeof(float); }
-  if (fused) L.grid += L.G;
-  return L;
-}
-
 // allocation + first reset; on any failure the caller (pih_create) destroys the half-built handle
 static int create_impl(pih_handle* h, const float* offsets_host, float** offd) {
   const pih_config* cfg = &h->cfg;
@@ -612,20 +166,14 @@ static int create_impl(pih_handle* h, const float* offsets_host, float** offd) {
   if (h->fly) {
     // One env per QUAD of lanes in the step wavefronts unless schedule + 32.  The fused launch (controller wavefronts + step wavefronts in
     // one grid; schedule + 8: IK inside the step wavefront) is used while ALL its workgroups -- each with the step's dynamic LDS -- are
-    // resident at once: 4 per CU in the quad layout (n <= 13 104 on 256 CUs), 1 per CU in the lane layout; bigger batches run the IK inside
-    // the step wavefront.
+    // resident at once (fly_fused_fits, pih_fly.hip); bigger batches run the IK inside the step wavefront.
     h->flyquad = (cfg->schedule & 32) == 0;
     int cus = 0; HIPCHK(h, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device));
-    const FlyLaunch fused = fly_launch(h, true);
-    h->fused = (cfg->schedule & 8) == 0 && fused.grid <= fused.per_cu * cus;
-    // (dynamic LDS beyond the default 64 KB limit: the per-lane contact rows and candidate staging of 64 lanes)
-    for (const FlyLaunch& L : {fly_launch(h, false), fused})
-      HIPCHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(L.kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.lds));
-    // mailbox [group][word][64 lanes]: the two 128-byte lines of a (group, word) hold no other group's targets
-    if (h->fused) { int rc = mailbox_alloc(h, (size_t)fused.G * 64 * fly::NJ); if (rc) return rc; }
-    const int nb64 = (cfg->n_envs + 63) / 64;
-    hipLaunchKernelGGL(pih_fly_init_offsets_kernel, dim3(nb64), dim3(64), 0, 0, h->state, *offd, cfg->n_envs);
-    hipLaunchKernelGGL(pih_fly_reset_kernel, dim3(nb64), dim3(64), 0, 0, h->P, h->state, (const unsigned char*)nullptr, 0, 0, cfg->n_envs);
+    h->fused = (cfg->schedule & 8) == 0 && fly_fused_fits(cfg->n_envs, h->flyquad, cus);
+    HIPCHK(h, fly_step_prepare(h->flyquad));
+    if (h->fused) { int rc = mailbox_alloc(h, fly_mail_words(cfg->n_envs)); if (rc) return rc; }
+    fly_init_offsets_launch(0, h->state, *offd, cfg->n_envs);
+    fly_reset_launch(0, h->P, h->state, nullptr, 0, 0, cfg->n_envs);
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipDeviceSynchronize());
     return 0;
@@ -636,18 +184,18 @@ static int create_impl(pih_handle* h, const float* offsets_host, float** offd) {
   // wavefronts in the bin buffers (fused) or by block 0 of pih_pre_kernel in `order` (two launches)
   h->fused = (cfg->schedule & 8) == 0;
   if (h->fused) {
-    int rc = mailbox_alloc(h, (size_t)cfg->n_envs * CTRL_WORDS);
+    int rc = mailbox_alloc(h, peg_mail_words(cfg->n_envs));
     if (rc) return rc;
     if (cfg->schedule & 1) {
-      h->bin_ints = 64 + (size_t)64 * cfg->n_envs;
+      h->bin_ints = peg_bin_ints(cfg->n_envs);
       HIPCHK(h, hipMalloc(&h->bins, 3 * h->bin_ints * sizeof(int)));
       HIPCHK(h, hipMemset(h->bins, 0, 3 * h->bin_ints * sizeof(int)));
     }
   } else if (cfg->schedule & 1) HIPCHK(h, hipMalloc(&h->order, (size_t)cfg->n_envs * sizeof(int)));
-  hipLaunchKernelGGL(pih_init_offsets_kernel, dim3((cfg->n_envs + 63) / 64), dim3(64), 0, 0, h->state, *offd, cfg->n_envs);
-  hipLaunchKernelGGL(pih_reset_kernel, dim3(cfg->n_envs), dim3(64), 0, 0, h->P, h->state, (const unsigned char*)nullptr, 0, 0);
+  peg_init_offsets_launch(0, h->state, *offd, cfg->n_envs);
+  peg_reset_launch(0, h->P, h->state, nullptr, 0, 0, cfg->n_envs);
   // the first launch (epoch 1) reads bin buffer 1: every env once, ordered by the contact counts of the reset state
-  if (h->bins) hipLaunchKernelGGL(pih_bins_init_kernel, dim3(64), dim3(256), 0, 0, h->state, h->bins + h->bin_ints, cfg->n_envs);
+  if (h->bins) peg_bins_init_launch(0, h->state, h->bins + h->bin_ints, cfg->n_envs);
   HIPCHK(h, hipGetLastError());
   HIPCHK(h, hipDeviceSynchronize());
   return 0;
@@ -691,8 +239,7 @@ int pih_reset(pih_handle* h, const uint8_t* mask_dev, int hard, uint64_t seed, v
   if (seed != 0) { h->cfg.seed = seed; h->P.seed = seed; h->rewind_pending = true; }
   const int rewind = h->rewind_pending ? 1 : 0;
   h->rewind_pending = false;
-  if (h->fly) hipLaunchKernelGGL(pih_fly_reset_kernel, dim3((h->cfg.n_envs + 63) / 64), dim3(64), 0, (hipStream_t)stream, h->P, h->state, mask_dev, hard != 0, rewind, h->cfg.n_envs);
-  else hipLaunchKernelGGL(pih_reset_kernel, dim3(h->cfg.n_envs), dim3(64), 0, (hipStream_t)stream, h->P, h->state, mask_dev, hard != 0, rewind);
+  (h->fly ? fly_reset_launch : peg_reset_launch)((hipStream_t)stream, h->P, h->state, mask_dev, hard != 0, rewind, h->cfg.n_envs);
   HIPCHK(h, hipGetLastError());
   return 0;
 }
@@ -718,33 +265,27 @@ static int launch_step(pih_handle* h, const float* actions, float* obs, float* r
   }
   // random-fly: the fused launch (IK in controller wavefronts of the same grid) while all its workgroups fit the chip at once, else (and
   // with schedule + 8) the IK inside the step wavefront.  peg-in-hole: the fused launch, or with schedule + 8 the two-launch step.
-  if (h->fly) {
-    const FlyLaunch L = fly_launch(h, h->fused);
-    FlyFused FF; memset(&FF, 0, sizeof FF);
-    if (h->fused) {
-      const int e = next_epoch(h);
-      if (e < 0) return e;
-      FF.G = L.G; FF.epoch = e; FF.mail = h->mail; FF.flags = h->flags; FF.err = h->errw;
-    }
-    if (t) HIPCHK(h, hipEventRecord(t->b, s));
-    hipLaunchKernelGGL(L.kernel, dim3(L.grid), dim3(64), L.lds, s, h->P, h->state, actions, obs, reward, done, h->dbg, h->cfg.n_envs, FF);
-    if (t) HIPCHK(h, hipEventRecord(t->c, s));
-    HIPCHK(h, hipGetLastError());
-    return 0;
-  }
-  FusedArgs F; memset(&F, 0, sizeof F);
+  const int n = h->cfg.n_envs;
+  const StepIO io = {h->state, actions, obs, reward, done, h->dbg};
+  Mailbox mb = {h->mail, h->flags, h->errw, 0};
   if (h->fused) {
-    // one launch: controller wavefronts first, then the env wavefronts
-    const int e = next_epoch(h);
-    if (e < 0) return e;
-    F.G = (h->cfg.n_envs + 63) / 64; F.n = h->cfg.n_envs; F.epoch = e; F.mail = h->mail; F.flags = h->flags; F.err = h->errw;
-    if (h->bins) { F.bcur = h->bins + (size_t)(e % 3) * h->bin_ints; F.bnext = h->bins + (size_t)((e + 1) % 3) * h->bin_ints; F.bzero = h->bins + (size_t)((e + 2) % 3) * h->bin_ints; }
+    mb.epoch = next_epoch(h);
+    if (mb.epoch < 0) return mb.epoch;
+  }
+  if (h->fly) {
     if (t) HIPCHK(h, hipEventRecord(t->b, s));
-    hipLaunchKernelGGL(pih_step_kernel, dim3(F.G + h->cfg.n_envs), dim3(64), 0, s, h->P, h->state, actions, obs, reward, done, h->dbg, h->ovf, (const int*)nullptr, F);
+    fly_step_launch(s, h->P, io, n, h->flyquad, h->fused ? &mb : nullptr);
+  } else if (h->fused) {
+    // one launch: controller wavefronts first, then the env wavefronts; the three bin buffers rotate (current / next / being zeroed)
+    Bins bins = {nullptr, nullptr, nullptr};
+    const int e = mb.epoch;
+    if (h->bins) bins = {h->bins + (size_t)(e % 3) * h->bin_ints, h->bins + (size_t)((e + 1) % 3) * h->bin_ints, h->bins + (size_t)((e + 2) % 3) * h->bin_ints};
+    if (t) HIPCHK(h, hipEventRecord(t->b, s));
+    peg_step_fused_launch(s, h->P, io, h->ovf, n, mb, bins);
   } else {
-    hipLaunchKernelGGL(pih_pre_kernel, dim3(1 + (h->cfg.n_envs + 63) / 64), dim3(PRE_THREADS), 0, s, h->P, h->state, actions, h->order, h->cfg.n_envs);
+    peg_pre_launch(s, h->P, h->state, actions, h->order, n);
     if (t) HIPCHK(h, hipEventRecord(t->b, s));
-    hipLaunchKernelGGL(pih_step_kernel, dim3(h->cfg.n_envs), dim3(64), 0, s, h->P, h->state, actions, obs, reward, done, h->dbg, h->ovf, (const int*)h->order, F);
+    peg_step_launch(s, h->P, io, h->ovf, h->order, n);
   }
   if (t) HIPCHK(h, hipEventRecord(t->c, s));
   HIPCHK(h, hipGetLastError());
@@ -783,15 +324,15 @@ int pih_get_state(pih_handle* h, int field, void* out_dev, void* stream) {
       case PIH_FIELD_EE_POS: w0 = PIH_F_EE; nw = 3; break;
       default: h->err = "pih_get_state: field not available for the random-fly task"; return -2;
     }
-    hipLaunchKernelGGL(pih_soa_to_aos_kernel, dim3((n * nw + 255) / 256), dim3(256), 0, s, h->state, (float*)out_dev, n, PIH_FLY_STATE_WORDS, w0, nw);
+    fly_get_words_launch(s, h->state, (float*)out_dev, n, w0, nw);
     HIPCHK(h, hipGetLastError());
     return 0;
   }
   switch (field) {
     case PIH_FIELD_STATE: HIPCHK(h, hipMemcpyAsync(out_dev, h->state, (size_t)n * PIH_STATE_WORDS * sizeof(float), hipMemcpyDeviceToDevice, s)); return 0;
-    case PIH_FIELD_TIP_POSE: hipLaunchKernelGGL(pih_gather_kernel, dim3((n * 7 + 255) / 256), dim3(256), 0, s, h->state, (float*)out_dev, n, (int)PIH_S_TIP, 7); break;
-    case PIH_FIELD_CONTACT_FORCE: hipLaunchKernelGGL(pih_gather_kernel, dim3((n + 255) / 256), dim3(256), 0, s, h->state, (float*)out_dev, n, (int)PIH_S_CFORCE, 1); break;
-    case PIH_FIELD_EE_POS: hipLaunchKernelGGL(pih_gather_kernel, dim3((n * 3 + 255) / 256), dim3(256), 0, s, h->state, (float*)out_dev, n, (int)PIH_S_EE, 3); break;
+    case PIH_FIELD_TIP_POSE: peg_gather_launch(s, h->state, (float*)out_dev, n, (int)PIH_S_TIP, 7); break;
+    case PIH_FIELD_CONTACT_FORCE: peg_gather_launch(s, h->state, (float*)out_dev, n, (int)PIH_S_CFORCE, 1); break;
+    case PIH_FIELD_EE_POS: peg_gather_launch(s, h->state, (float*)out_dev, n, (int)PIH_S_EE, 3); break;
     default: h->err = "pih_get_state: unknown field"; return -2;
   }
   HIPCHK(h, hipGetLastError());
@@ -803,8 +344,7 @@ int pih_set_state(pih_handle* h, int field, const void* in_dev, void* stream) {
   if (field != PIH_FIELD_STATE) { h->err = "pih_set_state: only PIH_FIELD_STATE is writable"; return -2; }
   PIH_ENTER(h);
   if (h->fly) {
-    const int n = h->cfg.n_envs;
-    hipLaunchKernelGGL(pih_aos_to_soa_kernel, dim3((n * PIH_FLY_STATE_WORDS + 255) / 256), dim3(256), 0, (hipStream_t)stream, (const float*)in_dev, h->state, n, PIH_FLY_STATE_WORDS);
+    fly_set_state_launch((hipStream_t)stream, (const float*)in_dev, h->state, h->cfg.n_envs);
     HIPCHK(h, hipGetLastError());
     return 0;
   }
@@ -815,7 +355,7 @@ int pih_set_state(pih_handle* h, int field, const void* in_dev, void* stream) {
 int pih_ik(pih_handle* h, int n, const float* q0_dev, const float* tpos_dev, const float* tquat_dev, float* qout_dev, void* stream) {
   if (!h || n <= 0 || !q0_dev || !tpos_dev || !tquat_dev || !qout_dev) return -2;
   PIH_ENTER(h);
-  hipLaunchKernelGGL(pih_ik_kernel, dim3((n + 15) / 16), dim3(64), 0, (hipStream_t)stream, h->P, n, q0_dev, tpos_dev, tquat_dev, qout_dev);
+  ik_launch(false, (hipStream_t)stream, h->P, n, q0_dev, tpos_dev, tquat_dev, qout_dev);
   HIPCHK(h, hipGetLastError());
   return 0;
 }
@@ -823,7 +363,7 @@ int pih_ik(pih_handle* h, int n, const float* q0_dev, const float* tpos_dev, con
 int pih_ik_ur5(pih_handle* h, int n, const float* q0_dev, const float* tpos_dev, const float* tquat_dev, float* qout_dev, void* stream) {
   if (!h || n <= 0 || !q0_dev || !tpos_dev || !tquat_dev || !qout_dev) return -2;
   PIH_ENTER(h);
-  hipLaunchKernelGGL(pih_ik_ur5_kernel, dim3((n + 15) / 16), dim3(64), 0, (hipStream_t)stream, h->P, n, q0_dev, tpos_dev, tquat_dev, qout_dev);
+  ik_launch(true, (hipStream_t)stream, h->P, n, q0_dev, tpos_dev, tquat_dev, qout_dev);
   HIPCHK(h, hipGetLastError());
   return 0;
 }
@@ -898,7 +438,7 @@ int pih_render_ex(pih_handle* h, float* out_dev, int width, int height, int env_
   PIH_ENTER(h);
   int rows; const int strips = render_strips(height, env_count, &rows);
   PIH_RENDER_CHECK(c.too_many());
-  hipLaunchKernelGGL(pih_render_kernel, dim3(strips, env_count), dim3(RENDER_THREADS), 0, (hipStream_t)stream, h->state, out_dev, env_begin, width, height, rows, flags);
+  render_launch(dim3(strips, env_count), (hipStream_t)stream, h->state, out_dev, env_begin, width, height, rows, flags);
   HIPCHK(h, hipGetLastError());
   return 0;
 }
@@ -919,8 +459,7 @@ int pih_render_cam(pih_handle* h, float* out_dev, const float* cam_ptr, int widt
   if (fmt || cam_on_device)
     fly_image_launch(fmt, dim3(strips, env_count), (hipStream_t)stream, h->state, out_dev, cam, cam_on_device ? cam_ptr : nullptr, h->cfg.n_envs, h->P.object, env_begin, width, height, rows, flags);
   else      // the float4 image of one host camera: the kernel it has always been
-    hipLaunchKernelGGL(pih_fly_render_kernel, dim3(strips, env_count), dim3(RENDER_THREADS), 0, (hipStream_t)stream, h->state, out_dev, cam,
-                       h->cfg.n_envs, h->P.object, env_begin, width, height, rows, flags);
+    fly_render_launch(dim3(strips, env_count), (hipStream_t)stream, h->state, out_dev, cam, h->cfg.n_envs, h->P.object, env_begin, width, height, rows, flags);
   HIPCHK(h, hipGetLastError());
   return 0;
 }
@@ -973,7 +512,7 @@ int pih_grasp_labels(pih_handle* h, float* out_dev, float* meta_dev, int size, i
   }
   if (h->fly) { h->err = "pih_grasp_labels: the grasp labels belong to the peg-in-hole task"; return -2; }
   PIH_ENTER(h);
-  hipLaunchKernelGGL(pih_labels_kernel, dim3((size * size + 1023) / 1024, env_count), dim3(256), 0, (hipStream_t)stream, h->state, out_dev, meta_dev, env_begin, size);
+  labels_launch((hipStream_t)stream, h->state, out_dev, meta_dev, env_begin, env_count, size);
   HIPCHK(h, hipGetLastError());
   return 0;
 }

@@ -15,6 +15,7 @@
 // instances are instruction for instruction what they were.  A change to render_strip or view::camera_setup has to be made here too.
 #include <hip/hip_runtime.h>
 #include "pih_lit.h"
+#include "pih_launch.h"
 
 using namespace pih;
 

@@ -1,6 +1,6 @@
 // pih_mailbox.h -- the handshake of the fused launch (round 4): the controller wavefronts and the step wavefronts of ONE grid meet
 // through a mailbox in HBM.  Used by both tasks: pih_step_kernel (reader: Wave::await_controller, pih_wave.h) and pih_fly_step_kernel
-// (reader: MailboxIk, pih_hip.hip); the host side (allocation, per-launch epoch and error check) is mailbox_alloc / next_epoch there.
+// (reader: MailboxIk, pih_fly.hip); the host side (allocation, per-launch epoch and error check) is mailbox_alloc / next_epoch of pih_hip.hip.
 //
 // A controller wavefront computes the outputs of its group of 64 envs, stores them into the mailbox (mail_store) and publishes the group
 // with mailbox_publish: the launch's epoch goes into the group's flag.  A step wavefront waits for that flag (mailbox_await), then reads

@@ -9,6 +9,7 @@
 // with cnt = min(64, n - 64 blockIdx.x) rows, and reads LDS words below cnt (W | 1) <= 64 (W | 1).
 #include <hip/hip_runtime.h>
 #include "pih_robot.h"
+#include "pih_launch.h"
 
 using namespace pih;
 using namespace pih::robot;

@@ -9,6 +9,7 @@
 // pih_lit_view_kernel (pih_lit.hip) has the same steps written out, with the light.
 #include <hip/hip_runtime.h>
 #include "pih_view.h"
+#include "pih_launch.h"
 
 using namespace pih;
 

@@ -381,6 +381,30 @@ PIH_HD void row16_sum3(real& a, real& b, real& c) {
 // picked at compile time; rec4v: words W .. W + 2 as a vector
 template <int W> PIH_HD real rec4(const real4* q) { constexpr int c = W % 4; return c == 0 ? q[W / 4].x : c == 1 ? q[W / 4].y : c == 2 ? q[W / 4].z : q[W / 4].w; }
 template <int W> PIH_HD V3 rec4v(const real4* q) { return mk(rec4<W>(q), rec4<W + 1>(q), rec4<W + 2>(q)); }
+// One arm joint block of the row-space solvers (pgs_rows, pgs_rows2): the motor row, then -- LIMITS -- the lower and the upper limit row,
+// in Bullet's order.  ca / cl: the joint's motor and limit record (MR_* / LR_*), y = dinv (J du) of the joint; la / llo / lhi: its three
+// wave-uniform multipliers.  Returns the motor row's step, d2 / d3 the limit rows' (0 without LIMITS); CHECK: the rows' exit test into busy.
+template <bool CHECK, bool LIMITS> PIH_HD real arm_joint_rows(const real4& ca, const real4& cl, real y, real& la, real& llo, real& lhi,
+                                                              unsigned long long& busy, real& d2, real& d3) {
+  const real rh = rec4<MR_RHS>(&ca), th = rec4<MR_THRESH>(&ca), lim = rec4<MR_IMP>(&ca);
+  const real lor = rec4<LR_LO>(&cl), hir = rec4<LR_HI>(&cl), wd = rec4<LR_JWDINV>(&cl);
+  real sum = la + (rh - y);
+  sum = med3_(sum, -lim, lim);
+  const real dl = sum - la; la = sum;
+  if (CHECK) busy |= __ballot(absr(dl) > th);
+  d2 = 0; d3 = 0;
+  if (LIMITS) {
+    y += dl * wd;
+    real s2 = llo + (lor - y); s2 = max_(s2, (real)0);
+    d2 = s2 - llo; llo = s2;
+    if (CHECK) busy |= __ballot(absr(d2) > th);
+    y += d2 * wd;
+    real s3 = lhi + (hir + y); s3 = max_(s3, (real)0);
+    d3 = s3 - lhi; lhi = s3;
+    if (CHECK) busy |= __ballot(absr(d3) > th);
+  }
+  return dl;
+}
 constexpr int FR = NMOT + 3 * MERGED_CONTACTS;
 PIH_HD int pgs_rows(Wave& w, Shared& sh, const Params& P) {
   const int nc = __builtin_amdgcn_readfirstlane(sh.nc);
@@ -590,25 +614,13 @@ PIH_HD int pgs_rows(Wave& w, Shared& sh, const Params& P) {
           } else {
             const real4 ca = pa4[j % PF], cl = pl4[j % PF];
             if (j + PF < 9) { pa4[j % PF] = *reinterpret_cast<const real4*>(sh.mrec[j + PF]); pl4[j % PF] = *reinterpret_cast<const real4*>(sh.lrec[j + PF]); }
-            const real rh = rec4<MR_RHS>(&ca), th = rec4<MR_THRESH>(&ca), lim = rec4<MR_IMP>(&ca);
-            const real lor = rec4<LR_LO>(&cl), hir = rec4<LR_HI>(&cl), wd = rec4<LR_JWDINV>(&cl);
-            real y = -rdlane(za, j);
-            real sum = lam_a[j] + (rh - y);
-            sum = med3_(sum, -lim, lim);
-            const real dl = sum - lam_a[j]; lam_a[j] = sum;
-            if (CHECK) busy |= __ballot(absr(dl) > th);
+            real d2, d3;
             if (FULL || j >= 7) {
-              y += dl * wd;
-              real s2 = lam_lo[j] + (lor - y); s2 = max_(s2, (real)0);
-              const real d2 = s2 - lam_lo[j]; lam_lo[j] = s2;
-              if (CHECK) busy |= __ballot(absr(d2) > th);
-              y += d2 * wd;
-              real s3 = lam_hi[j] + (hir + y); s3 = max_(s3, (real)0);
-              const real d3 = s3 - lam_hi[j]; lam_hi[j] = s3;
-              if (CHECK) busy |= __ballot(absr(d3) > th);
+              const real dl = arm_joint_rows<CHECK, true>(ca, cl, -rdlane(za, j), lam_a[j], lam_lo[j], lam_hi[j], busy, d2, d3);
               za += Bn[j] * (dl + d2 - d3);
             } else {
-              amax = max_(amax, absr(sum));                         // watched in EVERY iteration (one v_max): a multiplier may touch its bound and leave it again
+              const real dl = arm_joint_rows<CHECK, false>(ca, cl, -rdlane(za, j), lam_a[j], lam_lo[j], lam_hi[j], busy, d2, d3);
+              amax = max_(amax, absr(lam_a[j]));                    // watched in EVERY iteration (one v_max): a multiplier may touch its bound and leave it again
               za += Bn[j] * dl;
             }
           }
@@ -881,8 +893,9 @@ PIH_HD int pgs_rows2(Wave& w, Shared& sh, const Params& P, const Ovf& ov, const 
   __threadfence_block();                                     // the streamed columns: written above, read back by the same lane
   w.sync();
   // ---- solve (every limit row in place)
-  // (the arm joints' three multipliers -- motor, lower, upper limit -- are wave-uniform values in registers, as in pgs_rows: the
-  //  register budget is set by pgs_rows, and three v_readlane + three lane commits per joint and iteration were the price of lanes)
+  // (the arm joints' three multipliers -- motor, lower, upper limit -- are wave-uniform values in registers and the joint block is
+  //  arm_joint_rows, as in pgs_rows: the register budget is set by pgs_rows, and three v_readlane + three lane commits per joint and
+  //  iteration were the price of lanes)
   real lam0 = c0.lam0, lam1 = c1.lam0, z0, z1;
   real lam_a[9], lam_lo[9], lam_hi[9];
 #pragma unroll
@@ -915,21 +928,8 @@ PIH_HD int pgs_rows2(Wave& w, Shared& sh, const Params& P, const Ovf& ov, const 
       if (j < 9) {
         const real4 ca = pa4[j % PF], cl = pl4[j % PF];
         if (j + PF < 9) { pa4[j % PF] = *reinterpret_cast<const real4*>(sh.mrec[j + PF]); pl4[j % PF] = *reinterpret_cast<const real4*>(sh.lrec[j + PF]); }
-        const real rh = rec4<MR_RHS>(&ca), th = rec4<MR_THRESH>(&ca), lim = rec4<MR_IMP>(&ca);
-        const real lor = rec4<LR_LO>(&cl), hir = rec4<LR_HI>(&cl), wd = rec4<LR_JWDINV>(&cl);
-        real y = -rdlane(za, j);
-        real sum = lam_a[j] + (rh - y);
-        sum = med3_(sum, -lim, lim);
-        const real dl = sum - lam_a[j]; lam_a[j] = sum;
-        if (CHECK) busy |= __ballot(absr(dl) > th);
-        y += dl * wd;
-        real s2 = lam_lo[j] + (lor - y); s2 = max_(s2, (real)0);
-        const real d2 = s2 - lam_lo[j]; lam_lo[j] = s2;
-        if (CHECK) busy |= __ballot(absr(d2) > th);
-        y += d2 * wd;
-        real s3 = lam_hi[j] + (hir + y); s3 = max_(s3, (real)0);
-        const real d3 = s3 - lam_hi[j]; lam_hi[j] = s3;
-        if (CHECK) busy |= __ballot(absr(d3) > th);
+        real d2, d3;
+        const real dl = arm_joint_rows<CHECK, true>(ca, cl, -rdlane(za, j), lam_a[j], lam_lo[j], lam_hi[j], busy, d2, d3);
         const real tot = dl + d2 - d3;
         za += pk_lo(BB[j]) * tot; zp1 = pk_pack(pk_lo(zp1), pk_hi(zp1) + pk_hi(BB[j]) * tot);
       }

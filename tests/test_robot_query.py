@@ -341,7 +341,7 @@ def test_new_kernels_use_no_scratch():
     most 33.5 KB of LDS (the staged Panda link states)."""
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     import isa_fingerprint as fp
-    assert "pih_robot.hip" in fp.SOURCES
+    assert "pih_robot.hip" in fp.sources(ROOT)
     meta = fp.metadata(fp.assembly(ROOT, "pih_robot.hip"))
     kinds = ("pih_robot_fk_kernel", "pih_robot_jacobian_kernel", "pih_robot_mass_kernel", "pih_robot_invdyn_kernel")
     assert len(meta) == 3 * 4 + 2 + 2, sorted(meta)       # three queries x two robots x direct / staged, inverse dynamics x two robots, two link-state kernels

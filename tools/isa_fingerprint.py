@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Fingerprint of the gfx950 code of every kernel of the library (pih_hip.hip, pih_fly_image.hip, pih_view.hip, pih_lit.hip, pih_robot.hip), without a GPU: one line per kernel with a hash of its instruction
+"""Fingerprint of the gfx950 code of every kernel of the library (every csrc/*.hip of the tree), without a GPU: one line per kernel with a hash of its instruction
 stream, the instruction count and the VGPR / AGPR / SGPR / LDS / scratch numbers of the code object metadata.  A refactor that leaves
 the lines of the hot kernels unchanged leaves their speed unchanged (the step kernels sit at the 256-register limit).
 Used that way for the camera kernels' shared pieces (one tile walk, one scene set-up per task: DESIGN.md 6.5): both listings are
@@ -9,6 +9,7 @@ index, the light hook under a thread test outside or inside the hook -- that dif
 then checked on the GPU: outputs byte for byte against the parent's build, times against the parent's spread (which sent
 pih_lit_view_kernel back to its own copy of the walk: its three lines are the parent's again).
 usage: python tools/isa_fingerprint.py [SOURCE_TREE]    (default: this checkout; e.g. a `git worktree add` of another commit)"""
+import glob
 import hashlib
 import os
 import re
@@ -23,10 +24,12 @@ from peg_in_hole_gym_amd.csrc.build import FLAGS  # noqa: E402
 META = ("vgpr_count", "agpr_count", "sgpr_count", "group_segment_fixed_size", "private_segment_fixed_size")
 
 
-SOURCES = ("pih_hip.hip", "pih_fly_image.hip", "pih_view.hip", "pih_lit.hip", "pih_robot.hip")       # the library's translation units (a tree from before one existed is read without it)
+def sources(tree):
+    """the translation units of a tree: every csrc/*.hip it has (another commit's tree has its own set)"""
+    return sorted(os.path.basename(p) for p in glob.glob(os.path.join(tree, "peg_in_hole_gym_amd", "csrc", "*.hip")))
 
 
-def assembly(tree, name="pih_hip.hip"):
+def assembly(tree, name):
     src = os.path.join(tree, "peg_in_hole_gym_amd", "csrc", name)
     with tempfile.TemporaryDirectory() as d:
         out = os.path.join(d, "out.s")
@@ -72,9 +75,9 @@ def metadata(asm):
 def main():
     tree = os.path.abspath(sys.argv[1]) if len(sys.argv) > 1 else ROOT
     meta, body = {}, {}
-    for src in SOURCES:
-        if os.path.exists(os.path.join(tree, "peg_in_hole_gym_amd", "csrc", src)):
-            asm = assembly(tree, src)
+    for src in sources(tree):
+        asm = assembly(tree, src)
+        if "amdhsa.kernels:" in asm:      # (a translation unit of host code alone has none)
             meta.update(metadata(asm)); body.update(kernels(asm))
     print("%-16s %6s  %4s %4s %4s %6s %4s  %s" % ("sha256[:16]", "instr", "vgpr", "agpr", "sgpr", "lds", "scr", "kernel"))
     for name, ins in sorted(body.items()):
