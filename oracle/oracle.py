@@ -205,6 +205,10 @@ class Oracle:
     def debug_udot(self, env=0):
         out = np.zeros(NDOF); self.L.piho_debug_udot(self.h, env, _dp(out)); return out
 
+    def debug_row_jw(self, env=0):
+        """J M^-1 J^T [CMAX, 3] of the contact rows (normal, t1, t2) of the last step; rows past the contact count are stale"""
+        out = np.zeros((CMAX, 3), self.real); self.L.piho_debug_row_jw(C.c_void_p(self.h), env, _dp(out)); return out
+
 
 # ---- stand-alone primitives
 def fk_arm(q, link=9):
@@ -248,6 +252,17 @@ def mass_matrix(state):
 def free_accel(state, cfg=None):
     cfg = cfg or default_config(); s = np.ascontiguousarray(state, dtype=np.float64); ud = np.zeros(NDOF)
     lib().piho_free_accel(C.byref(cfg), _dp(s), _dp(ud)); return ud
+
+
+def contact_row_response(state, linkA, linkB, p, normal, mu):
+    """J M^-1 J^T [n, 3] of the normal, t1 and t2 row of n contacts (links, point, normal, mu as in the rows of debug_contacts) at `state`,
+    by the row code of piho_step"""
+    s = np.ascontiguousarray(state, dtype=np.float64)
+    la = np.ascontiguousarray(linkA, dtype=np.int32); lb = np.ascontiguousarray(linkB, dtype=np.int32); n = len(la)
+    p = np.ascontiguousarray(p, dtype=np.float64).reshape(n, 3); nn = np.ascontiguousarray(normal, dtype=np.float64).reshape(n, 3)
+    mu = np.ascontiguousarray(mu, dtype=np.float64).reshape(n); jw = np.zeros((n, 3))
+    ip = C.POINTER(C.c_int32)
+    lib().piho_contact_row_response(_dp(s), C.c_int(n), la.ctypes.data_as(ip), lb.ctypes.data_as(ip), _dp(p), _dp(nn), _dp(mu), _dp(jw)); return jw
 
 
 def vel_constraint(cur, tar, dv):

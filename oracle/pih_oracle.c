@@ -476,6 +476,7 @@ typedef struct {
   real mu_clamp;                  /* copy of the handle's variant.mu_clamp for add_contact */
   real lambda_t[CMAX][2];         /* friction multipliers of the last step (diagnostics: tools/ill_conditioned_causes.py) */
   int nclamped;                   /* coordinate velocities that hit +-max_coord_vel in the last step */
+  real row_jw[CMAX][3];           /* J M^-1 J^T of the normal, t1 and t2 row of every contact of the last step */
 } Env;
 #ifdef _OPENMP
 #include <omp.h>
@@ -782,6 +783,20 @@ static void plane_space(const v3 n, v3 p, v3 q) {
 /* ------------------------------------------------------------------------------------------ step */
 typedef struct { real J[ND], W[ND]; real rhs, dinv, lo, hi, lambda, mu; int fparent; } Row;
 
+/* one row of a contact along `dir` (its normal or one of plane_space's tangents): J, W = M^-1 J (M factored), returns J W.  The rows of
+ * the attach weld (mu < -1.5) are angular.  Shared by step_env and the stand-alone piho_contact_row_response. */
+static real contact_row(const LinkKin* K, const real* M, const Contact* ct, const real* dir, Row* r) {
+  memset(r, 0, sizeof *r);
+  if (ct->mu < -1.5) { jac_row_ang(K, ct->linkA, dir, 1.0, r->J); if (ct->linkB >= 0) jac_row_ang(K, ct->linkB, dir, -1.0, r->J); }
+  else {
+    jac_row(K, ct->linkA, ct->p, dir, 1.0, r->J);
+    if (ct->linkB >= 0) jac_row(K, ct->linkB, ct->p, dir, -1.0, r->J);
+  }
+  memcpy(r->W, r->J, sizeof r->J); minv_apply(M, r->W);
+  real jw = 0; for (int k = 0; k < ND; k++) jw += r->J[k] * r->W[k];
+  return jw;
+}
+
 static void controller(const piho_config* c, Env* E, const real* action, const LinkKin* K,
                        real* mt_target, real* mt_kp, real* mt_maximp, int* mt_posctl, real pipe_motor_impulse) {
   real* s = E->s;
@@ -902,15 +917,10 @@ static void step_env(piho_handle* h, int e, const real* action, real* obs, real*
     for (int rep = 0; rep < 3; rep++) {
       const real* dir = rep == 0 ? ct->n : (rep == 1 ? t1 : t2);
       Row* r = &rows[nr++];
-      memset(r, 0, sizeof *r);
       const int ang = ct->mu < -1.5;                            /* angular rows of the attach weld */
-      if (ang) { jac_row_ang(K, ct->linkA, dir, 1.0, r->J); if (ct->linkB >= 0) jac_row_ang(K, ct->linkB, dir, -1.0, r->J); }
-      else {
-        jac_row(K, ct->linkA, ct->p, dir, 1.0, r->J);
-        if (ct->linkB >= 0) jac_row(K, ct->linkB, ct->p, dir, -1.0, r->J);
-      }
-      memcpy(r->W, r->J, sizeof r->J); minv_apply(M, r->W);
-      real jw = 0, ju = 0; for (int k = 0; k < ND; k++) { jw += r->J[k] * r->W[k]; ju += r->J[k] * u[k]; }
+      const real jw = contact_row(K, M, ct, dir, r);
+      E->row_jw[i][rep] = jw;
+      real ju = 0; for (int k = 0; k < ND; k++) ju += r->J[k] * u[k];
       r->dinv = 1.0 / jw;
       if (rep == 0) {
         real pen = ct->depth + c->linear_slop;
@@ -1276,6 +1286,19 @@ void piho_free_accel(const piho_config* c, const real state[128], real udot[38])
   for (int i = 0; i < ND; i++) udot[i] = -bias[i];
   minv_apply(M, udot);
 }
+void piho_contact_row_response(const real state[128], int n, const int32_t* linkA, const int32_t* linkB, const real* p, const real* normal, const real* mu, real* jw) {
+  LinkKin K[NL]; static real M[ND * ND];
+  fk(&state[PIHO_S_QARM], &state[PIHO_S_POS], &state[PIHO_S_QUAT], &state[PIHO_S_QJ], 0, NL, K);
+  mass_matrix(K, M); cholesky(M, 9, ND); cholesky(M + 9 * ND + 9, 29, ND);
+  for (int i = 0; i < n; i++) {
+    Contact ct; Row r; v3 t1, t2;
+    ct.linkA = linkA[i]; ct.linkB = linkB[i]; ct.key = 0; ct.depth = 0; ct.mu = mu[i];
+    v_cp(ct.p, p + 3 * i); v_cp(ct.n, normal + 3 * i);
+    plane_space(ct.n, t1, t2);
+    for (int rep = 0; rep < 3; rep++) jw[3 * i + rep] = contact_row(K, M, &ct, rep == 0 ? ct.n : (rep == 1 ? t1 : t2), &r);
+  }
+}
+void piho_debug_row_jw(const piho_handle* h, int env, real* out) { memcpy(out, h->env[env].row_jw, sizeof(real) * CMAX * 3); }
 int piho_real_bytes(void) { return (int)sizeof(real); }
 
 #include "pih_fly_oracle.c"   /* the 'random-fly' task (UR5 + free-flying object); shares the static helpers above */

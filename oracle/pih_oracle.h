@@ -123,6 +123,11 @@ void piho_jacobian_ur5(const piho_real q[6], piho_real Jlin[18], piho_real Jang[
 void piho_ik_ur5(const piho_config* c, const piho_real q0[6], const piho_real tpos[3], const piho_real tquat[4], piho_real qout[6]);
 void piho_mass_matrix(const piho_real state[128], piho_real M[38 * 38]);
 void piho_free_accel(const piho_config* c, const piho_real state[128], piho_real udot[38]);
+/* J M^-1 J^T of the normal, t1 and t2 row of n contacts at `state`, by the row code of piho_step (plane_space; angular rows where
+ * mu < -1.5).  Not the reciprocal: a friction row along the joint axes of a planar pipe is null. */
+void piho_contact_row_response(const piho_real state[128], int n, const int32_t* linkA, const int32_t* linkB,
+                               const piho_real* p /* [n,3] */, const piho_real* normal /* [n,3] */, const piho_real* mu /* [n] */,
+                               piho_real* jw /* [n,3] */);
 void piho_vel_constraint(const piho_real cur[3], const piho_real tar[3], piho_real dv, piho_real out[3]);
 void piho_rotate_vector(const piho_real v[3], const piho_real q[4], piho_real out[3]);
 void piho_quat_from_euler(const piho_real rpy[3], piho_real q[4]);
@@ -131,6 +136,7 @@ int piho_fsm_update(piho_real* state, piho_real* t, piho_real dt);   /* envs/peg
 void piho_env_offsets(const piho_real offset[3], int n, piho_real* out /* [n,3] */);   /* envs/base_env.py:35-55 */
 /* debug: contact list + solver rows of env 0 from the last step */
 int piho_debug_contacts(const piho_handle* h, int env, piho_real* out /* [CMAX,12]: linkA linkB px py pz nx ny nz depth mu key lambda_n */);
+void piho_debug_row_jw(const piho_handle* h, int env, piho_real* out /* [CMAX,3] J M^-1 J^T of the contact rows of the last step */);
 void piho_debug_udot(const piho_handle* h, int env, piho_real* out /* [38] free acceleration of the last step */);
 
 /* ---------------------------------------------------------------------------------------------------------------------

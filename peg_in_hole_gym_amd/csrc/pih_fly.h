@@ -683,7 +683,7 @@ PIH_HD void step_env(real* S, const Params& P, int env_global, const real* actio
     stamp(5);
     // ---- integrate
 #pragma unroll
-    for (int i = 0; i < FND; i++) u[i] = clampr(u[i] + du[i], -PIH_MAX_COORD_VEL, PIH_MAX_COORD_VEL);
+    for (int i = 0; i < FND; i++) u[i] = clamp_vel(u[i] + du[i], PIH_MAX_COORD_VEL);
 #pragma unroll
     for (int i = 0; i < NJ; i++) { S[PIH_F_QD + i] = u[i]; S[PIH_F_Q + i] = q[i] + dt * u[i]; }
 #pragma unroll

@@ -46,6 +46,9 @@ PIH_HD real rsqrt_(real x) { return (real)1 / (real)sqrt(x); }
 PIH_HD real norm(V3 a) { return (real)sqrt(dot(a, a)); }
 PIH_HD real clampr(real x, real lo, real hi) { return x < lo ? lo : (x > hi ? hi : x); }
 PIH_HD real absr(real x) { return x < 0 ? -x : x; }
+// the clamp of a coordinate velocity to +-lim.  A value that is not finite_small passes as it is, so that the finiteness test at the end of
+// the step sees it: under -ffast-math the compiler builds clampr from min / max, which answer a NaN with a bound
+PIH_HD real clamp_vel(real v, real lim) { return finite_small(v) ? clampr(v, -lim, lim) : v; }
 
 // 3x3 row-major
 struct M3 { real m[9]; };

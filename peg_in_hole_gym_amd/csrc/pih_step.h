@@ -140,7 +140,7 @@ PIH_HD void step_env(W& w, Shared& sh, const Params& P, const Ovf& ov, int env, 
     // integrate + bookkeeping
     w.par(ND, [&](int d) {
       real v = sh.u[d];
-      v = clampr(v, -PIH_MAX_COORD_VEL, PIH_MAX_COORD_VEL);   // Bullet m_maxCoordinateVelocity, floating base included
+      v = clamp_vel(v, PIH_MAX_COORD_VEL);   // Bullet m_maxCoordinateVelocity, floating base included
       if (d < 9) { S[PIH_S_QDARM + d] = v; S[PIH_S_QARM + d] += dt * v; }
       else if (d < 12) { S[PIH_S_VLIN + d - 9] = v; S[PIH_S_POS + d - 9] += dt * v; }
       else if (d < 15) S[PIH_S_VANG + d - 12] = v;

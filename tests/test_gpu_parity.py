@@ -6,6 +6,7 @@ import pytest
 
 from peg_in_hole_gym_amd import _lib
 from tests import parity_util as P
+from tests import step_stage_cases as G
 
 pytestmark = pytest.mark.gpu
 
@@ -73,6 +74,7 @@ def test_one_step_parity_resynchronised(torch_mod, oracle_mod):
     rng = np.random.default_rng(0)
     perr, ferr = [], []
     hist = np.zeros(49, int)
+    accel = {grp: 0.0 for grp in G.GROUPS}
     for t in range(300):
         a = rng.uniform(-1, 1, (N, 4))
         _to_gpu_state(torch, g, o.get_state()); led.before(o)
@@ -83,6 +85,9 @@ def test_one_step_parity_resynchronised(torch_mod, oracle_mod):
         ud = np.array([o.debug_udot(i) for i in range(N)])
         dbg = g.debug().cpu().numpy()
         assert (np.abs(ud - dbg[:, _lib.DBG_UDOT:_lib.DBG_UDOT + 38]).max(1) <= 1e-3 * (1 + np.abs(ud).max(1))).all()     # free acceleration, fp32
+        for grp, fig in G.accel_group_metric(dbg[:, _lib.DBG_UDOT:_lib.DBG_UDOT + 38], ud).items():               # ... per DOF group: a pipe joint's 1e6 rad/s^2 does not hide the arm
+            accel[grp] = max(accel[grp], fig)
+            assert fig <= G.GPU_FACTOR * G.MEASURED["accel"][grp], (t, grp, fig)
         np.testing.assert_array_equal(o.ncontacts(), sg[:, _lib.S_NCONTACT].astype(int))               # same contact sets
         np.testing.assert_array_equal(dg.cpu().numpy(), do)
         np.testing.assert_allclose(og.cpu().numpy()[:, 2:], oo[:, 2:], atol=1e-4)          # ee position
@@ -90,6 +95,7 @@ def test_one_step_parity_resynchronised(torch_mod, oracle_mod):
         cf = o.contact_force(); ferr.append(np.abs(sg[:, _lib.S_CFORCE] - cf) / (1 + np.abs(cf)))
         led.after(o, a, perr[-1], ferr[-1])
     print("contact-count histogram (env-steps per count):", hist[:hist.nonzero()[0].max() + 1].tolist())
+    print("free acceleration per DOF group, max|err| / (1 + max|ref|):", {k: "%.2e" % v for k, v in accel.items()})
     # both sides of the merged first response pass (MERGED_CONTACTS = 10: <= 10 contacts take one sweep, 11 take two)
     assert hist[10] > 20 and hist[11] > 20 and hist[9] > 20 and hist[12] > 20
     led.finish("one-step resynchronised N=32")

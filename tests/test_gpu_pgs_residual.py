@@ -119,7 +119,13 @@ def test_non_finite_pipe_velocity(rolled, pair64):
     d, n = pair64(bad)
     assert np.isfinite(d["state"]).all()
     print("NaN env %d: PIH_S_SOLVER default path %d, schedule + 64 path %d" % (e, d["state"][e, _lib.S_SOLVER], n["state"][e, _lib.S_SOLVER]))
-    assert d["state"][e, _lib.S_SOLVER] == 4      # the NaN reached the bit-pattern check, which sent the env to the clamped rows
+    # the env is reset, counted and reported on both paths: the velocity clamp of the step's tail passes a non-finite value on to the
+    # finiteness test (it used to answer a NaN with a bound, and the env went on with +-100 rad/s).  The reset clears PIH_S_SOLVER, so
+    # which rows ran is no longer visible in the record; that the speculation cannot accept the NaN shows in the equality with the
+    # schedule + 64 path below
+    for x in (d, n):
+        assert x["state"][e, _lib.S_SPARE] == ref["state"][e, _lib.S_SPARE] + 1 and x["done"][e] == 1 and x["invalid"][e] and x["state"][e, _lib.S_DONE] == 1
+        assert x["state"][e, _lib.S_STEPS] == 0 and x["state"][e, _lib.S_SOLVER] == 0
     others = np.arange(64) != e
     np.testing.assert_array_equal(d["state"][others], ref["state"][others])
     for k in ("obs", "reward", "done"):
@@ -128,7 +134,6 @@ def test_non_finite_pipe_velocity(rolled, pair64):
     np.testing.assert_array_equal(d["state"][e][NOT_SOLVER], n["state"][e][NOT_SOLVER])
     for k in ("obs", "reward", "done", "invalid"):
         np.testing.assert_array_equal(d[k][e], n[k][e])
-    # (whether that is a reset at all is the clamped rows' business: v_med3 drops a NaN operand, the motor row then holds its bound)
     assert d["state"][e, _lib.S_SPARE] == n["state"][e, _lib.S_SPARE]
 
 
