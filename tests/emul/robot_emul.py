@@ -8,12 +8,11 @@ import subprocess
 
 import numpy as np
 
+from tests.emul.render_emul import CXX, CXXFLAGS
+
 _DIR = os.path.dirname(os.path.abspath(__file__))
-CXX = os.environ.get("CXX", "g++")
-# CXXFLAGS of tests/emul/Makefile
-CXXFLAGS = ["-O2", "-fPIC", "-Wl,-Bsymbolic", "-fno-gnu-unique", "-fvisibility-inlines-hidden", "-std=c++17", "-Wall", "-Wno-unused-variable",
-            "-Wno-unused-but-set-variable", "-Wno-unknown-pragmas", "-fno-fast-math"]
-# ... of its sanitizer build
+# (the default CXXFLAGS of tests/emul/Makefile)
+# the flags of the Makefile's sanitizer build
 SANFLAGS = ["-O1", "-g", "-std=c++17", "-fno-fast-math", "-Wno-unknown-pragmas", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"]
 PANDA, UR5 = 0, 1
 

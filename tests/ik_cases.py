@@ -17,12 +17,11 @@ at the product.
   D  sign symmetry   the class A problems at the default config with tquat AND with -tquat: the two results agree.
 """
 import functools
-import os
-import re
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests.render_ref import macro as _macro          # the one reader of include/pih_model.h
+
 CHAINS = ("ur5", "panda")
 DEFAULT = (0.5, 20)                                                      # (ik_damping, ik_iters) of pih_default_config
 CONFIGS_A = ((0.5, 20), (0.5, 1), (0.5, 50), (0.05, 1), (0.05, 3))       # low damping for few iterations only: at (0.05, 50) the fp64 oracle itself amplifies 1e-12 to 6e-7
@@ -34,12 +33,6 @@ SEEDS = {("ur5", "A"): 6, ("panda", "A"): 0, ("ur5", "B"): 2, ("panda", "B"): 3,
 ARM = {"ur5": 6, "panda": 7}                                             # joints the IK moves
 WORDS = {"ur5": 6, "panda": 9}                                           # words of a pih_ik_ur5 / pih_ik problem (Panda: + two finger entries)
 FINGER = 0.02
-
-
-def _macro(name):
-    hdr = open(os.path.join(ROOT, "include", "pih_model.h")).read()
-    body = re.search(r"#define %s (.*)" % name, hdr).group(1).split("/*")[0]
-    return np.array(eval(body.replace("{", "[").replace("}", "]")), dtype=float)
 
 
 def f32(x):

@@ -70,3 +70,25 @@ class OracleBackend:
 
 def factory(n, offsets, **cfg):
     return OracleBackend(n, offsets, **cfg)
+
+
+class RecordingBackend:
+    """a backend that computes nothing: it records the keywords the task classes forward to render, render_view and link_states"""
+
+    def __init__(self, n, offsets, **cfg):
+        self.n, self.cfg, self.calls = n, cfg, []
+
+    def reset(self, mask=None, hard_reset=False):
+        pass
+
+    def render(self, width=300, height=300, **kw):
+        self.calls.append(dict(width=width, height=height, **kw))
+        return np.full((self.n, height, width, 4), 7.0, dtype=np.float32)
+
+    def render_view(self, **kw):
+        self.calls.append(kw)
+        return "image"
+
+    def link_states(self, **kw):
+        self.calls.append(kw)
+        return "states"

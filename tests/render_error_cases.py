@@ -4,6 +4,7 @@ A row is (entry point, task of the handle, case name, arguments); an argument le
 import ctypes as C
 
 from peg_in_hole_gym_amd import _lib
+from tests.render_cases import BAD_LIGHTS, DEGENERATE, camera_with
 
 N, W, H = 3, 16, 8          # envs per handle, image size
 SHADED, EE, RGBA8, DEPTH, CAM_DEV, EE_POS, LIGHT_DEV = (_lib.RENDER_SHADED, _lib.RENDER_CAM_EE, _lib.RENDER_OUT_RGBA8, _lib.RENDER_OUT_DEPTH,
@@ -18,8 +19,6 @@ ENTRIES = (("pih_render", "peg", False, False, False), ("pih_render_ex", "peg", 
 
 
 def table():
-    from tests.test_fly_image import DEGENERATE, camera_with
-    from tests.test_render_lit import BAD_LIGHTS
     rows = []
     for entry, task, has_flags, has_cam, has_light in ENTRIES:
         other = "fly" if task == "peg" else "peg"

@@ -1,16 +1,15 @@
 """Output formats and per-env cameras of the random-fly camera on the GPU: pih_render_cam with PIH_RENDER_OUT_RGBA8, PIH_RENDER_OUT_DEPTH
 and PIH_RENDER_CAM_DEVICE through PihVecEnv.render(fmt=..., camera=[count, 13]) and PihVecEnv.tracking_cameras, against the numpy fp64
-ray caster of tests/test_fly_render.py.  Rules, caps and the per-env-camera cases come from tests/test_fly_image.py (`I`), where the fp32
-host build of the same per-pixel code meets them first; the caps themselves are those of tests/test_gpu_fly_render.py (`G`)."""
+ray caster of tests/render_ref.py.  Rules, caps and the per-env-camera cases come from tests/render_cases.py; the fp32 host build of the
+same per-pixel code meets them first in tests/test_fly_image.py."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
 from peg_in_hole_gym_amd import _lib
-from tests import test_fly_image as I
-from tests import test_fly_render as T
-from tests import test_gpu_fly_render as G
+from tests import render_cases as RC
+from tests import render_ref as R
 
 GUARD = 4096
 
@@ -46,36 +45,37 @@ def _render_guarded(torch, g, W, H, fmt, count=None, **kw):
     return res
 
 
-def _check_packed(O, fig, rgba_flat, rgba_lit, depth, rec, cam, ee, obj, ref):
+def _check_packed(scene, fig, rgba_flat, rgba_lit, depth, cam, frame, ref):
     """one env's three images against the reference, into the running figures"""
     assert np.array_equal(rgba_flat[..., 3], rgba_lit[..., 3])                             # shading does not touch the segmentation
-    same = I.check_seg(O, rgba_flat[..., 3], rec, cam, ee, ref, exact=False)
-    fig.add_depth(I.depth_errors(depth, same, ref, cam))
-    fig.add_colour(I.colour_excess(rgba_flat[..., :3], same, ref[0]), False)
-    fig.add_colour(I.colour_excess(rgba_lit[..., :3], same, ref[1]), True)
+    same = RC.check_seg(scene, rgba_flat[..., 3], cam, frame, ref, exact=False)
+    fig.add_depth(RC.depth_errors(depth, same, ref, cam))
+    fig.add_colour(RC.colour_excess(rgba_flat[..., :3], same, ref[0]), False)
+    fig.add_colour(RC.colour_excess(rgba_lit[..., :3], same, ref[1]), True)
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("obj", [0, 1])
 def test_formats_all_cameras_and_sizes(torch_mod, oracle_mod, obj):
-    """N = 6, the four cameras, T.SIZES plus (5, 3): rgba8 flat and shaded, and depth, every env against the reference fed with the handle's
+    """N = 6, the four cameras, RC.SIZES plus (5, 3): rgba8 flat and shaded, and depth, every env against the reference fed with the handle's
     own state(); every call writes into a guarded view"""
     n = 6
-    g = G._gpu(n, object_id=obj)
-    fig = I.Figures()
-    for name in T.CAMERA_NAMES:
-        g.set_state(torch_mod.tensor(T.make_states(oracle_mod, obj, n, seed=G.SCENE_SEED[(obj, name)], eye_in_hand=name == "eye-in-hand")))
+    g = RC.fly_handle(n, object_id=obj)
+    fig = RC.Figures()
+    for name in RC.FLY_CAMERA_NAMES:
+        g.set_state(torch_mod.tensor(RC.make_fly_states(oracle_mod, obj, n, seed=RC.SCENE_SEED[(obj, name)], eye_in_hand=name == "eye-in-hand")))
         st = g.state().cpu().numpy()
-        for (W, H) in I.SIZES:
-            cam, ee = T.cameras(W, H)[name]
-            flat = _render_guarded(torch_mod, g, W, H, "rgba8", camera=cam, ee_frame=ee)
-            lit = _render_guarded(torch_mod, g, W, H, "rgba8", camera=cam, ee_frame=ee, shaded=True)
-            depth = _render_guarded(torch_mod, g, W, H, "depth", camera=cam, ee_frame=ee)
-            assert np.array_equal(depth, _render_guarded(torch_mod, g, W, H, "depth", camera=cam, ee_frame=ee, shaded=True))
+        for (W, H) in RC.IMAGE_SIZES:
+            cam, frame = RC.fly_cameras(W, H)[name]
+            flat = _render_guarded(torch_mod, g, W, H, "rgba8", camera=cam, ee_frame=frame == "ee")
+            lit = _render_guarded(torch_mod, g, W, H, "rgba8", camera=cam, ee_frame=frame == "ee", shaded=True)
+            depth = _render_guarded(torch_mod, g, W, H, "depth", camera=cam, ee_frame=frame == "ee")
+            assert np.array_equal(depth, _render_guarded(torch_mod, g, W, H, "depth", camera=cam, ee_frame=frame == "ee", shaded=True))
             for e in range(n):
-                ref = T.reference_render(oracle_mod, st[e], cam, obj, W, H, ee)
-                T.check_reference_scene(name, W, H, ref[2], obj)
-                _check_packed(oracle_mod, fig, flat[e], lit[e], depth[e], st[e], cam, ee, obj, ref)
+                scene = R.fly_scene(oracle_mod, st[e], obj)
+                ref = R.plain_reference(scene, cam, W, H, frame)
+                RC.fly_check_reference_scene(name, W, H, ref[2], obj)
+                _check_packed(scene, fig, flat[e], lit[e], depth[e], cam, frame, ref)
     print("object %d: %s" % (obj, fig.text()))
     fig.limits()
 
@@ -83,21 +83,21 @@ def test_formats_all_cameras_and_sizes(torch_mod, oracle_mod, obj):
 @pytest.mark.gpu
 def test_depth_plane_is_the_float4_depth(torch_mod, oracle_mod):
     n, obj = 6, 0
-    g = G._gpu(n, object_id=obj)
-    g.set_state(torch_mod.tensor(T.make_states(oracle_mod, obj, n, seed=G.SCENE_SEED[(obj, "close-up")])))
+    g = RC.fly_handle(n, object_id=obj)
+    g.set_state(torch_mod.tensor(RC.make_fly_states(oracle_mod, obj, n, seed=RC.SCENE_SEED[(obj, "close-up")])))
     worst = 0.0
-    for (W, H) in I.SIZES:
-        cam, ee = T.cameras(W, H)["close-up"]
+    for (W, H) in RC.IMAGE_SIZES:
+        cam, frame = RC.fly_cameras(W, H)["close-up"]
         depth = g.render(W, H, camera=cam, fmt="depth").cpu().numpy()
         img = g.render(W, H, camera=cam).cpu().numpy()
         assert depth.shape == (n, H, W) and depth.dtype == np.float32
         worst = max(worst, float(np.abs(depth - img[..., 0]).max()))
     print("max |depth plane - float4 channel 0| = %.3e (0 expected)" % worst)
-    assert worst <= G.DEPTH_VALUE_TOL
+    assert worst <= RC.FLY_DEPTH_VALUE_TOL
 
 
 def _case_handle(torch, case):
-    g = G._gpu(len(case["states"]), object_id=case["obj"])
+    g = RC.fly_handle(len(case["states"]), object_id=case["obj"])
     g.set_state(torch.tensor(case["states"]))
     return g, g.state().cpu().numpy(), torch.tensor(case["cams"], device="cuda")
 
@@ -105,9 +105,9 @@ def _case_handle(torch, case):
 @pytest.mark.gpu
 def test_per_env_cameras(torch_mod, oracle_mod):
     """N = 70: the camera of env e is row e of a device tensor (three cameras in turn); the full range and env_begin = 3, env_count = 5,
-    where row e belongs to env 3 + e.  The envs of I.per_env_cases against the reference rendered with their own row, and against a call
+    where row e belongs to env 3 + e.  The envs of RC.per_env_cases against the reference rendered with their own row, and against a call
     with that row as the one host camera."""
-    case = I.per_env_cases(oracle_mod)["cycle"]
+    case = RC.per_env_cases(oracle_mod)["cycle"]
     (W, H), obj, cams = case["size"], case["obj"], case["cams"]
     g, st, cams_dev = _case_handle(torch_mod, case)
     f4 = _render_guarded(torch_mod, g, W, H, "float4", camera=cams_dev)
@@ -117,41 +117,43 @@ def test_per_env_cameras(torch_mod, oracle_mod):
     assert np.array_equal(_render_guarded(torch_mod, g, W, H, "float4", count=5, env_begin=3, camera=sub), f4[3:8])
     assert np.array_equal(_render_guarded(torch_mod, g, W, H, "rgba8", count=5, env_begin=3, camera=sub), u8[3:8])
     assert np.array_equal(g.render(W, H, camera=cams[3:8].tolist(), env_begin=3, env_count=5, fmt="rgba8").cpu().numpy(), u8[3:8])      # converted and uploaded
-    fig = I.Figures(); zmax = dmax = cmax = 0.0; identical = True
+    fig = RC.Figures(); zmax = dmax = cmax = 0.0; identical = True
     for e in case["checked"]:
-        ref = T.reference_render(oracle_mod, st[e], cams[e], obj, W, H, False)
-        same = I.check_seg(oracle_mod, u8[e][..., 3], st[e], cams[e], False, ref, exact=False)
-        fig.add_depth(I.depth_errors(dp[e], same, ref, cams[e]))
-        fig.add_colour(I.colour_excess(u8[e][..., :3], same, ref[0]), False)
-        z, d, c = T.compare(f4[e].astype(np.float64), f4[e].astype(np.float64), ref[0], ref[2], ref[3], cams[e], obj, exact_class=False)
+        scene = R.fly_scene(oracle_mod, st[e], obj)
+        ref = R.plain_reference(scene, cams[e], W, H)
+        same = RC.check_seg(scene, u8[e][..., 3], cams[e], "env", ref, exact=False)
+        fig.add_depth(RC.depth_errors(dp[e], same, ref, cams[e]))
+        fig.add_colour(RC.colour_excess(u8[e][..., :3], same, ref[0]), False)
+        z, d, c = RC.compare(f4[e].astype(np.float64), R.classify(f4[e].astype(np.float64), obj), ref[0], ref[2], ref[3], cams[e], R.BG, exact_class=False)
         zmax = max(zmax, z); dmax = max(dmax, d); cmax = max(cmax, c.max())
         # the same env with its row as the single host camera
         one4 = g.render(W, H, camera=cams[e].tolist(), env_begin=e, env_count=1).cpu().numpy()[0]
         one8 = g.render(W, H, camera=cams[e].tolist(), env_begin=e, env_count=1, fmt="rgba8").cpu().numpy()[0]
         identical = identical and np.array_equal(one4, f4[e]) and np.array_equal(one8, u8[e])
         agree = one8[..., 3] == u8[e][..., 3]
-        assert (~agree).mean() <= T.CLASS_SHARE and np.array_equal(one8[agree], u8[e][agree])
-        assert np.abs(one4[..., 0] - f4[e][..., 0])[agree].max() <= G.DEPTH_VALUE_TOL and np.abs(one4[..., 1:] - f4[e][..., 1:])[agree].max() <= G.COLOUR_TOL
+        assert (~agree).mean() <= RC.CLASS_SHARE and np.array_equal(one8[agree], u8[e][agree])
+        assert np.abs(one4[..., 0] - f4[e][..., 0])[agree].max() <= RC.FLY_DEPTH_VALUE_TOL and np.abs(one4[..., 1:] - f4[e][..., 1:])[agree].max() <= RC.FLY_COLOUR_TOL
     print("per-env cameras: %s; float4: max relative depth error %.3e, depth-buffer value %.3e, colour %.3e; bit-identical to the single-camera calls: %s"
           % (fig.text(), zmax, dmax, cmax, identical))
     fig.limits()
-    assert zmax <= G.DEPTH_REL_TOL and dmax <= G.DEPTH_VALUE_TOL and cmax <= G.COLOUR_TOL
+    assert zmax <= RC.FLY_DEPTH_REL_TOL and dmax <= RC.FLY_DEPTH_VALUE_TOL and cmax <= RC.FLY_COLOUR_TOL
 
 
 @pytest.mark.gpu
 def test_per_env_eye_in_hand_cameras(torch_mod, oracle_mod):
     """N = 6: rows that differ in fov (50 .. 70 degrees), given in each env's ee_link frame"""
-    case = I.per_env_cases(oracle_mod)["eye-in-hand"]
+    case = RC.per_env_cases(oracle_mod)["eye-in-hand"]
     (W, H), obj, cams = case["size"], case["obj"], case["cams"]
     g, st, cams_dev = _case_handle(torch_mod, case)
     flat = _render_guarded(torch_mod, g, W, H, "rgba8", camera=cams_dev, ee_frame=True)
     lit = _render_guarded(torch_mod, g, W, H, "rgba8", camera=cams_dev, ee_frame=True, shaded=True)
     depth = _render_guarded(torch_mod, g, W, H, "depth", camera=cams_dev, ee_frame=True)
-    fig = I.Figures()
+    fig = RC.Figures()
     for e in case["checked"]:
-        ref = T.reference_render(oracle_mod, st[e], cams[e], obj, W, H, True)
-        T.check_reference_scene("eye-in-hand", W, H, ref[2], obj)
-        _check_packed(oracle_mod, fig, flat[e], lit[e], depth[e], st[e], cams[e], True, obj, ref)
+        scene = R.fly_scene(oracle_mod, st[e], obj)
+        ref = R.plain_reference(scene, cams[e], W, H, "ee")
+        RC.fly_check_reference_scene("eye-in-hand", W, H, ref[2], obj)
+        _check_packed(scene, fig, flat[e], lit[e], depth[e], cams[e], "ee", ref)
     print("per-env eye-in-hand: %s" % fig.text())
     fig.limits()
 
@@ -159,7 +161,7 @@ def test_per_env_eye_in_hand_cameras(torch_mod, oracle_mod):
 @pytest.mark.gpu
 def test_degenerate_rows_give_the_background(torch_mod, oracle_mod):
     """N = 6: row 2 has eye == target, row 4 fov = NaN: those two images are background and finite, the other four are what they were"""
-    case = I.per_env_cases(oracle_mod)["degenerate"]
+    case = RC.per_env_cases(oracle_mod)["degenerate"]
     (W, H), obj, cams = case["size"], case["obj"], case["cams"]
     assert case["degenerate"] == (2, 4)
     g, st, cams_dev = _case_handle(torch_mod, case)
@@ -171,11 +173,12 @@ def test_degenerate_rows_give_the_background(torch_mod, oracle_mod):
     for e in case["degenerate"]:
         assert (dp[e] == 1.0).all() and (u8[e] == 255).all() and (lit[e] == 255).all()
         assert (f4[e][..., 0] == 1.0).all() and (f4[e][..., 1:] == 255.0).all()
-    fig = I.Figures()
+    fig = RC.Figures()
     for e in case["checked"]:
-        ref = T.reference_render(oracle_mod, st[e], cams[e], obj, W, H, False)
-        _check_packed(oracle_mod, fig, u8[e], lit[e], dp[e], st[e], cams[e], False, obj, ref)
-        assert np.abs(f4[e][..., 0] - dp[e]).max() <= G.DEPTH_VALUE_TOL
+        scene = R.fly_scene(oracle_mod, st[e], obj)
+        ref = R.plain_reference(scene, cams[e], W, H)
+        _check_packed(scene, fig, u8[e], lit[e], dp[e], cams[e], "env", ref)
+        assert np.abs(f4[e][..., 0] - dp[e]).max() <= RC.FLY_DEPTH_VALUE_TOL
     print("rows next to degenerate ones: %s" % fig.text())
     fig.limits()
 
@@ -184,7 +187,7 @@ def test_degenerate_rows_give_the_background(torch_mod, oracle_mod):
 def test_tracking_cameras_follow_the_object(torch_mod, oracle_mod):
     """after reset and 40 steps every env is seen from (1.2, 0.6, 0.9) looking at its own object, cameras built on the device"""
     n, obj, (W, H) = 6, 0, (61, 61)
-    g = G._gpu(n, object_id=obj, auto_reset=0)
+    g = RC.fly_handle(n, object_id=obj, auto_reset=0)
     g.reset(seed=11)
     rng = np.random.default_rng(11)
     for _ in range(40):
@@ -195,13 +198,14 @@ def test_tracking_cameras_follow_the_object(torch_mod, oracle_mod):
     dp = g.render(W, H, camera=cams_dev, fmt="depth").cpu().numpy()
     st = g.state().cpu().numpy(); cams = cams_dev.cpu().numpy()
     assert np.array_equal(cams[:, 3:6], st[:, _lib.F_OPOS:_lib.F_OPOS + 3])
-    fig = I.Figures(); centred = 0
+    fig = RC.Figures(); centred = 0
     for e in range(n):
-        ref = T.reference_render(oracle_mod, st[e], cams[e], obj, W, H, False)
-        same = I.check_seg(oracle_mod, u8[e][..., 3], st[e], cams[e], False, ref, exact=False)
-        fig.add_depth(I.depth_errors(dp[e], same, ref, cams[e]))
-        fig.add_colour(I.colour_excess(u8[e][..., :3], same, ref[0]), False)
-        if ref[2][H // 2, W // 2] == T.OBJECT:
+        scene = R.fly_scene(oracle_mod, st[e], obj)
+        ref = R.plain_reference(scene, cams[e], W, H)
+        same = RC.check_seg(scene, u8[e][..., 3], cams[e], "env", ref, exact=False)
+        fig.add_depth(RC.depth_errors(dp[e], same, ref, cams[e]))
+        fig.add_colour(RC.colour_excess(u8[e][..., :3], same, ref[0]), False)
+        if ref[2][H // 2, W // 2] == R.OBJECT:
             centred += 1
             assert u8[e][H // 2, W // 2, 3] == _lib.SEG_OBJECT
     print("tracking cameras: the object is on the centre pixel of %d of %d reference images; %s" % (centred, n, fig.text()))
@@ -213,7 +217,7 @@ def test_errors(torch_mod):
     from peg_in_hole_gym_amd.vec_env import PihVecEnv
     torch = torch_mod
     L = _lib.load()
-    fly = G._gpu(3)
+    fly = RC.fly_handle(3)
     out = torch.empty(3, 48, 64, 4, device="cuda")
     cams = torch.tensor([_lib.FLY_CAM_DEFAULT] * 3, device="cuda")
     both = _lib.RENDER_OUT_RGBA8 | _lib.RENDER_OUT_DEPTH

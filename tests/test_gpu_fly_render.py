@@ -1,35 +1,15 @@
 """Free camera of the 'random-fly' task on the GPU: pih_render_cam / PihVecEnv.render / RandomFly.render / BaseEnv.render against the
-numpy fp64 ray caster of tests/test_fly_render.py (same scenes, cameras, sizes and comparison rules).
-
-Tolerance.  The fp32 HOST build of the kernel's per-pixel code (tests/test_fly_render.py::test_host_build_matches_the_reference[f32],
-g++ -O2 -fno-fast-math, correctly rounded division and square root) differs from the fp64 reference over all scenes by at most the
-F32_HOST_* numbers below.  The library is built with -ffast-math and -fno-hip-fp32-correctly-rounded-divide-sqrt: its reciprocal square
-roots and divisions are 1-2 ulp each over a chain of about ten operations, so the GPU gets 8 x the host numbers.
-  * The relative error of the eye-space depth is recovered from the fp32 depth-buffer value 1 - near / z: one ulp of it (6e-8) is
-    6e-8 z / near of z, i.e. 6e-4 at the far plane z = 100 = 1e4 near -- the table next to the horizon sets the host number.
-  * Flat colours are products 255 x table entry: rounding of one fp32 multiplication.
-  * Shaded colours take the bar of tests/test_render.py (p99 < 0.05 and median < 1e-3 grey levels): normals at grazing hits differ in fp32
-    (host build: 8.2e-2 at the worst pixel)."""
+numpy fp64 ray caster of tests/render_ref.py, with the scenes, cameras, sizes, comparison rules and tolerances (RC.FLY_*_TOL, derived
+there from the fp32 host build) of tests/render_cases.py, which tests/test_fly_render.py shares."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
 from peg_in_hole_gym_amd import _lib
-
-F32_HOST_MAX_DEPTH_REL = 7.943e-04       # max |z - z_ref| / z_ref, fp32 host build vs fp64 reference
-F32_HOST_MAX_DEPTH_VALUE = 2.026e-06     # max |depth-buffer value - reference's|
-F32_HOST_MAX_FLAT_COLOUR = 5.493e-06     # max |rgb - rgb_ref| of the flat images, 0..255 scale
-DEPTH_REL_TOL = 8 * F32_HOST_MAX_DEPTH_REL
-DEPTH_VALUE_TOL = 8 * F32_HOST_MAX_DEPTH_VALUE
-COLOUR_TOL = 8 * F32_HOST_MAX_FLAT_COLOUR
-
-DT = 1.0 / 120.0
-# seeds of the six arm poses per (object, camera).  An eye-in-hand scene puts the object 0.35 m along the tool axis, which for some arm poses
-# is under the table: such a scene shows no object and fails the conditions of tests/test_fly_render.py::check_reference_scene (the
-# Amicelli seeds 213 and 233 have one), so that pair takes the next seed whose six scenes meet them.
-SCENE_SEED = {(obj, name): 200 + 10 * obj + ci for obj in (0, 1) for ci, name in enumerate(("overview", "close-up", "horizon", "eye-in-hand"))}
-SCENE_SEED[(1, "eye-in-hand")] = 253
+from tests import render_cases as RC
+from tests import render_ref as R
+from tests.render_cases import FLY_COLOUR_TOL as COLOUR_TOL, FLY_DEPTH_REL_TOL as DEPTH_REL_TOL, FLY_DEPTH_VALUE_TOL as DEPTH_VALUE_TOL
 
 
 @pytest.fixture(scope="module")
@@ -39,42 +19,34 @@ def torch_mod():
     return torch
 
 
-def _gpu(n, **kw):
-    from peg_in_hole_gym_amd.vec_env import PihVecEnv
-    kw.setdefault("max_episode_steps", 480); kw.setdefault("contact_margin", 0.02); kw.setdefault("dt", DT)
-    return PihVecEnv(n, task_id=1, **kw)
-
-
-def _check(T, O, img, flat, rec, cam, ee, obj, shaded, name=None):
+def _check(O, img, flat, rec, cam, frame, obj, shaded, name=None):
     """one env's image against the reference under the class share, depth and colour rules; prints the figures before it asserts"""
     H, W = img.shape[:2]
-    rflat, rlit, rcls, rz = T.reference_render(O, rec, cam, obj, W, H, ee)
+    rflat, rlit, rcls, rz = R.plain_reference(R.fly_scene(O, rec, obj), cam, W, H, frame)
     if name is not None:
-        T.check_reference_scene(name, W, H, rcls, obj)
-    zerr, derr, cerr = T.compare(img.astype(np.float64), flat.astype(np.float64), rlit if shaded else rflat, rcls, rz, cam, obj, exact_class=False)
-    return zerr, derr, cerr
+        RC.fly_check_reference_scene(name, W, H, rcls, obj)
+    return RC.compare(img.astype(np.float64), R.classify(flat.astype(np.float64), obj), rlit if shaded else rflat, rcls, rz, cam, R.BG, exact_class=False)
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("obj", [0, 1])
 def test_parity_all_cameras_sizes_flat_and_shaded(torch_mod, oracle_mod, obj):
     """N = 6: the four cameras, the three sizes, flat and shaded, every env against the reference fed with the handle's own state()"""
-    from tests import test_fly_render as T
     n = 6
-    g = _gpu(n, object_id=obj)
+    g = RC.fly_handle(n, object_id=obj)
     zmax = dmax = cmax = 0.0; shaded_err = []
-    for name in T.CAMERA_NAMES:
-        g.set_state(torch_mod.tensor(T.make_states(oracle_mod, obj, n, seed=SCENE_SEED[(obj, name)], eye_in_hand=name == "eye-in-hand")))
+    for name in RC.FLY_CAMERA_NAMES:
+        g.set_state(torch_mod.tensor(RC.make_fly_states(oracle_mod, obj, n, seed=RC.SCENE_SEED[(obj, name)], eye_in_hand=name == "eye-in-hand")))
         st = g.state().cpu().numpy()
-        for (W, H) in T.SIZES:
-            cam, ee = T.cameras(W, H)[name]
-            flat = g.render(W, H, camera=cam, ee_frame=ee).cpu().numpy()
-            lit = g.render(W, H, camera=cam, ee_frame=ee, shaded=True).cpu().numpy()
+        for (W, H) in RC.SIZES:
+            cam, frame = RC.fly_cameras(W, H)[name]
+            flat = g.render(W, H, camera=cam, ee_frame=frame == "ee").cpu().numpy()
+            lit = g.render(W, H, camera=cam, ee_frame=frame == "ee", shaded=True).cpu().numpy()
             assert flat.shape == (n, H, W, 4) and np.array_equal(flat[..., 0], lit[..., 0])          # shading does not touch the depth buffer
             for e in range(n):
-                z, d, c = _check(T, oracle_mod, flat[e], flat[e], st[e], cam, ee, obj, False, name)
+                z, d, c = _check(oracle_mod, flat[e], flat[e], st[e], cam, frame, obj, False, name)
                 zmax = max(zmax, z); dmax = max(dmax, d); cmax = max(cmax, c.max())
-                z, d, c = _check(T, oracle_mod, lit[e], flat[e], st[e], cam, ee, obj, True)
+                z, d, c = _check(oracle_mod, lit[e], flat[e], st[e], cam, frame, obj, True)
                 shaded_err.append(c)
     shaded_err = np.concatenate(shaded_err)
     print("object %d: max relative depth error %.3e (bound %.3e), depth-buffer value %.3e (%.3e), flat colour %.3e (%.3e), shaded colour p99 %.3e median %.3e max %.3e"
@@ -86,17 +58,16 @@ def test_parity_all_cameras_sizes_flat_and_shaded(torch_mod, oracle_mod, obj):
 @pytest.mark.gpu
 def test_soa_indexing_and_sub_ranges(torch_mod, oracle_mod):
     """N = 70 (not a multiple of the wave): word w of env e is state[w * n + e]; a sub-range renders the same pixels"""
-    from tests import test_fly_render as T
     n, obj, (W, H) = 70, 0, (97, 61)
-    g = _gpu(n, object_id=obj)
-    g.set_state(torch_mod.tensor(T.make_states(oracle_mod, obj, n, seed=300)))
+    g = RC.fly_handle(n, object_id=obj)
+    g.set_state(torch_mod.tensor(RC.make_fly_states(oracle_mod, obj, n, seed=300)))
     st = g.state().cpu().numpy()
-    cam, ee = T.cameras(W, H)["close-up"]
+    cam, frame = RC.fly_cameras(W, H)["close-up"]
     full = g.render(W, H, camera=cam).cpu().numpy()
     part = g.render(W, H, env_begin=3, env_count=5, camera=cam).cpu().numpy()
     assert part.shape == (5, H, W, 4) and np.array_equal(part, full[3:8])
     for e in (0, 63, 64, 69):
-        z, d, c = _check(T, oracle_mod, full[e], full[e], st[e], cam, ee, obj, False, "close-up")
+        z, d, c = _check(oracle_mod, full[e], full[e], st[e], cam, frame, obj, False, "close-up")
         print("env %d: max relative depth error %.3e, depth-buffer value %.3e, colour %.3e" % (e, z, d, c.max()))
         assert z <= DEPTH_REL_TOL and d <= DEPTH_VALUE_TOL and c.max() <= COLOUR_TOL
 
@@ -104,9 +75,8 @@ def test_soa_indexing_and_sub_ranges(torch_mod, oracle_mod):
 @pytest.mark.gpu
 def test_live_state_and_default_camera(torch_mod, oracle_mod):
     """after reset and 40 steps the image is the reference's for state() of the same handle; camera=None is PIH_FLY_CAM_DEFAULT"""
-    from tests import test_fly_render as T
     n, obj, (W, H) = 6, 0, (97, 61)
-    g = _gpu(n, object_id=obj, auto_reset=0)
+    g = RC.fly_handle(n, object_id=obj, auto_reset=0)
     g.reset(seed=11)
     rng = np.random.default_rng(11)
     for _ in range(40):
@@ -114,9 +84,9 @@ def test_live_state_and_default_camera(torch_mod, oracle_mod):
     st = g.state().cpu().numpy()
     img = g.render(W, H).cpu().numpy()
     assert np.array_equal(img, g.render(W, H, camera=_lib.FLY_CAM_DEFAULT).cpu().numpy())
-    assert np.abs(st[:, _lib.F_Q:_lib.F_Q + 6] - T.REST).max() > 1e-3                     # the arms have moved
+    assert np.abs(st[:, _lib.F_Q:_lib.F_Q + 6] - RC.REST).max() > 1e-3                     # the arms have moved
     for e in range(n):
-        z, d, c = _check(T, oracle_mod, img[e], img[e], st[e], _lib.FLY_CAM_DEFAULT, False, obj, False)
+        z, d, c = _check(oracle_mod, img[e], img[e], st[e], _lib.FLY_CAM_DEFAULT, "env", obj, False)
         print("env %d: max relative depth error %.3e, depth-buffer value %.3e, colour %.3e" % (e, z, d, c.max()))
         assert z <= DEPTH_REL_TOL and d <= DEPTH_VALUE_TOL and c.max() <= COLOUR_TOL
 
@@ -135,7 +105,7 @@ def test_errors_and_untouched_paths(torch_mod):
     out = torch.empty(3, 48, 64, 4, device="cuda")
     assert L.pih_render_cam(peg.h, out.data_ptr(), None, 64, 48, 0, 3, 0, None) == -2
     assert b"random-fly" in L.pih_last_error(peg.h)
-    fly = _gpu(3)
+    fly = RC.fly_handle(3)
     assert L.pih_render_ex(fly.h, out.data_ptr(), 64, 48, 0, 3, 0, None) == -2
     assert b"peg-in-hole" in L.pih_last_error(fly.h)
     assert L.pih_render(fly.h, out.data_ptr(), 64, 48, 0, 3, None) == -2
@@ -167,7 +137,6 @@ def test_errors_and_untouched_paths(torch_mod):
 def test_base_env_renders_random_fly(torch_mod, oracle_mod):
     """BaseEnv.render fills `images` for task='random-fly'; every agent's image is the reference's for its own state, so the env offset
     does not enter an env-local camera"""
-    from tests import test_fly_render as T
     from peg_in_hole_gym_amd.envs import BaseEnv
     env = BaseEnv(task="random-fly", task_num=2, offset=[2., 3., 0.], args=["Banana", 1 / 120.])
     env.reset()
@@ -180,7 +149,7 @@ def test_base_env_renders_random_fly(torch_mod, oracle_mod):
     for e in range(2):
         img = env.images[e]
         assert img.shape == (300, 300, 4) and img.dtype == np.float64
-        z, d, c = _check(T, oracle_mod, img, flat[e].astype(np.float64), st[e], _lib.FLY_CAM_DEFAULT, False, 0, True)
+        z, d, c = _check(oracle_mod, img, flat[e].astype(np.float64), st[e], _lib.FLY_CAM_DEFAULT, "env", 0, True)
         print("agent %d: max relative depth error %.3e, depth-buffer value %.3e, shaded colour p99 %.3e median %.3e" % (e, z, d, np.percentile(c, 99), np.median(c)))
         assert z <= DEPTH_REL_TOL and d <= DEPTH_VALUE_TOL
         shaded_err.append(c)

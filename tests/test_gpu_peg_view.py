@@ -1,31 +1,16 @@
 """Free camera of the peg-in-hole task on the GPU: pih_render_view / PihVecEnv.render_view against the numpy fp64 ray caster of
-tests/test_peg_view.py (same states, cameras, sizes and comparison rules).
-
-Tolerance, by the rule of tests/test_gpu_fly_render.py.  The fp32 HOST build of the kernel's per-pixel code
-(tests/test_peg_view.py::test_host_build_matches_the_reference[f32], g++ -O2 -fno-fast-math, correctly rounded division and square root)
-differs from the fp64 reference over all scenes by at most the F32_HOST_* numbers below.  The library is built with -ffast-math and
--fno-hip-fp32-correctly-rounded-divide-sqrt: its reciprocal square roots and divisions are 1-2 ulp each over a chain of about ten
-operations, so the GPU gets 8 x the host numbers.
-  * Depth: both host maxima come from rays that graze a capsule or the hole tube -- the root of a discriminant close to 0 carries the
-    square root of its rounding error: the overview (5.4e-4, 2.8e-6) and the hole close-up (4.7e-4, 2.6e-6) set them, the horizon has
-    2.0e-4, the wrist preset 5.2e-5, the eye-in-hand camera 1.5e-5.
-  * Flat colours are constants of the scene, no arithmetic: the host number is 0 and so is the bound.
-  * Shaded colours take the bar of tests/test_render.py (p99 < 0.05 and median < 1e-3 grey levels): normals at grazing hits and at the
-    edges of the finger boxes differ in fp32 (host build: 3.4 at the worst pixel, p99 1.0e-3, median 1.1e-5)."""
+tests/render_ref.py, with the states, cameras, sizes, comparison rules and tolerances (RC.PEG_*_TOL, derived there from the fp32 host
+build) of tests/render_cases.py, which tests/test_peg_view.py shares."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
 from peg_in_hole_gym_amd import _lib
-
-F32_HOST_MAX_DEPTH_REL = 5.363e-04       # max |z - z_ref| / z_ref, fp32 host build vs fp64 reference
-F32_HOST_MAX_DEPTH_VALUE = 2.752e-06     # max |depth-buffer value - reference's|
-F32_HOST_MAX_FLAT_COLOUR = 0.0           # max |rgb - rgb_ref| of the flat images, 0..255 scale
-DEPTH_REL_TOL = 8 * F32_HOST_MAX_DEPTH_REL
-DEPTH_VALUE_TOL = 8 * F32_HOST_MAX_DEPTH_VALUE
-COLOUR_TOL = 8 * F32_HOST_MAX_FLAT_COLOUR
-SHADED_P99, SHADED_MEDIAN = 0.05, 1e-3   # grey levels
+from tests import render_cases as RC
+from tests import render_ref as R
+from tests.render_cases import (PEG_COLOUR_TOL as COLOUR_TOL, PEG_DEPTH_REL_TOL as DEPTH_REL_TOL, PEG_DEPTH_VALUE_TOL as DEPTH_VALUE_TOL, SHADED_MEDIAN,
+                                SHADED_P99)
 
 
 @pytest.fixture(scope="module")
@@ -37,8 +22,7 @@ def torch_mod():
 
 @pytest.fixture(scope="module")
 def states(oracle_mod):
-    from tests import test_peg_view as T
-    return T.make_states(oracle_mod)
+    return RC.make_view_states(oracle_mod)
 
 
 def _peg(n, **kw):
@@ -47,47 +31,46 @@ def _peg(n, **kw):
 
 
 def _tile(states, n):
-    """n records: the six states of tests/test_peg_view.py, repeated"""
+    """n records: the six states of RC.make_view_states, repeated"""
     return np.ascontiguousarray(states[np.arange(n) % len(states)])
 
 
-def _check(T, O, img, seg, rec, cam, frame, shaded, name=None, cache=None):
+def _check(O, img, seg, rec, cam, frame, shaded, name=None, cache=None):
     """one env's float4 image and seg bytes against the reference under the class share, depth and colour rules"""
     H, W = img.shape[:2]
     key = (rec.tobytes(), tuple(cam), frame, W, H)
     if cache is None or key not in cache:
-        ref = T.reference_render(O, rec, cam, W, H, frame)
+        ref = R.plain_reference(R.peg_scene(O, rec), cam, W, H, frame)
         if cache is not None:
             cache[key] = ref
     else:
         ref = cache[key]
     rflat, rlit, rseg, rz = ref
     if name is not None:
-        T.check_reference_scene(name, W, H, rseg, cam)
-    return T.compare(img.astype(np.float64), seg, rlit if shaded else rflat, rseg, rz, cam, exact_class=False)
+        RC.peg_check_reference_scene(name, W, H, rseg, cam)
+    return RC.compare(img.astype(np.float64), seg, rlit if shaded else rflat, rseg, rz, cam, _lib.SEG_NONE, exact_class=False)
 
 
 @pytest.mark.gpu
 def test_parity_all_cameras_sizes_flat_and_shaded(torch_mod, oracle_mod, states):
     """N = 6: the five cameras, the three sizes, flat and shaded, every env against the reference fed with the handle's own state().  The
     class of a pixel is its seg byte (rgba8 of the same call arguments)."""
-    from tests import test_peg_view as T
     n = 6
     g = _peg(n)
     g.set_state(torch_mod.tensor(states))
     st = g.state().cpu().numpy()
     zmax = dmax = cmax = 0.0; shaded_err = []; cache = {}
-    for name in T.CAMERA_NAMES:
-        for (W, H) in T.SIZES:
-            cam, frame = T.cameras(W, H)[name]
+    for name in RC.PEG_CAMERA_NAMES:
+        for (W, H) in RC.SIZES:
+            cam, frame = RC.peg_cameras(W, H)[name]
             flat = g.render_view(W, H, camera=cam, frame=frame).cpu().numpy()
             lit = g.render_view(W, H, camera=cam, frame=frame, shaded=True).cpu().numpy()
             seg = g.render_view(W, H, camera=cam, frame=frame, fmt="rgba8").cpu().numpy()[..., 3]
             assert flat.shape == (n, H, W, 4) and np.array_equal(flat[..., 0], lit[..., 0])          # shading does not touch the depth channel
             for e in range(n):
-                z, d, c = _check(T, oracle_mod, flat[e], seg[e], st[e], cam, frame, False, name, cache)
+                z, d, c = _check(oracle_mod, flat[e], seg[e], st[e], cam, frame, False, name, cache)
                 zmax = max(zmax, z); dmax = max(dmax, d); cmax = max(cmax, c.max())
-                z, d, c = _check(T, oracle_mod, lit[e], seg[e], st[e], cam, frame, True, None, cache)
+                z, d, c = _check(oracle_mod, lit[e], seg[e], st[e], cam, frame, True, None, cache)
                 shaded_err.append(c)
     shaded_err = np.concatenate(shaded_err)
     print("max relative depth error %.3e (bound %.3e), depth-buffer value %.3e (%.3e), flat colour %.3e (%.3e), shaded colour p99 %.3e median %.3e max %.3e"
@@ -140,18 +123,17 @@ def test_wrist_preset_against_pih_render(torch_mod, states):
 @pytest.mark.gpu
 def test_sub_ranges(torch_mod, oracle_mod, states):
     """N = 70 (not a multiple of the wave): a sub-range renders the same pixels; envs 0, 63, 64 and 69 against the reference"""
-    from tests import test_peg_view as T
     n, (W, H) = 70, (97, 61)
     g = _peg(n)
     g.set_state(torch_mod.tensor(_tile(states, n)))
     st = g.state().cpu().numpy()
-    cam, frame = T.cameras(W, H)["overview"]
+    cam, frame = RC.peg_cameras(W, H)["overview"]
     full = g.render_view(W, H, camera=cam).cpu().numpy()
     part = g.render_view(W, H, env_begin=3, env_count=5, camera=cam).cpu().numpy()
     assert part.shape == (5, H, W, 4) and np.array_equal(part, full[3:8])
     seg = g.render_view(W, H, camera=cam, fmt="rgba8").cpu().numpy()[..., 3]
     for e in (0, 63, 64, 69):
-        z, d, c = _check(T, oracle_mod, full[e], seg[e], st[e], cam, frame, False, "overview")
+        z, d, c = _check(oracle_mod, full[e], seg[e], st[e], cam, frame, False, "overview")
         print("env %d: max relative depth error %.3e, depth-buffer value %.3e, colour %.3e" % (e, z, d, c.max()))
         assert z <= DEPTH_REL_TOL and d <= DEPTH_VALUE_TOL and c.max() <= COLOUR_TOL
 
@@ -163,14 +145,13 @@ def _pack(rgb):
 @pytest.mark.gpu
 def test_packed_formats(torch_mod, states):
     """rgba8 == the pack of the float4 image, bytewise; depth == channel 0, bitwise; flat and shaded, every camera; out= is written in place"""
-    from tests import test_peg_view as T
     torch = torch_mod
     n, (W, H) = 6, (97, 61)
     g = _peg(n)
     g.set_state(torch.tensor(states))
     segs = set()
-    for name in T.CAMERA_NAMES:
-        cam, frame = T.cameras(W, H)[name]
+    for name in RC.PEG_CAMERA_NAMES:
+        cam, frame = RC.peg_cameras(W, H)[name]
         for shaded in (False, True):
             f4 = g.render_view(W, H, camera=cam, frame=frame, shaded=shaded).cpu().numpy()
             r8 = g.render_view(W, H, camera=cam, frame=frame, shaded=shaded, fmt="rgba8")
@@ -196,13 +177,12 @@ def test_packed_formats(torch_mod, states):
 def test_per_env_device_cameras(torch_mod, states):
     """Row e of a [count, 13] camera tensor == the single host camera call for that env, bitwise, in all three formats; a degenerate row and
     a NaN row give the background and leave their neighbours alone"""
-    from tests import test_peg_view as T
     torch = torch_mod
     n, (W, H) = 6, (97, 61)
     g = _peg(n)
     g.set_state(torch.tensor(states))
     names = ("overview", "hole close-up", "horizon", "overview", "hole close-up", "horizon")
-    rows = [T.cameras(W, H)[nm][0] for nm in names]
+    rows = [RC.peg_cameras(W, H)[nm][0] for nm in names]
     rows[3] = list(rows[3]); rows[3][0] += 0.2                                     # (not twice the same camera)
     cams = torch.tensor(rows, dtype=torch.float32, device="cuda")
     for frame in ("env", "ee_pos"):

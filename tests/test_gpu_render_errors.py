@@ -2,7 +2,7 @@
 (on a handle of either task) answer every call of the table in tests/render_error_cases.py with the return code and the exact
 pih_last_error text that tools/record_render_errors.py recorded in tests/golden/render_errors.json -- NULL out, zero sizes, env ranges, a
 misaligned out pointer, every flag bit alone, both formats, both camera frames, the device flags with NULL arrays, the handle of the wrong
-task, the degenerate cameras of tests/test_fly_image.py, NaN and +inf in each camera word, the bad lights of tests/test_render_lit.py, double
+task, the degenerate cameras, NaN and +inf in each camera word, the bad lights of tests/render_cases.py, double
 faults (which of two simultaneous faults is reported), and good calls that return 0.  The file was recorded from the build before the
 argument checks of pih_hip.hip were merged into shared helpers; a characterisation test: a difference is a change of behaviour.
 The `env_count > 65535` branch is not in the table: a 3-env handle cannot reach it (the env range is tested first)."""

@@ -1,14 +1,17 @@
-"""Lit camera images on the GPU: pih_render_lit / PihVecEnv.render(light=...) / render_view(light=...) against the numpy fp64 reference of
-tests/test_render_lit.py -- same scenes, cameras, sizes, lights and rules: the class share of the task's module, the shadow state equal on
-every decided pixel, the undecided cap (on the reference), and that module's colour bar: the project's bar for shaded colours (p99 < 0.05,
-median < 1e-3 grey levels) times 1 + specular shininess / diffuse of the light.  The fp32 host build meets that bar with p99 <= 2.8e-3 and
-median <= 4.8e-6 (light `low` / `shiny`); it is a bar on percentiles, and the GPU takes it as it stands."""
+"""Lit camera images on the GPU: pih_render_lit / PihVecEnv.render(light=...) / render_view(light=...) against lit_reference of
+tests/render_ref.py -- the scenes, cameras, sizes, lights and rules of tests/render_cases.py, which tests/test_render_lit.py shares: the
+class share of the task, the shadow state equal on every decided pixel, the undecided cap (on the reference), and the colour bar: the
+project's bar for shaded colours (p99 < 0.05, median < 1e-3 grey levels) times 1 + specular shininess / diffuse of the light.  The fp32
+host build meets that bar with p99 <= 2.8e-3 and median <= 4.8e-6 (light `low` / `shiny`); it is a bar on percentiles, and the GPU takes
+it as it stands."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
 from peg_in_hole_gym_amd import _lib
+from tests import render_cases as RC
+from tests.render_ref import L_SHADOW, L_SPEC
 
 
 @pytest.fixture(scope="module")
@@ -23,11 +26,6 @@ def _peg(n, **kw):
     return PihVecEnv(n, **kw)
 
 
-def _fly(n, **kw):
-    from tests import test_gpu_fly_render as G
-    return G._gpu(n, **kw)
-
-
 def _render(g, case, light, fmt="float4", **kw):
     """the handle's lit image of all its envs for a case's camera and size"""
     W, H = case["size"]
@@ -36,8 +34,8 @@ def _render(g, case, light, fmt="float4", **kw):
     return g.render(W, H, camera=case["cam"], ee_frame=case["frame"] == "ee", fmt=fmt, light=light, **kw)
 
 
-def _parity(T, g, cases):
-    """every case x the four lights under the rules of T.check_image; the images of all envs are rendered once per (camera, size, light)"""
+def _parity(g, cases):
+    """every case x the four lights under the rules of RC.check_image; the images of all envs are rendered once per (camera, size, light)"""
     images = {}
 
     def gpu(case, lw):
@@ -47,57 +45,50 @@ def _parity(T, g, cases):
         img, seg = images[key]
         return img[case["env"]], seg[case["env"]]
 
-    for ln in T.LIGHT_NAMES:
-        light = T.LIGHTS[ln]; errs = []; worst = 0.0; und = 0.0
+    for ln in RC.LIGHT_NAMES:
+        light = RC.LIGHTS[ln]; errs = []; worst = 0.0; und = 0.0
         for key, case in cases.items():
-            ref = T.case_reference(case, light)
+            ref = RC.case_reference(case, light)
             und = max(und, (~ref["decided"]).mean())
-            assert (~ref["decided"]).mean() <= T.UNDECIDED_CAP, (key, ln)
+            assert (~ref["decided"]).mean() <= RC.UNDECIDED_CAP, (key, ln)
             try:
-                err, share = T.check_image(ref, case["task"], lambda lw: gpu(case, lw), light, exact=False)
+                err, share = RC.check_image(ref, case["task"], lambda lw: gpu(case, lw), light, exact=False)
             except AssertionError as ex:
                 raise AssertionError("%s, light %s: %s" % (key, ln, ex)) from None
             errs.append(err); worst = max(worst, share)
-        errs = np.concatenate(errs); f = T.colour_factor(light)
+        errs = np.concatenate(errs); f = RC.colour_factor(light)
         print("light %-8s: colour error max %.3e, p99 %.3e (bound %.3e), median %.3e (bound %.3e); worst class share %.4f; largest undecided share %.4f"
-              % (ln, errs.max(), np.percentile(errs, 99), T.SHADED_P99 * f, np.median(errs), T.SHADED_MEDIAN * f, worst, und))
-        assert np.percentile(errs, 99) < T.SHADED_P99 * f and np.median(errs) < T.SHADED_MEDIAN * f
+              % (ln, errs.max(), np.percentile(errs, 99), RC.SHADED_P99 * f, np.median(errs), RC.SHADED_MEDIAN * f, worst, und))
+        assert np.percentile(errs, 99) < RC.SHADED_P99 * f and np.median(errs) < RC.SHADED_MEDIAN * f
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", ["wrist", "overview", "hole close-up", "eye-in-hand", "horizon"])
 def test_parity_peg_in_hole(torch_mod, oracle_mod, name):
-    """the six state slots (eight envs: T.PEG_STATE_FOR) x the three sizes x the four lights under one camera, float4 plus the seg of rgba8,
+    """the six state slots (eight envs: RC.PEG_STATE_FOR) x the three sizes x the four lights under one camera, float4 plus the seg of rgba8,
     every env against the reference fed with the handle's own state()"""
-    from tests import test_render_lit as T
     g = _peg(8)
-    g.set_state(torch_mod.tensor(T.make_peg_states(oracle_mod)))
-    _parity(T, g, T.peg_cases(oracle_mod, g.state().cpu().numpy(), (name,)))
+    g.set_state(torch_mod.tensor(RC.make_peg_states(oracle_mod)))
+    _parity(g, RC.peg_cases(oracle_mod, g.state().cpu().numpy(), (name,)))
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", ["overview", "close-up", "horizon", "eye-in-hand"])
 @pytest.mark.parametrize("obj", [0, 1])
 def test_parity_random_fly(torch_mod, oracle_mod, obj, name):
-    """six envs (the scenes of tests/test_gpu_fly_render.py) x the three sizes x the four lights under one camera"""
-    from tests import test_fly_render as FR
-    from tests import test_gpu_fly_render as G
-    from tests import test_render_lit as T
-    g = _fly(6, object_id=obj)
-    g.set_state(torch_mod.tensor(FR.make_states(oracle_mod, obj, 6, seed=G.SCENE_SEED[(obj, name)], eye_in_hand=name == "eye-in-hand")))
-    _parity(T, g, T.fly_cases(oracle_mod, obj, name, g.state().cpu().numpy()))
+    """six envs (the scenes of RC.SCENE_SEED) x the three sizes x the four lights under one camera"""
+    g = RC.fly_handle(6, object_id=obj)
+    g.set_state(torch_mod.tensor(RC.make_fly_states(oracle_mod, obj, 6, seed=RC.SCENE_SEED[(obj, name)], eye_in_hand=name == "eye-in-hand")))
+    _parity(g, RC.fly_cases(oracle_mod, obj, name, g.state().cpu().numpy()))
 
 
 def _handles(torch_mod, O):
     """one handle per task with the scenes of the parity tests, and a case (camera, size) for each"""
-    from tests import test_fly_render as FR
-    from tests import test_gpu_fly_render as G
-    from tests import test_render_lit as T
-    peg = _peg(8); peg.set_state(torch_mod.tensor(T.make_peg_states(O)))
-    fly = _fly(6, object_id=0); fly.set_state(torch_mod.tensor(FR.make_states(O, 0, 6, seed=G.SCENE_SEED[(0, "overview")])))
-    pc = T.peg_cases(O, peg.state().cpu().numpy(), ("overview", "wrist", "eye-in-hand"))
-    fc = T.fly_cases(O, 0, "overview", fly.state().cpu().numpy()[:1])
-    fe = T.fly_cases(O, 0, "eye-in-hand", fly.state().cpu().numpy()[:1])
+    peg = _peg(8); peg.set_state(torch_mod.tensor(RC.make_peg_states(O)))
+    fly = RC.fly_handle(6, object_id=0); fly.set_state(torch_mod.tensor(RC.make_fly_states(O, 0, 6, seed=RC.SCENE_SEED[(0, "overview")])))
+    pc = RC.peg_cases(O, peg.state().cpu().numpy(), ("overview", "wrist", "eye-in-hand"))
+    fc = RC.fly_cases(O, 0, "overview", fly.state().cpu().numpy()[:1])
+    fe = RC.fly_cases(O, 0, "eye-in-hand", fly.state().cpu().numpy()[:1])
     return [(peg, pc[("peg", n, (97, 61), 0)]) for n in ("overview", "wrist", "eye-in-hand")] + [(fly, fc[("fly0", "overview", (97, 61), 0)]), (fly, fe[("fly0", "eye-in-hand", (97, 61), 0)])]
 
 
@@ -106,11 +97,10 @@ def test_switch_off_identity(torch_mod, oracle_mod):
     """default direction, specular 0, shadow factor 1: the depth channel is bit-equal to the shaded image of render_view / render, colours
     within 1e-3 grey levels (ten times 255 x a few fp32 roundings: the kernel normalises the direction the unlit kernels hold as constants);
     the seg bytes and the depth-only image are the unlit call's bit for bit, under any light"""
-    from tests import test_render_lit as T
-    off = list(_lib.LIGHT_DEFAULT); off[T.L_SPEC] = 0.0; off[T.L_SHADOW] = 1.0
+    off = list(_lib.LIGHT_DEFAULT); off[L_SPEC] = 0.0; off[L_SHADOW] = 1.0
     hs = _handles(torch_mod, oracle_mod)
     for g, case in hs:
-        for (W, H) in T.SIZES:
+        for (W, H) in RC.SIZES:
             c = dict(case, size=(W, H))
             lit = _render(g, c, off).cpu().numpy()
             kw = dict(frame=case["frame"]) if case["task"] == "peg" else dict(ee_frame=case["frame"] == "ee")
@@ -120,7 +110,7 @@ def test_switch_off_identity(torch_mod, oracle_mod):
             d = np.abs(lit[..., 1:].astype(np.float64) - shaded[..., 1:])
             print("%s %s %dx%d: max colour difference to the shaded image %.3e" % (case["task"], case["name"], W, H, d.max()))
             assert d.max() <= 1e-3
-            for light in ("default", T.LIGHTS["low"]):
+            for light in ("default", RC.LIGHTS["low"]):
                 assert np.array_equal(_render(g, c, light, fmt="rgba8").cpu().numpy()[..., 3], f(W, H, camera=case["cam"], fmt="rgba8", **kw).cpu().numpy()[..., 3])
                 assert np.array_equal(_render(g, c, light, fmt="depth").cpu().numpy(), shaded[..., 0])
     # no camera: the task's preset
@@ -133,11 +123,10 @@ def test_switch_off_identity(torch_mod, oracle_mod):
 def test_per_env_device_lights(torch_mod, oracle_mod):
     """six different rows == six single-light calls bit for bit, in float4 and rgba8; a [3, 11] tensor with env_begin = 2 == the matching
     slices; a degenerate row and one with a NaN give their envs the background and the call returns 0; random_lights"""
-    from tests import test_render_lit as T
     rng = np.random.default_rng(7)
     for g, case in _handles(torch_mod, oracle_mod)[::3]:
         n = 6
-        rows = np.array([T.LIGHTS["default"], T.LIGHTS["low"], T.LIGHTS["below"], T.LIGHTS["shiny"], T.LIGHTS["low"], T.LIGHTS["shiny"]], dtype=np.float32)
+        rows = np.array([RC.LIGHTS["default"], RC.LIGHTS["low"], RC.LIGHTS["below"], RC.LIGHTS["shiny"], RC.LIGHTS["low"], RC.LIGHTS["shiny"]], dtype=np.float32)
         rows[4, :3] = [-0.3, 0.8, 0.4]; rows[5, 10] = 0.3
         for fmt in ("float4", "rgba8"):
             per_env = _render(g, case, torch_mod.tensor(rows, device=g.device), fmt=fmt, env_count=n).cpu().numpy()
@@ -168,7 +157,6 @@ def test_per_env_device_lights(torch_mod, oracle_mod):
 def test_errors(torch_mod, oracle_mod):
     """each degenerate host light returns -2 and the message names the field; both formats, an unknown bit, a misaligned pointer and a NULL
     device light return -2; the old entry points still refuse bit 64"""
-    from tests import test_render_lit as T
     for g, case in _handles(torch_mod, oracle_mod)[::3]:
         L, h = g.L, g.h
         W, H = 40, 30
@@ -176,7 +164,7 @@ def test_errors(torch_mod, oracle_mod):
         light = (C.c_float * 11)(*_lib.LIGHT_DEFAULT)
         call = lambda ptr, lgt, flags, count=g.n: L.pih_render_lit(h, ptr, None, lgt, W, H, 0, count, flags, None)
         assert call(out.data_ptr(), light, 0) == 0 and call(out.data_ptr(), None, _lib.RENDER_SHADED) == 0
-        for field, _, words in T.BAD_LIGHTS:
+        for field, _, words in RC.BAD_LIGHTS:
             assert call(out.data_ptr(), (C.c_float * 11)(*words), 0) == -2
             msg = L.pih_last_error(h).decode()
             assert "degenerate light: " + field in msg, (field, msg)

@@ -8,14 +8,10 @@ import sys
 import numpy as np
 import pytest
 
+from tests.render_ref import macro as _macro          # the one reader of include/pih_model.h
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REF = os.path.join(ROOT, "tests", "golden", "model_assets")
-
-
-def _macro(name):
-    hdr = open(os.path.join(ROOT, "include", "pih_model.h")).read()
-    body = re.search(r"#define %s (.*)" % name, hdr).group(1).split("/*")[0]
-    return np.array(eval(body.replace("{", "[").replace("}", "]")), dtype=float)
 
 
 @pytest.fixture(scope="module")

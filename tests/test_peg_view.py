@@ -1,15 +1,8 @@
 """Free camera of the peg-in-hole task (pih_render_view, peg_in_hole_gym_amd/csrc/pih_view.h), CPU part: the product's per-scene and
-per-pixel code, compiled on the host in fp64 and fp32 (tests/emul/pih_view_emul.cpp), against a numpy fp64 ray caster written here from
-the camera and image semantics of include/pih.h.  The ray caster itself is anchored to the fp64 oracle: for the wrist preset it has to
-reproduce Oracle.render.  The GPU part is tests/test_gpu_peg_view.py, which takes the reference, the cameras and the comparison rules from
-this module.
-
-Two links of the stand-in arm are joint spheres that their neighbours' capsules partly or wholly cover (pih_view.h, header comment).
-Link 1's sphere is the end sphere of links 0 and 2: by the rule of pih_view.h (sphere links first, a later link needs a hit nearer by
-1e-5) it owns what the two cylinders leave of it, a lune on the outside of the bend between links 0 and 2 (0.215 rad at the rest pose:
-13 mm at its widest).  PIH_VIEW_CAM_OVERVIEW is aimed so that this lune owns pixels in all six states at all three sizes, so the
-overview has to show links 0, 1, 2, 3, 4 and 6.  Link 5's sphere (r = 0.055) lies inside the end spheres of links 4 and 6 (r = 0.06): no
-ray from outside reaches it first, and it must own no pixel in any image."""
+per-pixel code, compiled on the host in fp64 and fp32 (tests/emul/pih_view_emul.cpp, bound in tests/emul/render_emul.py), against the
+numpy fp64 ray caster of tests/render_ref.py.  The ray caster itself is anchored to the fp64 oracle here: for the wrist preset it has to
+reproduce Oracle.render.  States, cameras, comparison rules and tolerances are those of tests/render_cases.py, which the GPU part,
+tests/test_gpu_peg_view.py, shares."""
 import ctypes as C
 import os
 import re
@@ -19,362 +12,49 @@ import numpy as np
 import pytest
 
 from peg_in_hole_gym_amd import _lib
+from tests import render_cases as RC
+from tests import render_ref as R
+from tests.emul import render_emul
+from tests.emul.render_emul import view_render as host_render
+from tests.oracle_backend import RecordingBackend
+from tests.render_ref import COL_ARM, SEG_FINGER0
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SIZES = ((97, 61), (64, 64), (40, 30))          # (W, H): two tile columns, the second partial, rows no multiple of 16 | one tile column | narrower than a wave
-LIGHT = np.array([-50.0, 30.0, 100.0]) / np.linalg.norm([-50.0, 30.0, 100.0])
-AMBIENT, DIFFUSE = 0.6, 0.35
-CLASS_SHARE = 0.003                             # share of an image's pixels that may differ in class (silhouette rays in fp32; tests/test_render.py)
-ARM_TIE = 1e-5                                  # VIEW_ARM_TIE of pih_view.h
-ARM_ORDER = (1, 5, 0, 2, 3, 4, 6)               # ARM_ORDER of pih_view.h
-SEG_HAND, SEG_FINGER0 = 6, 7
-COL_ARM, COL_HAND, COL_PIPE, COL_TABLE, COL_BG = 204.0, 77.0, 232.0, 153.0, 255.0
-ANL = 9
-HOLE_AXIS_EYE = 0.25                            # the close-up looks along the hole's axis (x) from this far
-
-
-def _macro(name):
-    hdr = open(os.path.join(ROOT, "include", "pih_model.h")).read()
-    return np.array(eval(re.search(r"#define %s (.*)" % name, hdr).group(1).split("/*")[0].replace("{", "[").replace("}", "]").replace("(", "").replace(")", "")), dtype=float)
-
-
-HOLE_POS = _macro("PIH_HOLE_POS")
-TABLE_Z = float(_macro("PIH_TABLE_Z"))
-
-
-def cameras(W, H):
-    """name -> (13 camera words, frame)"""
-    hx, hy, hz = HOLE_POS
-    return {
-        "wrist": (list(_lib.VIEW_CAM_WRIST), "ee_pos"),
-        "overview": (list(_lib.VIEW_CAM_OVERVIEW), "env"),
-        "hole close-up": ([hx + HOLE_AXIS_EYE, hy, hz, hx, hy, hz, 0, 0, 1, 15, 1, 0.01, 100], "env"),
-        # forward along the tool axis (z of the grasp-target frame) from 2 cm behind the grasp target, between the pads: with closed fingers
-        # the eye lies on the pad faces, with open ones (the scripted state) the pads frame the image.  (An eye 2 cm in FRONT of the grasp
-        # target is under the table in the scripted state and sees nothing: replaced.)
-        "eye-in-hand": ([0, 0, -0.02, 0, 0, 0.98, 1, 0, 0, 60, 1, 0.01, 100], "ee"),
-        "horizon": ([1.6, 0, 0.5, 0, 0, 0.5, 0, 0, 1, 60, W / H, 0.01, 30], "env"),      # the table reaches the far plane
-    }
-
-
-CAMERA_NAMES = ("wrist", "overview", "hole close-up", "eye-in-hand", "horizon")
-FRAME_FLAG = {"env": 0, "ee": _lib.RENDER_CAM_EE, "ee_pos": _lib.RENDER_CAM_EE_POS}
-
-
-def _quat_matrix(q):
-    qx, qy, qz, qw = q
-    return np.array([[1 - 2 * (qy * qy + qz * qz), 2 * (qx * qy - qz * qw), 2 * (qx * qz + qy * qw)],
-                     [2 * (qx * qy + qz * qw), 1 - 2 * (qx * qx + qz * qz), 2 * (qy * qz - qx * qw)],
-                     [2 * (qx * qz - qy * qw), 2 * (qy * qz + qx * qw), 1 - 2 * (qx * qx + qy * qy)]])
-
-
-def _axis_angle(a, th):
-    K = np.array([[0, -a[2], a[1]], [a[2], 0, -a[0]], [-a[1], a[0], 0]])
-    return np.eye(3) + np.sin(th) * K + (1 - np.cos(th)) * (K @ K)
-
-
-# ------------------------------------------------------------------------------------------------ scenes
-def make_states(O):
-    """float32 [6, 256] records from the oracle: the rest pose, three resets, a scripted episode after the fingers have closed (the eye of
-    the wrist camera lies on the pad faces: the near-plane case of pih_render.h), 40 random-action steps.  Rounded to float32 here, so
-    every build and the reference see the same numbers."""
-    recs = [O.Oracle(1).get_state()[0]]
-    for seed in (11, 12, 13):
-        recs.append(O.Oracle(1, seed=seed).get_state()[0])
-    o = O.Oracle(1, mode=1, dv=0.05, seed=4)
-    for _ in range(1400):
-        o.step(np.zeros((1, 4)))
-        if o.get_state()[0, _lib.S_FSM] >= 4:
-            break
-    s = o.get_state()[0]
-    assert s[_lib.S_FSM] >= 4 and max(s[_lib.S_QARM + 7], s[_lib.S_QARM + 8]) < 0.03, "the scripted episode has not closed the fingers"
-    recs.append(s)
-    o = O.Oracle(1, seed=21); rng = np.random.default_rng(5)
-    for _ in range(40):
-        o.step(rng.uniform(-1, 1, (1, 4)))
-    recs.append(o.get_state()[0])
-    out = np.zeros((len(recs), _lib.STATE_WORDS), dtype=np.float32)       # (the oracle's record is the physical state; the warm-start words stay 0)
-    out[:, :O.STATE_WORDS] = np.array(recs)
-    return out
-
-
-def scene_geometry(O, rec):
-    """the primitives of one state record, fp64: arm origins [8, 3] (base, links 0..6), hand spheres (centres, radii), finger boxes
-    (R, centre), pipe vertices [25, 3], grasp-target pose (p, R)"""
-    rec = np.asarray(rec, dtype=np.float64)
-    q = rec[_lib.S_QARM:_lib.S_QARM + 9]
-    arm = [O.fk_arm(q, L) for L in range(ANL)]
-    org = np.array([np.zeros(3)] + [arm[L][0] for L in range(7)])
-    sl, sc, sr = _macro("PIH_ARM_SPH_LINK").astype(int), _macro("PIH_ARM_SPH_C"), _macro("PIH_ARM_SPH_R")
-    s0 = int(_macro("PIH_ARM_PIPE_SPH0"))
-    hand = [(arm[sl[i]][0] + _quat_matrix(arm[sl[i]][1]) @ sc[i], sr[i]) for i in range(s0, s0 + 4)]
-    assert all(sl[i] == 6 for i in range(s0, s0 + 4))
-    f0, fc = int(_macro("PIH_FINGER_LINK0")), _macro("PIH_FINGER_BOX_C")
-    boxes = [(_quat_matrix(arm[f0 + f][1]), arm[f0 + f][0] + _quat_matrix(arm[f0 + f][1]) @ fc[f]) for f in range(2)]
-    # the pipe chain from the tables: root = the free body, then revolute links
-    rfix, tfix, axis = _macro("PIH_LINK_RFIX").reshape(-1, 3, 3), _macro("PIH_LINK_TFIX"), _macro("PIH_LINK_AXIS")
-    R = _quat_matrix(rec[_lib.S_QUAT:_lib.S_QUAT + 4]); o = rec[_lib.S_POS:_lib.S_POS + 3].copy()
-    pose = [(o, R)]
-    for L in range(ANL + 1, len(tfix)):
-        o = o + R @ tfix[L]
-        R = R @ rfix[L] @ _axis_angle(axis[L], rec[_lib.S_QJ + L - ANL - 1])
-        pose.append((o, R))
-    slk, sy, sv = _macro("PIH_PIPE_SAMP_LINK").astype(int), _macro("PIH_PIPE_SAMP_Y"), _macro("PIH_PIPE_SAMP_VERTEX").astype(int)
-    vtx = np.array([pose[slk[i]][0] + pose[slk[i]][1] @ np.array([0, sy[i], 0]) for i in range(len(sv)) if sv[i]])
-    assert vtx.shape == (25, 3)
-    pe, qe = O.fk_arm(q, 9)
-    return org, hand, boxes, vtx, (pe, _quat_matrix(qe))
-
-
-def arm_radii():
-    sl, sc, sr = _macro("PIH_ARM_SPH_LINK").astype(int), _macro("PIH_ARM_SPH_C"), _macro("PIH_ARM_SPH_R")
-    r = [0.06] * 7
-    for i in range(len(sl)):
-        if sl[i] < 7 and not sc[i].any():
-            r[sl[i]] = sr[i]
-    assert r == [0.06, 0.06, 0.06, 0.06, 0.06, 0.055, 0.06]
-    return r
-
-
-# ------------------------------------------------------------------------------------------------ the reference
-def _ref_sphere(oc, d, r):
-    b = d @ oc; disc = b * b - (oc @ oc - r * r)
-    t = -b - np.sqrt(np.maximum(disc, 0.0))
-    return np.where((disc >= 0) & (t > 0), t, np.inf)
-
-
-def _ref_capsule(o, d, a, b, r):
-    ba, oa = b - a, o - a
-    baba, bard, baoa, rdoa, oaoa = ba @ ba, d @ ba, ba @ oa, d @ oa, oa @ oa
-    A = baba - bard * bard; B = baba * rdoa - baoa * bard; Cc = baba * oaoa - baoa * baoa - r * r * baba
-    h = B * B - A * Cc
-    with np.errstate(divide="ignore", invalid="ignore"):
-        t = (-B - np.sqrt(np.maximum(h, 0.0))) / A; y = baoa + t * bard
-        best = np.where((h >= 0) & (A > 1e-18) & (y > 0) & (y < baba) & (t > 0), t, np.inf)
-    return np.minimum(best, np.minimum(_ref_sphere(oa, d, r), _ref_sphere(o - b, d, r)))
-
-
-def _ref_tube(o, d):
-    hl, ri, ro = float(_macro("PIH_HOLE_HALFLEN")), float(_macro("PIH_HOLE_RIN")), float(_macro("PIH_HOLE_ROUT"))
-    oc = o - HOLE_POS
-    a = d[..., 1] ** 2 + d[..., 2] ** 2; b = oc[1] * d[..., 1] + oc[2] * d[..., 2]
-    best = np.full(d.shape[:2], np.inf)
-    with np.errstate(divide="ignore", invalid="ignore"):
-        for rr, sign in ((ro, -1.0), (ri, 1.0)):          # outer surface (entering), inner surface (leaving the bore wall from inside)
-            disc = b * b - a * (oc[1] ** 2 + oc[2] ** 2 - rr * rr)
-            t = (-b + sign * np.sqrt(np.maximum(disc, 0.0))) / a
-            ok = (a >= 1e-18) & (disc >= 0) & (t > 0) & (np.abs(oc[0] + t * d[..., 0]) <= hl) & (t < best)
-            best = np.where(ok, t, best)
-        for end in (-hl, hl):                             # annular end caps
-            t = (end - oc[0]) / d[..., 0]
-            r2 = (oc[1] + t * d[..., 1]) ** 2 + (oc[2] + t * d[..., 2]) ** 2
-            ok = (np.abs(d[..., 0]) >= 1e-15) & (t > 0) & (t < best) & (r2 >= ri * ri) & (r2 <= ro * ro)
-            best = np.where(ok, t, best)
-    return best
-
-
-def _ref_box(o, d, R, c, h):
-    ol = R.T @ (o - c); dl = d @ R
-    tmin = np.full(d.shape[:2], -np.inf); tmax = np.full(d.shape[:2], np.inf); miss = np.zeros(d.shape[:2], bool)
-    with np.errstate(divide="ignore", invalid="ignore"):
-        for k in range(3):
-            par = np.abs(dl[..., k]) < 1e-15
-            miss |= par & (abs(ol[k]) > h[k])
-            t1 = (-h[k] - ol[k]) / dl[..., k]; t2 = (h[k] - ol[k]) / dl[..., k]
-            lo, hi = np.minimum(t1, t2), np.maximum(t1, t2)
-            tmin = np.where(par, tmin, np.maximum(tmin, lo)); tmax = np.where(par, tmax, np.minimum(tmax, hi))
-    return np.where(miss | (tmin > tmax) | (tmax <= 0) | (tmin <= 0), np.inf, tmin)
-
-
-def _capsule_normal(ph, a, b):
-    ba = b - a
-    q = np.clip(((ph - a) @ ba) / max(ba @ ba, 1e-20), 0.0, 1.0)
-    r = ph - (a + q[:, None] * ba)
-    return r / np.maximum(np.linalg.norm(r, axis=-1, keepdims=True), 1e-12)
-
-
-def _tube_normal(ph):
-    hl, ri, ro = float(_macro("PIH_HOLE_HALFLEN")), float(_macro("PIH_HOLE_RIN")), float(_macro("PIH_HOLE_ROUT"))
-    oc = ph - HOLE_POS; rr = np.sqrt(oc[:, 1] ** 2 + oc[:, 2] ** 2)
-    cap = np.abs(oc[:, 0]) >= hl - 1e-5
-    k = np.where(rr > 0.5 * (ri + ro), 1.0, -1.0) / np.maximum(rr, 1e-12)
-    n = np.stack([np.zeros_like(rr), oc[:, 1] * k, oc[:, 2] * k], -1)
-    n[cap] = np.stack([np.where(oc[cap, 0] > 0, 1.0, -1.0), np.zeros(cap.sum()), np.zeros(cap.sum())], -1)
-    return n
-
-
-def _box_normal(ph, R, c, h):
-    pl = (ph - c) @ R; a = np.abs(pl) / h
-    nl = np.zeros_like(pl)
-    kx = (a[:, 0] >= a[:, 1]) & (a[:, 0] >= a[:, 2]); ky = ~kx & (a[:, 1] >= a[:, 2]); kz = ~kx & ~ky
-    for k, m in enumerate((kx, ky, kz)):
-        nl[m, k] = np.where(pl[m, k] > 0, 1.0, -1.0)
-    return nl @ R.T
-
-
-def reference_render(O, rec, cam, W, H, frame="env", cam_exact=False):
-    """-> (flat image, shaded image: float64 [H, W, 4] = depth value, r, g, b; seg [H, W]; eye-space depth z [H, W], inf where nothing was
-    hit).  rec: one env's state record; cam: 13 words, used as the float32 numbers the C ABI takes (cam_exact: as the doubles they are --
-    the oracle's near plane is 0.001, not float32(0.001), which is 1.8e-9 of depth value 2.7 cm above the table); frame: "env", "ee" or
-    "ee_pos"."""
-    cam = np.asarray(cam, dtype=np.float64) if cam_exact else np.asarray(cam, dtype=np.float32).astype(np.float64)
-    org, hand, boxes, vtx, (pe, Re) = scene_geometry(O, rec)
-    eye, target, up = cam[0:3], cam[3:6], cam[6:9]
-    fov, aspect, near, far = cam[9:13]
-    if frame == "ee":
-        eye, target, up = pe + Re @ eye, pe + Re @ target, Re @ up
-    elif frame == "ee_pos":
-        eye, target = pe + eye, pe + target
-    f = target - eye; f /= np.linalg.norm(f)
-    s = np.cross(f, up); s /= np.linalg.norm(s)
-    u = np.cross(s, f)
-    T = np.tan(np.radians(fov) / 2)
-    xc = (2 * (np.arange(W) + 0.5) / W - 1) * T * aspect
-    yc = (1 - 2 * (np.arange(H) + 0.5) / H) * T
-    d = f + xc[None, :, None] * s + yc[:, None, None] * u
-    d /= np.linalg.norm(d, axis=-1, keepdims=True)
-    df = d @ f
-    best = np.full((H, W), np.inf); seg = np.full((H, W), _lib.SEG_NONE); col = np.full((H, W), COL_BG); nrm = np.zeros((H, W, 3))
-
-    def clipped(t):
-        z = t * df
-        with np.errstate(invalid="ignore"):
-            return np.where(np.isfinite(t) & (t > 0) & (z >= near) & (z <= far), t, np.inf)
-
-    def take(t, sg, colour, normal_of):
-        m = t < best
-        if m.any():
-            best[m] = t[m]; seg[m] = sg; col[m] = colour
-            nrm[m] = normal_of(eye + t[m][:, None] * d[m])
-
-    with np.errstate(divide="ignore", invalid="ignore"):
-        t = (TABLE_Z - eye[2]) / d[..., 2]
-    take(clipped(np.where(np.isfinite(t), t, np.inf)), _lib.VIEW_SEG_TABLE, COL_TABLE, lambda ph: np.array([0.0, 0.0, 1.0]))
-    pr = float(_macro("PIH_PIPE_RADIUS"))
-    for sgm in range(24):
-        take(clipped(_ref_capsule(eye, d, vtx[sgm], vtx[sgm + 1], pr)), _lib.VIEW_SEG_PIPE0 + sgm, COL_PIPE, lambda ph, a=vtx[sgm], b=vtx[sgm + 1]: _capsule_normal(ph, a, b))
-    take(clipped(_ref_tube(eye, d)), _lib.VIEW_SEG_HOLE, COL_PIPE, _tube_normal)
-    bh = _macro("PIH_FINGER_BOX_H")
-    for k, (R, c) in enumerate(boxes):
-        take(clipped(_ref_box(eye, d, R, c, bh)), SEG_FINGER0 + k, COL_HAND, lambda ph, R=R, c=c: _box_normal(ph, R, c, bh))
-    for (c, r) in hand:
-        take(clipped(_ref_sphere(eye - c, d, r)), SEG_HAND, COL_HAND, lambda ph, c=c: (ph - c) / np.maximum(np.linalg.norm(ph - c, axis=-1, keepdims=True), 1e-12))
-    # the arm's own nearest hit first: sphere links first, a later link takes the pixel only if it is nearer by more than ARM_TIE
-    radii = arm_radii()
-    abest = np.full((H, W), np.inf); alink = np.full((H, W), -1)
-    for L in ARM_ORDER:
-        t = clipped(_ref_capsule(eye, d, org[L], org[L + 1], radii[L]))
-        m = t < abest * (1 - ARM_TIE)
-        abest[m] = t[m]; alink[m] = L
-    for L in range(7):
-        take(np.where(alink == L, abest, np.inf), L, COL_ARM, lambda ph, a=org[L], b=org[L + 1]: _capsule_normal(ph, a, b))
-    z = best * df
-    hit = np.isfinite(best)
-    depth = np.ones((H, W))
-    depth[hit] = far * (z[hit] - near) / (z[hit] * (far - near))
-    lit = AMBIENT + DIFFUSE * np.maximum(nrm @ LIGHT, 0.0)
-    rgb = np.repeat(col[..., None], 3, -1)
-    lit_rgb = np.where(hit[..., None], rgb * lit[..., None], rgb)
-    return np.concatenate([depth[..., None], rgb], -1), np.concatenate([depth[..., None], lit_rgb], -1), seg, np.where(hit, z, np.inf)
-
-
-def linear_depth(depth_value, cam):
-    near, far = [float(x) for x in np.asarray(cam, dtype=np.float32)[11:13]]
-    return near * far / (far - np.asarray(depth_value, dtype=np.float64) * (far - near))
-
-
-def check_reference_scene(name, W, H, seg, cam):
-    """What makes a scene worth comparing, asserted on the REFERENCE image"""
-    owned = set(np.unique(seg).tolist())
-    assert 5 not in owned, "link 5's sphere lies inside its neighbours' end spheres"
-    if name == "overview":
-        pipes = [s for s in owned if _lib.VIEW_SEG_PIPE0 <= s < _lib.VIEW_SEG_PIPE0 + 24]
-        assert {0, 1, 2, 3, 4, 6} <= owned and (owned & {SEG_FINGER0, SEG_FINGER0 + 1}) and len(pipes) >= 3 and {_lib.VIEW_SEG_HOLE, _lib.VIEW_SEG_TABLE} <= owned, sorted(owned)
-    if name == "hole close-up":
-        # the eye is on the hole's axis: the rays that clear the far rim of the bore by a fifth of its radius look through it, at whatever
-        # lies behind -- in some states the hand; background or table must be among it
-        T = np.tan(np.radians(cam[9]) / 2)
-        xc = (2 * (np.arange(W) + 0.5) / W - 1) * T * cam[10]; yc = (1 - 2 * (np.arange(H) + 0.5) / H) * T
-        bore = np.hypot(xc[None, :], yc[:, None]) < 0.8 * float(_macro("PIH_HOLE_RIN")) / (HOLE_AXIS_EYE + float(_macro("PIH_HOLE_HALFLEN")))
-        assert bore.sum() >= 4 and (seg[bore] != _lib.VIEW_SEG_HOLE).all() and np.isin(seg[bore], (_lib.VIEW_SEG_TABLE, _lib.SEG_NONE)).any(), seg[bore]
-        assert (seg == _lib.VIEW_SEG_HOLE).sum() >= 20 * bore.sum() // 16, (seg == _lib.VIEW_SEG_HOLE).sum()
-    if name == "eye-in-hand":
-        assert any(s > 6 and s != _lib.SEG_NONE for s in owned), sorted(owned)
-    if name == "horizon":
-        assert {_lib.VIEW_SEG_TABLE, _lib.SEG_NONE} <= owned, sorted(owned)
-
-
-def compare(img, seg, ref_img, ref_seg, ref_z, cam, exact_class):
-    """-> (max relative error of the eye-space depth, max absolute error of the depth-buffer value, array of absolute colour errors) over
-    the pixels whose class (seg value) agrees; asserts the class rule: identical everywhere (exact_class) or at most CLASS_SHARE of the
-    image different"""
-    same = seg == ref_seg
-    if exact_class:
-        assert same.all(), "%d pixels differ in class" % (~same).sum()
-    else:
-        assert (~same).mean() <= CLASS_SHARE, "%.4f of the pixels differ in class" % (~same).mean()
-    hit = same & (ref_seg != _lib.SEG_NONE)
-    assert (img[..., 0][same & (ref_seg == _lib.SEG_NONE)] == 1.0).all()
-    z = linear_depth(img[..., 0], cam)
-    zerr = (np.abs(z - ref_z)[hit] / ref_z[hit]).max() if hit.any() else 0.0
-    derr = np.abs(img[..., 0] - ref_img[..., 0])[hit].max() if hit.any() else 0.0
-    return zerr, derr, np.abs(img[..., 1:] - ref_img[..., 1:])[same].reshape(-1)
+ROOT = R.ROOT
 
 
 # ------------------------------------------------------------------------------------------------ host builds and references
-# the flags of tests/emul/Makefile
-CXXFLAGS = "-O2 -fPIC -Wl,-Bsymbolic -fno-gnu-unique -fvisibility-inlines-hidden -std=c++17 -Wall -Wno-unused-variable -Wno-unused-but-set-variable -Wno-unknown-pragmas -fno-fast-math".split()
-
-
 @pytest.fixture(scope="module")
 def host_builds(tmp_path_factory):
-    d = tmp_path_factory.mktemp("peg_view_emul")
-    libs = {}
-    for prec, real in (("f64", "double"), ("f32", "float")):
-        so = str(d / ("libpih_view_%s.so" % prec))
-        subprocess.check_call(["g++"] + CXXFLAGS + ["-DPIH_REAL=" + real, "-shared", "-o", so, os.path.join(ROOT, "tests", "emul", "pih_view_emul.cpp")])
-        L = C.CDLL(so)
-        L.pihv_render.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_float), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_uint8), C.POINTER(C.c_double)]
-        L.pihv_pack_byte.argtypes = [C.c_double]
-        assert L.pihv_real_bytes() == (8 if prec == "f64" else 4)
-        libs[prec] = L
-    return libs
-
-
-def host_render(L, rec, cam, W, H, shaded, frame, cull, expect=0):
-    """-> (float4 image [H, W, 4], rgba8 image [H, W, 4] uint8, depth image [H, W]) of the host build"""
-    rec = np.ascontiguousarray(rec, dtype=np.float64); cam = np.ascontiguousarray(cam, dtype=np.float32)
-    assert rec.shape == (_lib.STATE_WORDS,) and cam.shape == (_lib.CAM_WORDS,)
-    out = np.zeros((H, W, 4)); rgba = np.zeros((H, W, 4), dtype=np.uint8); depth = np.zeros((H, W))
-    flags = (_lib.RENDER_SHADED if shaded else 0) | FRAME_FLAG[frame]
-    rc = L.pihv_render(rec.ctypes.data_as(C.POINTER(C.c_double)), cam.ctypes.data_as(C.POINTER(C.c_float)), W, H, flags, int(cull),
-                       out.ctypes.data_as(C.POINTER(C.c_double)), rgba.ctypes.data_as(C.POINTER(C.c_uint8)), depth.ctypes.data_as(C.POINTER(C.c_double)))
-    assert rc == expect
-    return out, rgba, depth
+    return render_emul.libs(tmp_path_factory.mktemp("peg_view_emul"), "view")
 
 
 @pytest.fixture(scope="module")
 def states(oracle_mod):
-    return make_states(oracle_mod)
+    return RC.make_view_states(oracle_mod)
 
 
 @pytest.fixture(scope="module")
-def reference_images(oracle_mod, states):
+def scenes(oracle_mod, states):
+    return [R.peg_scene(oracle_mod, rec) for rec in states]
+
+
+@pytest.fixture(scope="module")
+def reference_images(states, scenes):
     """{(camera, (W, H), state index): (record, camera words, frame, flat reference, shaded reference, seg, z)}, computed once for the module.
     Every (state, camera) pair met its scene condition with the first choice of seeds: none had to be replaced."""
     out = {}
-    for name in CAMERA_NAMES:
-        for (W, H) in SIZES:
-            cam, frame = cameras(W, H)[name]
+    for name in RC.PEG_CAMERA_NAMES:
+        for (W, H) in RC.SIZES:
+            cam, frame = RC.peg_cameras(W, H)[name]
             for k, rec in enumerate(states):
-                flat, lit, seg, z = reference_render(oracle_mod, rec, cam, W, H, frame)
-                check_reference_scene(name, W, H, seg, cam)
+                flat, lit, seg, z = R.plain_reference(scenes[k], cam, W, H, frame)
+                RC.peg_check_reference_scene(name, W, H, seg, cam)
                 out[(name, (W, H), k)] = (rec, cam, frame, flat, lit, seg, z)
     return out
 
 
 # ------------------------------------------------------------------------------------------------ 1. the reference against the oracle
-def test_reference_reproduces_the_oracle_wrist_camera(oracle_mod, states, reference_images):
+def test_reference_reproduces_the_oracle_wrist_camera(oracle_mod, states, scenes, reference_images):
     """The wrist preset of the numpy ray caster == Oracle.render, flat and shaded, on all six states: colour class identical (which also
     says that the wrist camera never sees the arm), depth value <= 1e-9, colour <= 1e-6.  This anchors pipe, finger, tube and table
     geometry of the new reference to the fp64 oracle."""
@@ -383,7 +63,7 @@ def test_reference_reproduces_the_oracle_wrist_camera(oracle_mod, states, refere
     for k, rec in enumerate(states):
         o = O.Oracle(1); o.set_state(rec[:O.STATE_WORDS].astype(np.float64)[None])
         for (W, H) in ((97, 61), (40, 30)):
-            flat, lit, seg, _ = reference_render(O, rec, _lib.VIEW_CAM_WRIST, W, H, "ee_pos", cam_exact=True)
+            flat, lit, seg, _ = R.plain_reference(scenes[k], _lib.VIEW_CAM_WRIST, W, H, "ee_pos", cam_exact=True)
             assert np.array_equal(seg, reference_images[("wrist", (W, H), k)][5])
             a, b = o.render(W, H)[0], o.render(W, H, shaded=True)[0]
             assert np.array_equal(a[..., 1:], flat[..., 1:]), (k, W, H, int((a[..., 1] != flat[..., 1]).sum()))
@@ -399,7 +79,7 @@ def test_reference_reproduces_the_oracle_wrist_camera(oracle_mod, states, refere
 def test_host_build_matches_the_reference(host_builds, reference_images, prec):
     """All five cameras, six states, three sizes, flat and shaded.  fp64: class identical on every pixel, relative depth error and depth
     value error <= 1e-9, colour error <= 1e-6.  fp32: at most CLASS_SHARE of an image's pixels differ in class; the maximum errors are
-    printed -- they are the yardstick of the GPU tolerances (tests/test_gpu_peg_view.py), which the host build itself has to meet.  Both:
+    printed -- they are the yardstick of the GPU tolerances (RC.PEG_*_TOL), which the host build itself has to meet.  Both:
     the image rendered with the tile lists of the product's screen-bound test equals the one rendered with every primitive on for every
     tile, bit for bit, in all three formats."""
     L = host_builds[prec]
@@ -413,7 +93,7 @@ def test_host_build_matches_the_reference(host_builds, reference_images, prec):
                 assert np.array_equal(a, b), (name, W, H, k, shaded, int((a != b).sum()))
             img, rgba, _ = culled
             worst_share = max(worst_share, (rgba[..., 3] != rseg).mean())
-            zerr, derr, cerr = compare(img, rgba[..., 3], rlit if shaded else rflat, rseg, rz, cam, exact_class=prec == "f64")
+            zerr, derr, cerr = RC.compare(img, rgba[..., 3], rlit if shaded else rflat, rseg, rz, cam, _lib.SEG_NONE, exact_class=prec == "f64")
             zmax = max(zmax, zerr); dmax = max(dmax, derr)
             if shaded:
                 cmax_shaded = max(cmax_shaded, cerr.max()); shaded_err.append(cerr)
@@ -425,9 +105,8 @@ def test_host_build_matches_the_reference(host_builds, reference_images, prec):
     if prec == "f64":
         assert zmax <= 1e-9 and dmax <= 1e-9 and max(cmax_flat, cmax_shaded) <= 1e-6
     else:
-        from tests import test_gpu_peg_view as G
-        assert zmax <= G.DEPTH_REL_TOL and dmax <= G.DEPTH_VALUE_TOL and cmax_flat <= G.COLOUR_TOL
-        assert np.percentile(shaded_err, 99) < G.SHADED_P99 and np.median(shaded_err) < G.SHADED_MEDIAN
+        assert zmax <= RC.PEG_DEPTH_REL_TOL and dmax <= RC.PEG_DEPTH_VALUE_TOL and cmax_flat <= RC.PEG_COLOUR_TOL
+        assert np.percentile(shaded_err, 99) < RC.SHADED_P99 and np.median(shaded_err) < RC.SHADED_MEDIAN
 
 
 # ------------------------------------------------------------------------------------------------ 6. formats
@@ -466,11 +145,11 @@ def test_degenerate_camera_gives_the_background(host_builds, states):
 
 # ------------------------------------------------------------------------------------------------ 7. coincident link origins
 @pytest.mark.parametrize("prec", ["f64", "f32"])
-def test_links_whose_origins_coincide_render_as_spheres(oracle_mod, host_builds, states, prec):
+def test_links_whose_origins_coincide_render_as_spheres(oracle_mod, host_builds, states, scenes, prec):
     """Link 1's origin is link 0's (PIH_LINK_TFIX[1] = 0): its capsule is the sphere of radius 0.06 around the shoulder.  Known answer: the
     ray through the shoulder centre (the centre pixel of an odd-sized image aimed at it) hits at |eye - centre| - 0.06, on link 1 -- links 0
     and 2 end in the same sphere, and the rule of pih_view.h gives it to the sphere link."""
-    org = scene_geometry(oracle_mod, states[0])[0]
+    org = R.scene_geometry(oracle_mod, states[0])[0]
     centre = org[1]
     assert np.array_equal(org[1], org[2]) and np.array_equal(org[5], org[6]) and np.allclose(centre, [0, 0, 0.333])
     # eyes level with the shoulder, where link 0's cylinder (below) is not in the way, and on the side link 2's cylinder leans away from or
@@ -483,8 +162,8 @@ def test_links_whose_origins_coincide_render_as_spheres(oracle_mod, host_builds,
         assert rgba[2, 2, 3] == 1 and img[2, 2, 1] == COL_ARM
         # fp32: the depth-buffer value near 1 has a quantum of 2^-24, which is z^2 / near times that in z (near = 0.01); four of them
         tol = 1e-12 * dist if prec == "f64" else 4 * dist ** 2 / 0.01 * 2.0 ** -24
-        assert abs(linear_depth(img[2, 2, 0], cam) - (dist - 0.06)) <= tol, (linear_depth(img[2, 2, 0], cam), dist - 0.06)
-        ref = reference_render(oracle_mod, states[0], cam, 5, 5)
+        assert abs(RC.linear_depth(img[2, 2, 0], cam) - (dist - 0.06)) <= tol, (RC.linear_depth(img[2, 2, 0], cam), dist - 0.06)
+        ref = R.plain_reference(scenes[0], cam, 5, 5)
         assert ref[2][2, 2] == 1 and abs(ref[3][2, 2] - (dist - 0.06)) <= 1e-12
 
 
@@ -522,20 +201,8 @@ def test_library_exports_the_view_camera():
     assert hasattr(L, "pih_render_view")
 
 
-class _FakeBackend:
-    def __init__(self, n, offsets, **cfg):
-        self.n, self.cfg, self.calls = n, cfg, []
-
-    def reset(self, mask=None, hard_reset=False):
-        pass
-
-    def render_view(self, **kw):
-        self.calls.append(kw)
-        return "image"
-
-
 def test_peg_in_hole_render_view_delegates_to_the_backend():
     from peg_in_hole_gym_amd.envs.peg_in_hole import PegInHole
-    t = PegInHole(backend_factory=_FakeBackend)
+    t = PegInHole(backend_factory=RecordingBackend)
     assert t.render_view(camera=list(_lib.VIEW_CAM_OVERVIEW), fmt="rgba8", width=64, height=48) == "image"
     assert t._backend.calls == [dict(camera=list(_lib.VIEW_CAM_OVERVIEW), fmt="rgba8", width=64, height=48)] and t._backend.cfg["task_id"] == 0

@@ -15,6 +15,7 @@ import pytest
 
 from tests import robot_cases as rc
 from tests.emul import robot_emul
+from tests.oracle_backend import RecordingBackend
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ROBOTS = (rc.PANDA, rc.UR5)
@@ -300,21 +301,10 @@ def test_argument_checks_that_need_no_device():
     assert L.pih_robot_dims(0, None) == -2 and "out" in L.pih_last_error(None).decode()
 
 
-class _FakeBackend:
-    def __init__(self, n, offsets, **cfg):
-        self.calls = []
-
-    def reset(self, mask=None):
-        pass
-
-    def link_states(self, **kw):
-        self.calls.append(kw); return "states"
-
-
 def test_task_classes_delegate_link_states():
     from peg_in_hole_gym_amd.envs.peg_in_hole import PegInHole, RandomFly
     for cls in (PegInHole, RandomFly):
-        t = cls(backend_factory=_FakeBackend)
+        t = cls(backend_factory=RecordingBackend)
         assert t.link_states(env_begin=0) == "states" and t._backend.calls == [{"env_begin": 0}]
 
 
