@@ -324,6 +324,8 @@ def _fly_protos(L):
     L.piho_fly_set_state.argtypes = [C.c_void_p, dp]
     L.piho_fly_debug_contacts.argtypes = [C.c_void_p, C.c_int, dp]
     L.piho_fly_debug_udot.argtypes = [C.c_void_p, C.c_int, dp]
+    for f in ("piho_fly_debug_rows", "piho_fly_get_pgs_residual", "piho_fly_get_clamp_margin"):
+        getattr(L, f).argtypes = [C.c_void_p, dp]
     L.piho_fly_mass_matrix.argtypes = [dp, dp]
     L.piho_fly_arm_kinetic_energy.argtypes = [dp, dp]
     L.piho_fly_arm_kinetic_energy.restype = C.c_float if L._np_real is np.float32 else C.c_double
@@ -383,6 +385,18 @@ class FlyOracle:
 
     def debug_udot(self, env=0):
         out = np.zeros(12, self.real); self.L.piho_fly_debug_udot(self.h, env, _dp(out)); return out
+
+    def debug_rows(self):
+        """[n, 6, 3]: the motor, lower-limit and upper-limit multiplier of every arm joint after the last step"""
+        out = np.zeros((self.n, 6, 3), self.real); self.L.piho_fly_debug_rows(self.h, _dp(out)); return out
+
+    def pgs_residual(self):
+        """largest squared row residual of the last sweep of the last step"""
+        r = np.zeros(self.n, self.real); self.L.piho_fly_get_pgs_residual(self.h, _dp(r)); return r
+
+    def clamp_margin(self):
+        """smallest |lambda + dl - bound| of any row from a finite bound of its clamp (0, +-effort dt) over all sweeps of the last step"""
+        r = np.zeros(self.n, self.real); self.L.piho_fly_get_clamp_margin(self.h, _dp(r)); return r
 
 
 def fly_object_names():

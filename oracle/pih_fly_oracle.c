@@ -53,6 +53,7 @@ typedef struct {
   FContact contacts[FNC]; int ncontacts, landed;
   real contact_force, udot[FND];
   int pgs_iters;
+  real joint_lambda[3 * FNJ], pgs_residual, clamp_margin;   /* read-outs of the last step's solve (piho_fly_debug_rows and the getters below) */
 } FEnv;
 struct piho_fly_handle { piho_config cfg; FEnv* env; };
 
@@ -320,6 +321,7 @@ static void fly_step_env(piho_fly_handle* h, int e, const real* action, real* ob
   }
   real dv[FND]; memset(dv, 0, sizeof dv);
   E->pgs_iters = 0;
+  real res_last = 0, margin = 1e30;      /* read-outs only: neither enters the arithmetic of the sweep */
   for (int it = 0; it < c->solver_iters; it++) {
     real res2 = 0;
     E->pgs_iters = it + 1;
@@ -327,14 +329,26 @@ static void fly_step_env(piho_fly_handle* h, int e, const real* action, real* ob
       FRow* r = &rows[i];
       real jd = 0; for (int k = 0; k < FND; k++) jd += r->J[k] * dv[k];
       real dl = r->rhs - jd * r->dinv, sum = r->lambda + dl;
+#ifndef PIHO_FLY_NO_READOUTS      /* (defined by tests/test_fly_stages.py alone: a second build whose step must give the same bits) */
+      { real m = fabs(sum - r->lo); if (r->hi < 1e29 && fabs(sum - r->hi) < m) m = fabs(sum - r->hi); if (m < margin) margin = m; }
+#endif
       if (sum < r->lo) { dl = r->lo - r->lambda; sum = r->lo; } else if (sum > r->hi) { dl = r->hi - r->lambda; sum = r->hi; }
       r->lambda = sum;
       for (int k = 0; k < FND; k++) dv[k] += r->W[k] * dl;
       real rs = dl / r->dinv; if (rs * rs > res2) res2 = rs * rs;
     }
+#ifndef PIHO_FLY_NO_READOUTS
+    res_last = res2;
+#endif
     if (exit_checked(it + 1, c->solver_iters, c->exit_check_stride) && res2 <= c->residual_threshold) break;   /* cadence: 1 = Bullet's (every iteration); s > 1 = the product's */
   }
   for (int i = 0; i < FND; i++) u[i] = clampd(u[i] + dv[i], -MAX_COORD_VEL, MAX_COORD_VEL);
+#ifndef PIHO_FLY_NO_READOUTS
+  E->pgs_residual = res_last; E->clamp_margin = margin;
+  for (int i = 0; i < 3 * FNJ; i++) E->joint_lambda[i] = rows[i].lambda;
+#else
+  (void)res_last; (void)margin;
+#endif
   E->contact_force = 0;
   for (int k = 0; k < FNC; k++) if (crow[k] >= 0) { E->contacts[k].lambda = rows[crow[k]].lambda; E->contact_force += rows[crow[k]].lambda / dt; }
 
@@ -418,6 +432,12 @@ void piho_fly_debug_contacts(const piho_fly_handle* h, int env, real* out) {
     if (!c->valid) for (int i = 1; i < 10; i++) o[i] = 0;
   }
 }
+/* [n, 6, 3]: the motor, lower-limit and upper-limit multiplier of every arm joint after the last step */
+void piho_fly_debug_rows(const piho_fly_handle* h, real* out) { for (int e = 0; e < h->cfg.n_envs; e++) memcpy(out + (size_t)e * 3 * FNJ, h->env[e].joint_lambda, sizeof(real) * 3 * FNJ); }
+/* largest squared row residual of the last sweep of the last step (what the exit test compares with residual_threshold) */
+void piho_fly_get_pgs_residual(const piho_fly_handle* h, real* out) { for (int e = 0; e < h->cfg.n_envs; e++) out[e] = h->env[e].pgs_residual; }
+/* smallest distance |lambda + dl - bound| of any row from a finite bound of its clamp (0, +-effort dt) over all sweeps of the last step */
+void piho_fly_get_clamp_margin(const piho_fly_handle* h, real* out) { for (int e = 0; e < h->cfg.n_envs; e++) out[e] = h->env[e].clamp_margin; }
 void piho_fly_debug_udot(const piho_fly_handle* h, int env, real* out) { memcpy(out, h->env[env].udot, sizeof(real) * FND); }
 void piho_fly_mass_matrix(const real q[6], real M[36]) {
   FLink K[FNJ]; fly_fk(q, K, NULL, NULL);

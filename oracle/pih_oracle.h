@@ -164,6 +164,9 @@ void piho_fly_debug_contacts(const piho_fly_handle* h, int env, piho_real* out /
 int piho_fly_num_contact_slots(void);    /* 2 x PIH_FLY_OBJ_MAXSPH (object sphere vs arm, vs table) + 5 (arm links 1..5 vs table) */
 const char* piho_fly_object_name(int object_id);   /* PIH_FLY_OBJ_NAMES[object_id], NULL past the end */
 void piho_fly_debug_udot(const piho_fly_handle* h, int env, piho_real* out /* [12] */);
+void piho_fly_debug_rows(const piho_fly_handle* h, piho_real* out /* [n,6,3]: motor, lower-limit, upper-limit multiplier per arm joint, last step */);
+void piho_fly_get_pgs_residual(const piho_fly_handle* h, piho_real* out /* [n] largest squared row residual of the last sweep */);
+void piho_fly_get_clamp_margin(const piho_fly_handle* h, piho_real* out /* [n] smallest |lambda + dl - bound| over rows and sweeps, last step */);
 void piho_fly_mass_matrix(const piho_real q[6], piho_real M[36]);
 piho_real piho_fly_arm_kinetic_energy(const piho_real q[6], const piho_real qd[6]);
 void piho_fly_random_pos(uint64_t seed, uint64_t ctr, piho_real out[3]);   /* envs/utils.py:97-107 with the counter RNG */
