@@ -185,8 +185,13 @@ PIH_HD void step_env(W& w, Shared& sh, const Params& P, const Ovf& ov, int env, 
   real rew = norm(dh) < (real)0.05 ? (real)1 : (real)0;
   for (int i = 0; i < 7; i++) S[PIH_S_TIP + i] = tip[i];
   S[PIH_S_EE] = eep.x + S[PIH_S_OFFSET]; S[PIH_S_EE + 1] = eep.y + S[PIH_S_OFFSET + 1]; S[PIH_S_EE + 2] = eep.z + S[PIH_S_OFFSET + 2];
-  bool bad = false;
-  for (int i = 0; i < 86; i++) bad = bad || !finite_small(S[i]);
+  // non-finite words among the 86 checked ones: lane = word, a hit raises a flag word in LDS (r_lam is dead here: the warm-start cache
+  // and the contact force were taken from it before the sync above; a frozen env never filled it)
+  real* const flag = sh.r_lam;
+  w.sync();
+  flag[0] = 0;
+  w.par(86, [&](int i) { if (!finite_small(S[i])) flag[0] = 1; });
+  const bool bad = flag[0] != 0;
   if (!frozen && P.mode == 0 && (rew > 0 || S[PIH_S_STEPS] >= (real)P.maxsteps)) S[PIH_S_DONE] = 1;
   obs[0] = S[PIH_S_QARM + 7]; obs[1] = S[PIH_S_QARM + 8];
   obs[2] = eep.x + S[PIH_S_OFFSET]; obs[3] = eep.y + S[PIH_S_OFFSET + 1]; obs[4] = eep.z + S[PIH_S_OFFSET + 2];
