@@ -282,5 +282,9 @@ const char* pih_last_error(pih_handle* h);
 /* words of a link state of the robot-model queries declared in pih_robot.h: pos (3), quat xyzw (4), linear velocity of the frame origin (3),
  * angular velocity (3).  Defined here for the same reason */
 #define PIH_LINK_STATE_WORDS 13
+/* words of a ray (from xyz, to xyz) and of a ray's record (hit fraction, seg, hit position xyz, normal xyz) of the batched ray test declared
+ * in pih_robot.h.  Defined here for the same reason */
+#define PIH_RAY_WORDS 6
+#define PIH_RAY_HIT_WORDS 8
 #include "pih_robot.h"
 #endif

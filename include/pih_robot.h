@@ -1,4 +1,4 @@
-/* pih_robot.h -- C ABI of the batched robot-model queries (libpih_hip.so); an addition to pih.h, which includes this file: include pih.h.
+/* pih_robot.h -- C ABI of the batched robot-model and scene queries (libpih_hip.so); an addition to pih.h, which includes this file: include pih.h.
  * The ABI version stays PIH_ABI_VERSION (the change is additive).  Declared here and not in pih.h for the reason pih_render_view.h
  * states: tests pin the list of functions pih.h itself declares; tests/test_robot_query.py compares _lib.ROBOT_EXPORTS with THIS file.
  *
@@ -7,6 +7,7 @@
  *   pih_robot_jacobian                 p.calculateJacobian(body, link, localPosition, q, ...)
  *   pih_robot_mass_matrix              p.calculateMassMatrix(body, q)
  *   pih_robot_inverse_dynamics         p.calculateInverseDynamics(body, q, qd, qdd)  -- see the damping note below
+ *   pih_ray_test                       p.rayTestBatch(from, to, parentObjectUniqueId, parentLinkIndex)  -- the scene query, at the end
  *
  * Conventions: n problems, independent of the handle's env count (as pih_ik); both robots work on a handle of either task (as pih_ik /
  * pih_ik_ur5).  Every pointer is a DEVICE pointer to float32, row-major, contiguous.  Nothing synchronises: the work is enqueued on the
@@ -63,6 +64,40 @@ int pih_robot_inverse_dynamics(pih_handle* h, int robot, int n, const float* q_d
  *   random-fly:  the 7 UR5 frames, then the object
  * env_begin < 0, env_count <= 0 or env_begin + env_count > n_envs: -2, as pih_render_cam. */
 int pih_link_states(pih_handle* h, float* out_dev, int env_begin, int env_count, void* stream);
+
+/* Batched ray tests against the scene the task's free camera draws, at the envs' CURRENT state: rays_per_env rays for each of the envs
+ * env_begin .. env_begin + env_count - 1, on handles of both tasks.
+ *   peg-in-hole  the 38 primitives of pih_render_view -- 7 arm capsules, 4 hand spheres, 2 finger boxes, 24 pipe capsules, the hole
+ *                tube -- and the table plane
+ *   random-fly   the 6 UR5 capsules, the object's spheres and the table plane of pih_render_cam
+ * A ray is PIH_RAY_WORDS floats: the segment from (words 0..2) to (words 3..5) in the env-local frame (the env's offset does not enter,
+ * as for the cameras), or with PIH_RAY_FRAME_EE in the end-effector frame of each env.  rays_dev float[env_count, rays_per_env, 6], or
+ * with PIH_RAY_SHARED float[rays_per_env, 6].
+ * out_dev float[env_count, rays_per_env, PIH_RAY_HIT_WORDS], per ray:
+ *   word 0      hit fraction in (0, 1]: where along from -> to the nearest hit lies; 1 = no hit, as p.rayTestBatch reports it
+ *   word 1      what was hit, the task's segmentation value as a float -- peg-in-hole: arm link 0 .. 6 (the hand is 6), fingers 7 and 8,
+ *               PIH_VIEW_SEG_HOLE, PIH_VIEW_SEG_TABLE, PIH_VIEW_SEG_PIPE0 + pipe capsule; random-fly: link 0 .. 5, PIH_SEG_OBJECT,
+ *               PIH_SEG_TABLE; PIH_SEG_NONE for no hit
+ *   words 2..4  hit position, words 5..7 outward unit normal, both env-local whatever frame the ray came in
+ *   no hit      1, PIH_SEG_NONE, position = to (env-local), normal 0
+ * Hits are entry hits of front faces with ray parameter 0 < t <= |to - from|: a ray that starts inside a sphere, a capsule or a box does
+ * not hit it (but a ray from inside a long capsule along its axis reports the end sphere it runs into); the hole's bore wall is hit from
+ * inside the bore; the table plane is two-sided, its normal +z.  The nearest hit wins;
+ * among the peg-in-hole arm's overlapping capsules the rule of pih_render_view decides, so a ray through a pixel centre names the link
+ * the rgba8 image's seg byte names.
+ * A ray with a word that is NaN, infinite or beyond 1e15, or shorter than 1e-15, gets the no-hit record with the position words = its
+ * `to` words as given; no other ray is affected, and no table is indexed by anything derived from ray data.
+ * Errors: -2, and pih_last_error names the argument: a NULL handle (pih_last_error(NULL)), NULL out_dev or rays_dev, rays_per_env < 1 or
+ * > 2^20, env_begin / env_count outside the handle's envs (as pih_link_states) or env_count > 65535, an unknown flag bit, out_dev or
+ * rays_dev not 16-byte aligned.  Nothing synchronises: the work is enqueued on the caller's stream. */
+#define PIH_RAY_FRAME_EE     1  /* rays are given in the end-effector frame of each env: peg-in-hole the grasp-target frame
+                                   (as PIH_RENDER_CAM_EE of pih_render_view), random-fly ee_link (as PIH_RENDER_CAM_EE) */
+#define PIH_RAY_SHARED       2  /* rays_dev is float[rays_per_env, 6], the same rays for every env of the call
+                                   (default: float[env_count, rays_per_env, 6]) */
+#define PIH_RAY_IGNORE_ROBOT 4  /* the arm is transparent: peg-in-hole arm capsules, hand spheres and finger boxes;
+                                   random-fly the six UR5 capsules (a sensor mounted on the hand looks out through it) */
+int pih_ray_test(pih_handle* h, float* out_dev, const float* rays_dev, int rays_per_env,
+                 int env_begin, int env_count, int flags, void* stream);
 #ifdef __cplusplus
 }
 #endif

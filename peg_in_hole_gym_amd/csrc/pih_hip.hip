@@ -639,6 +639,25 @@ int pih_link_states(pih_handle* h, float* out_dev, int env_begin, int env_count,
   return 0;
 }
 
+// ---- batched ray tests (include/pih_robot.h; kernels in pih_rays.hip)
+int pih_ray_test(pih_handle* h, float* out_dev, const float* rays_dev, int rays_per_env, int env_begin, int env_count, int flags, void* stream) {
+  if (!h) return robot_bad(h, "pih_ray_test", "h", "is NULL");
+  if (!out_dev) return robot_bad(h, "pih_ray_test", "out_dev", "is NULL");
+  if (!rays_dev) return robot_bad(h, "pih_ray_test", "rays_dev", "is NULL");
+  if (rays_per_env < 1) return robot_bad(h, "pih_ray_test", "rays_per_env", "is smaller than 1");
+  if (rays_per_env > (1 << 20)) return robot_bad(h, "pih_ray_test", "rays_per_env", "is larger than 2^20");
+  if (env_begin < 0 || env_count <= 0 || env_begin > h->cfg.n_envs || env_count > h->cfg.n_envs - env_begin)
+    return robot_bad(h, "pih_ray_test", "env_begin / env_count", "is outside the handle's envs");
+  if (env_count > 65535) return robot_bad(h, "pih_ray_test", "env_count", "is larger than 65535 per call");
+  if ((flags & ~(PIH_RAY_FRAME_EE | PIH_RAY_SHARED | PIH_RAY_IGNORE_ROBOT)) != 0) return robot_bad(h, "pih_ray_test", "flags", "has an unknown bit");
+  if ((reinterpret_cast<uintptr_t>(out_dev) & 15) != 0) return robot_bad(h, "pih_ray_test", "out_dev", "must be 16-byte aligned");
+  if ((reinterpret_cast<uintptr_t>(rays_dev) & 15) != 0) return robot_bad(h, "pih_ray_test", "rays_dev", "must be 16-byte aligned");
+  PIH_ENTER(h);
+  ray_test_launch(h->fly, (hipStream_t)stream, h->state, out_dev, rays_dev, rays_per_env, h->cfg.n_envs, h->P.object, env_begin, env_count, flags);
+  HIPCHK(h, hipGetLastError());
+  return 0;
+}
+
 const char* pih_last_error(pih_handle* h) { return h ? h->err.c_str() : g_err.c_str(); }
 
 }  // extern "C"

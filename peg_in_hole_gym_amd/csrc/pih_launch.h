@@ -62,4 +62,7 @@ void robot_invdyn_launch(int robot, hipStream_t stream, int n, const float* q, c
 void link_states_launch(bool fly_task, hipStream_t stream, const float* state, float* out, int n_envs, int env_begin, int env_count);
 int robot_dims(int robot, int* ndof, int* nframes);
 int link_states_frames(int task_id);
+// ---- pih_rays.hip: the batched ray tests of include/pih_robot.h
+void ray_test_launch(bool fly_task, hipStream_t stream, const float* state, float* out, const float* rays_dev, int rays_per_env,
+                     int n_envs, int object, int env_begin, int env_count, int flags);
 }  // namespace pih

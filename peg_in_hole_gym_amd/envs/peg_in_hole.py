@@ -124,6 +124,11 @@ class PegInHole(MetaEnv):
         (PihVecEnv.link_states) -> the backend's [envs, 34, 13] tensor"""
         return self._backend.link_states(**kw)
 
+    def ray_test(self, rays, **kw):
+        """rayTestBatch against the scene of render_view -- arm, hand, fingers, pipe, hole, table -- at the current state
+        (PihVecEnv.ray_test: frame, ignore_robot, env_begin, env_count, out) -> the backend's [envs, rays, 8] tensor"""
+        return self._backend.ray_test(rays, **kw)
+
 
 class RandomFly(MetaEnv):
     """'random-fly' (README.md:38: task='random-fly', args=['Banana', 1/120.]): the UR5 of assets/urdf/ur5.urdf driven by
@@ -165,3 +170,8 @@ class RandomFly(MetaEnv):
         """getLinkStates(computeLinkVelocity=1) of the UR5's 7 frames and the object in world coordinates (PihVecEnv.link_states) -> the
         backend's [envs, 8, 13] tensor"""
         return self._backend.link_states(**kw)
+
+    def ray_test(self, rays, **kw):
+        """rayTestBatch against the scene of render(camera=...) -- UR5, object, table -- at the current state (PihVecEnv.ray_test: frame,
+        ignore_robot, env_begin, env_count, out) -> the backend's [envs, rays, 8] tensor"""
+        return self._backend.ray_test(rays, **kw)

@@ -38,6 +38,31 @@ def random_lights(n, device, generator=None, elevation=(20.0, 80.0)):
     return light
 
 
+def ray_fan(origin, axis, half_angle_deg, rings, per_ring, length, device=None):
+    """A cone of rays for PihVecEnv.ray_test, the proximity-sensor pattern: float32 [1 + rings * per_ring, 6] rows (from, to).  Every ray
+    starts at `origin` and is `length` long; ray 0 runs along `axis`, ring k = 1 .. rings holds per_ring rays at the angle
+    half_angle_deg * k / rings from the axis, equally spaced around it (ring k turned by half a spacing against ring k - 1).  origin and
+    axis: 3 numbers or tensors (axis need not be unit).  Pure torch on `device` (default: origin's, if it is a tensor): no host round
+    trip."""
+    if rings < 0 or per_ring < 1 or not (0.0 <= float(half_angle_deg) < 180.0):
+        raise ValueError("ray_fan: rings >= 0, per_ring >= 1 and 0 <= half_angle_deg < 180, got %r, %r, %r" % (rings, per_ring, half_angle_deg))
+    if device is None:
+        device = origin.device if torch.is_tensor(origin) else "cpu"
+    o = torch.as_tensor(origin, dtype=torch.float32).to(device).reshape(3)
+    a = torch.as_tensor(axis, dtype=torch.float32).to(device).reshape(3)
+    a = a / torch.linalg.norm(a)
+    # a unit vector across the axis: from the coordinate axis the cone's axis is furthest from
+    helper = torch.where(a[0].abs() < 0.9, torch.tensor([1.0, 0.0, 0.0], device=device), torch.tensor([0.0, 1.0, 0.0], device=device))
+    u = torch.linalg.cross(a, helper); u = u / torch.linalg.norm(u)
+    v = torch.linalg.cross(a, u)
+    k = torch.arange(1, rings + 1, dtype=torch.float32, device=device).repeat_interleave(per_ring)
+    j = torch.arange(per_ring, dtype=torch.float32, device=device).repeat(rings)
+    polar = torch.cat([torch.zeros(1, device=device), torch.deg2rad(torch.as_tensor(float(half_angle_deg), device=device)) * k / max(rings, 1)])
+    azim = torch.cat([torch.zeros(1, device=device), (j + 0.5 * k) * (2.0 * np.pi / per_ring)])
+    d = torch.cos(polar)[:, None] * a + torch.sin(polar)[:, None] * (torch.cos(azim)[:, None] * u + torch.sin(azim)[:, None] * v)
+    return torch.cat([o.expand(len(d), 3), o + float(length) * d], dim=1).contiguous()
+
+
 class PihVecEnv:
     """N independent worlds of one task on one MI355X.
 
@@ -288,6 +313,46 @@ class PihVecEnv:
         with torch.cuda.device(self.device):
             self._chk(self.L.pih_link_states(self.h, out.data_ptr(), int(env_begin), int(count), self._stream()), "pih_link_states")
         return out
+
+    _RAY_FRAME = {"env": 0, "ee": _lib.RAY_FRAME_EE}
+
+    def ray_test(self, rays, frame="env", ignore_robot=False, env_begin=0, env_count=None, out=None):
+        """rayTestBatch against the scene the task's free camera draws, at the envs' CURRENT state (pih_ray_test, include/pih_robot.h):
+        peg-in-hole arm, hand, finger pads, pipe, hole and table; random-fly UR5, object and table.
+        rays: [R, 6] = (from xyz, to xyz), the same rays for every env of the call, or [count, R, 6], one set per env (row e: env
+            env_begin + e).  A float32 tensor on this handle's device is used in place, anything else is converted and moved there.
+        frame: "env" = the env-local frame (the env offset does not enter); "ee" = the end-effector frame of each env (peg-in-hole: the
+            grasp-target frame; random-fly: ee_link) -- parentObjectUniqueId / parentLinkIndex of rayTestBatch.
+        ignore_robot: the arm is transparent (a sensor mounted on the hand looks out through it).
+        -> float32 [count, R, 8] on the device: hit fraction in (0, 1] (1 = no hit), what was hit (the seg values of render_view /
+        render's "rgba8" format as floats, _lib.SEG_NONE for nothing), hit position xyz and outward unit normal xyz, both env-local.
+        No hit: position = the ray's end, normal 0.  A ray with a NaN / Inf word or of zero length reports no hit; the others of the call
+        are not affected.  out: a contiguous float32 tensor of that shape on this handle's device (ValueError otherwise)."""
+        count = self.n - env_begin if env_count is None else env_count
+        if frame not in self._RAY_FRAME:
+            raise ValueError("ray_test: frame must be one of %s, got %r" % (sorted(self._RAY_FRAME), frame))
+        rays = torch.as_tensor(rays).to(device=self.device, dtype=torch.float32).contiguous()
+        if rays.ndim not in (2, 3) or rays.shape[-1] != _lib.RAY_WORDS or rays.shape[-2] < 1 or (rays.ndim == 3 and rays.shape[0] != count):
+            raise ValueError("ray_test: rays must have shape [R, %d] (shared) or [%d, R, %d] (one set per env of the call) with R >= 1, got %s"
+                             % (_lib.RAY_WORDS, count, _lib.RAY_WORDS, tuple(rays.shape)))
+        if rays.data_ptr() % 16:
+            rays = rays.clone()                # (a view into a larger tensor: the kernel loads aligned pairs of words)
+        R = rays.shape[-2]
+        shape = (count, R, _lib.RAY_HIT_WORDS)
+        if out is None:
+            out = torch.empty(shape, device=self.device)
+        elif not (torch.is_tensor(out) and out.dtype == torch.float32 and tuple(out.shape) == shape and self._here(out) and out.is_contiguous()):
+            raise ValueError("ray_test: out must be a contiguous float32 tensor of shape %s on %s" % (shape, self.device))
+        flags = self._RAY_FRAME[frame] | (_lib.RAY_SHARED if rays.ndim == 2 else 0) | (_lib.RAY_IGNORE_ROBOT if ignore_robot else 0)
+        self._rays_keep = rays                 # (a converted copy lives until the next call: the launch is asynchronous)
+        with torch.cuda.device(self.device):
+            self._chk(self.L.pih_ray_test(self.h, out.data_ptr(), rays.data_ptr(), int(R), int(env_begin), int(count), flags, self._stream()), "pih_ray_test")
+        return out
+
+    def ray_fan(self, origin, axis, half_angle_deg, rings, per_ring, length):
+        """float32 [1 + rings * per_ring, 6] device tensor: a cone of rays from `origin` about `axis` (module function ray_fan), for
+        ray_test -- with frame="ee" a proximity sensor that rides on the hand.  Built on the device, no host round trip."""
+        return ray_fan(origin, axis, half_angle_deg, rings, per_ring, length, device=self.device)
 
     def _here(self, t):
         """is the tensor on this handle's device? (a handle made with device="cuda" has no index)"""
