@@ -1,12 +1,11 @@
-// pih_fly.hip -- the kernels of the random-fly task: step, reset, state layout, and pih_fly_render_kernel, the float4 image of one host
-// camera (the other formats and cameras: pih_fly_image.hip, pih_lit.hip; the reason they are apart is stated there).  gfx950 only.  The C ABI (pih_hip.hip) reaches them through the launch functions at the end (pih_launch.h), which own the
-// choice of instantiation, the grid, the dynamic LDS and whether the fused grid fits the chip.
+// pih_fly.hip -- the kernels of the random-fly task: step, reset, state layout (its cameras: pih_fly_image.hip, pih_lit.hip).  gfx950 only.
+// The C ABI (pih_hip.hip) reaches them through the launch functions at the end (pih_launch.h), which own the choice of instantiation, the
+// grid, the dynamic LDS and whether the fused grid fits the chip.
 #include <hip/hip_runtime.h>
 #include <cstring>
 #include <type_traits>
 #include "pih_device.h"      // (QuadDpp of pih_ikq.h, the mailbox, the debug stamps of pih_wave.h)
 #include "pih_fly.h"
-#include "pih_fly_render.h"
 #include "pih_launch.h"
 
 using namespace pih;
@@ -154,23 +153,6 @@ __global__ void pih_fly_init_offsets_kernel(float* __restrict__ state, const flo
   for (int k = 0; k < 3; k++) state[(size_t)(PIH_F_OFFSET + k) * n + e] = offsets ? offsets[3 * e + k] : 0.f;
 }
 
-// free camera of the random-fly task (pih_fly_render.h): grid = (strips, envs), 256 threads (4 waves); out float[count, H, W, 4] = depth,
-// r, g, b.  state is structure-of-arrays: the 13 words the scene needs are wave-uniform (scalar) loads (load_fly_pose).  One host camera,
-// validated by pih_render_cam: no camera test here (pih_fly_image_kernel has it); the tile walk is render_strip.
-__global__ void __launch_bounds__(RENDER_THREADS) pih_fly_render_kernel(const float* __restrict__ state, float* __restrict__ out, fly::FlyCam cam,
-                                                                        int n, int object, int env_begin, int W, int H, int rows_per_strip, int flags) {
-  using namespace fly;
-  __shared__ FlyScene sc;
-  const int tid = threadIdx.x, e = blockIdx.y, env = env_begin + e;
-  const int r0 = blockIdx.x * rows_per_strip, r1 = min(H, r0 + rows_per_strip);
-  if (tid < 16) scene_setup_poses(sc, load_fly_pose(state, env, n), cam, object, flags, tid);
-  __syncthreads();
-  scene_setup_bounds(sc, object, tid);
-  __syncthreads();
-  render_strip<unsigned>(sc, FlyGrid(sc, W, H), reinterpret_cast<float4*>(out), (size_t)e * H, W, r0, r1, tid,
-                         [&](unsigned prims, real xc, real yc) { return to_float4(shade(sc, prims, xc, yc, flags)); });
-}
-
 // ------------------------------------------------------------------------------------------------ launches (pih_launch.h)
 // The random-fly step launch of n envs in a layout (quad: one env per quad of lanes), fused or not: the instantiation of pih_fly_step_kernel,
 // the grid (G controller workgroups in front of the step workgroups when fused), the dynamic LDS of every workgroup, and how many of them a
@@ -221,9 +203,5 @@ void fly_get_words_launch(hipStream_t stream, const float* soa, float* aos, int 
 }
 void fly_set_state_launch(hipStream_t stream, const float* aos, float* soa, int n) {
   hipLaunchKernelGGL(pih_aos_to_soa_kernel, dim3((n * PIH_FLY_STATE_WORDS + 255) / 256), dim3(256), 0, stream, aos, soa, n, PIH_FLY_STATE_WORDS);
-}
-void fly_render_launch(dim3 grid, hipStream_t stream, const float* state, float* out, const fly::FlyCam& cam,
-                       int n, int object, int env_begin, int W, int H, int rows_per_strip, int flags) {
-  hipLaunchKernelGGL(pih_fly_render_kernel, grid, dim3(RENDER_THREADS), 0, stream, state, out, cam, n, object, env_begin, W, H, rows_per_strip, flags);
 }
 }  // namespace pih

@@ -1,11 +1,11 @@
-// pih_fly_image.hip -- the free camera of the random-fly task (pih_fly_render.h) with the options pih_fly_render_kernel of pih_fly.hip
-// does not have; that kernel stays as it is (the float4 image of one host camera).  A translation unit of its own: with these kernels in
-// its translation unit the compiler scheduled pih_fly_render_kernel differently (same instructions, another order), and tools/isa_fingerprint.py
-// is to show every older kernel unchanged.
+// pih_fly_image.hip -- the free camera of the random-fly task (pih_fly_render.h; pih_render_cam): every output format, one host camera
+// or per-env cameras.  A translation unit of its own beside pih_fly.hip: the fly step kernels' code stays what tools/isa_fingerprint.py
+// shows for it whatever changes here.
 //   FMT       0: float4 (depth, r, g, b) | PIH_RENDER_OUT_RGBA8: one 32-bit word (r, g, b, seg) | PIH_RENDER_OUT_DEPTH: one float
 //   cam_dev   != nullptr (PIH_RENDER_CAM_DEVICE): float[count, PIH_CAM_WORDS], row blockIdx.y is this workgroup's camera -- 13 more
-//             wave-uniform loads, like the state words; nullptr: `cam`, by value
-// Mapping as pih_fly_render_kernel: grid = (strips, envs), 256 threads (4 waves).  The kernel is two calls of pih_fly_render.h:
+//             wave-uniform loads, like the state words; nullptr: `cam`, by value, which has passed pih_render_cam's test (the kernel's
+//             own test of it costs nothing measurable: profiles/camera_refactor_bench.txt, profiles/scene_share_bench.txt)
+// Mapping: grid = (strips, envs), 256 threads (4 waves).  The kernel is two calls of pih_fly_render.h:
 // fly::camera_setup (pose and camera row, camera_or_preset, the scene's two phases in LDS; with fly::NoLight) and fly::render_image (the
 // tile walk render_strip in the format FMT, one pixel per lane: a wave instruction stores 256 contiguous bytes of an image row in the two
 // packed formats, 1 KB in float4); pih_lit_fly_kernel (pih_lit.hip) is the same two calls with the light hooked in.

@@ -16,8 +16,8 @@
 // PIH_RENDER_CAM_EE: eye, target and up are given in the ee_link frame of the env's UR5 (chain_ee<Ur5Chain>) -- an eye-in-hand camera.
 // Output formats: float4 (depth, r, g, b) as above; PIH_RENDER_OUT_RGBA8 = bytes (r, g, b, seg), seg = the hit's kind (link 0 .. 5,
 // PIH_SEG_OBJECT, PIH_SEG_TABLE, PIH_SEG_NONE); PIH_RENDER_OUT_DEPTH = the depth value alone.  PIH_RENDER_CAM_DEVICE: one camera per env,
-// read by the kernel, tested by the kernel (cam_degenerate): a degenerate one gives its env the background.  Kernels: pih_fly_render_kernel
-// (pih_fly.hip; float4, one host camera) and pih_fly_image_kernel (pih_fly_image.hip; everything else).
+// read by the kernel, tested by the kernel (cam_degenerate): a degenerate one gives its env the background.  Kernel: pih_fly_image_kernel
+// (pih_fly_image.hip), one instance per output format, for one host camera and for per-env cameras alike.
 //
 // Mapping (as pih_render.h): one 256-thread workgroup per (env, strip of rows), the scene once per workgroup in LDS; each WAVE walks
 // 16-row x 64-column tiles; lane i < FLY_NPRIM tests the conservative screen bound of primitive i (camera coordinates; a capsule's bound
@@ -25,8 +25,16 @@
 // tile, the ballot is the tile's primitive list, one tile row is one coalesced 1 KB store.
 // Everything here is PIH_HD on `real`: the host build of tests/emul compiles the same per-scene and per-pixel code in fp64 and fp32.
 //
+// This scene's primitive list -- its order, which array holds which primitive, its radii, its normals, its bounding spheres -- is spelled
+// out once for the cameras, here: nearest_hit (the walk), kind_normal, prim_ball.  The shaded camera (shade_kind) and
+// the lit camera (lit::lit_kind) are built on them; pih_view.h holds the same three for the peg-in-hole scene.  Two walks remain beside
+// it: the shadow ray of pih_lit.h (an any-hit walk with a light-space cull) and the ray tests of pih_rays.h, which keep their own copy
+// (DESIGN.md 6.5 says why).  The camera and ray kernels are held
+// to their outputs' bits by tests/test_gpu_scene_bits.py and to their times by a measurement against the build before
+// (profiles/scene_share_bench.txt); tools/isa_fingerprint.py holds the step kernels.
+//
 // This header is also the home of what ALL camera kernels share (the wrist camera of pih_render.h, this camera, pih_view.h, pih_lit.h), each
-// piece once: FlyGrid (pixel grid), camera_or_preset, load_row, load_fly_pose, Pixels / NoLight (with lit::LitPixels / lit::LightHook)
+// piece once: CameraRay / camera_ray / depth_value (a pixel's ray and its depth-buffer value), Ball, FlyGrid (pixel grid), camera_or_preset, load_row, load_fly_pose, Pixels / NoLight (with lit::LitPixels / lit::LightHook)
 // -- these also in the host build -- and, device only, render_strip (THE tile walk), render_image (the walk in an output format),
 // camera_setup (this task's scene set-up; view::camera_setup is the peg-in-hole one) and dispatch_fmt (format -> kernel instance).
 #pragma once
@@ -146,13 +154,41 @@ PIH_HD bool prim_on_tile(const FlyScene& sc, int i, real tu0, real tu1, real tv0
 // the mask with every primitive of the object on (what a tile without culling sees)
 PIH_HD unsigned all_prims(int object) { return (1u << (RCAP + R_NSPH[object])) - 1u; }
 
-// one pixel: xc, yc = camera-plane coordinates of the pixel centre (already multiplied by tx / ty); prims = bit i set if primitive i
-// may cover the pixel (wave-uniform); kind = what the ray hit: link 0 .. RCAP - 1, KIND_OBJECT, KIND_TABLE or KIND_NONE
-PIH_HD real4 shade_kind(const FlyScene& sc, unsigned prims, real xc, real yc, int flags, int& kind_out) {
-  const V3 eye = ld3(sc.eye);
-  const real inv = rsqrt_((real)1 + xc * xc + yc * yc);      // = d . f
-  const V3 d = inv * (ld3(sc.f) + xc * ld3(sc.s) + yc * ld3(sc.u));
-  const real tnear = sc.znear / inv, tfar = sc.zfar / inv;   // ray parameters of the clip planes
+// ---- what the per-pixel code of both scenes shares (this scene's and view::ViewScene's; shaded and lit cameras)
+// the ray of a pixel, eye + t d, and the ray parameters of the near and far planes
+struct CameraRay { V3 o, d; real inv, tnear, tfar; };      // inv = d . f
+// the ray through the point (xc, yc) of the camera plane (already multiplied by tx / ty)
+template <class S /* FlyScene, view::ViewScene */> PIH_HD CameraRay camera_ray(const S& sc, real xc, real yc) {
+  CameraRay r;
+  r.o = ld3(sc.eye);
+  r.inv = rsqrt_((real)1 + xc * xc + yc * yc);
+  r.d = r.inv * (ld3(sc.f) + xc * ld3(sc.s) + yc * ld3(sc.u));
+  r.tnear = sc.znear / r.inv; r.tfar = sc.zfar / r.inv;      // ray parameters of the clip planes
+  return r;
+}
+// the depth-buffer value of a hit at ray parameter t (hit = false: nothing was hit)
+template <class S> PIH_HD real depth_value(const S& sc, const CameraRay& ray, real t, bool hit) {
+  real depth = 1;
+  if (hit) {
+    const real z = t * ray.inv;
+    depth = sc.zfar * (z - sc.znear) / (z * (sc.zfar - sc.znear));
+  }
+  return depth;
+}
+// the sphere that holds a primitive (centre, radius), grown by the caller's margin `pad` (LIT_CULL_SLACK for the light-space cull of
+// pih_lit.h).  The margin is the last term of the one sum 0.5 |b - a| + r + pad: under -ffast-math a margin added to the finished radius
+// is another sum, which matters wherever a radius enters a hit's bits
+struct Ball { V3 c; real r; };
+PIH_HD Ball capsule_ball(V3 a, V3 b, real r, real pad) { Ball s; s.c = (real)0.5 * (a + b); s.r = (real)0.5 * norm(b - a) + r + pad; return s; }
+PIH_HD Ball sphere_ball(V3 c, real r, real pad) { Ball s; s.c = c; s.r = r + pad; return s; }
+
+// ---- THE walk of this scene: the nearest hit of a pixel's ray among the table and the primitives of `prims` (bit i: primitive i;
+// wave-uniform), in the order table, capsules, object spheres; a later primitive takes the ray only if it is nearer; a hit outside
+// tnear .. tfar is dropped.  t = ray parameter (PIH_BIG: none), kind = link 0 .. RCAP - 1, KIND_OBJECT (sphere `which`), KIND_TABLE or KIND_NONE
+struct FlyHit { real t; int kind, which; };
+PIH_HD FlyHit nearest_hit(const FlyScene& sc, unsigned prims, const CameraRay& ray) {
+  const V3 eye = ray.o, d = ray.d;
+  const real tnear = ray.tnear, tfar = ray.tfar;
   real best = PIH_BIG;
   int kind = KIND_NONE, which = 0;
   if (absr(d.z) > (real)1e-30) {
@@ -171,31 +207,36 @@ PIH_HD real4 shade_kind(const FlyScene& sc, unsigned prims, real xc, real yc, in
     const real t = ray_sphere(eye - ld3(sc.sph[i]), d, sc.sphr[i]);
     if (t < best && t >= tnear && t <= tfar) { best = t; kind = KIND_OBJECT; which = i; }
   }
-  real depth = 1;
-  if (kind != KIND_NONE) {
-    const real z = best * inv;
-    depth = sc.zfar * (z - sc.znear) / (z * (sc.zfar - sc.znear));
-  }
+  FlyHit h; h.t = best; h.kind = kind; h.which = which;
+  return h;
+}
+// outward unit normal at the point ph of a hit: radial on capsules and spheres, +z on the table
+PIH_HD V3 kind_normal(const FlyScene& sc, const FlyHit& h, V3 ph) {
+  V3 n = mk(0, 0, 1);
+  if (h.kind < RCAP) n = capsule_normal(ph, ld3(sc.cap[h.kind][0]), ld3(sc.cap[h.kind][1]));
+  else if (h.kind == KIND_OBJECT) n = capsule_normal(ph, ld3(sc.sph[h.which]), ld3(sc.sph[h.which]));      // (radial: a sphere is a capsule of length 0)
+  return n;
+}
+// the sphere that holds primitive i < FLY_NPRIM
+PIH_HD Ball prim_ball(const FlyScene& sc, int i, real pad) {
+  if (i < RCAP) return capsule_ball(ld3(sc.cap[i][0]), ld3(sc.cap[i][1]), sc.capr[i], pad);
+  return sphere_ball(ld3(sc.sph[i - RCAP]), sc.sphr[i - RCAP], pad);
+}
+
+// one pixel: xc, yc = camera-plane coordinates of the pixel centre (already multiplied by tx / ty); prims = bit i set if primitive i
+// may cover the pixel (wave-uniform); kind_out = what the ray hit
+PIH_HD real4 shade_kind(const FlyScene& sc, unsigned prims, real xc, real yc, int flags, int& kind_out) {
+  const CameraRay ray = camera_ray(sc, xc, yc);
+  const FlyHit h = nearest_hit(sc, prims, ray);
   real lit = 1;
-  if ((flags & PIH_RENDER_SHADED) && kind != KIND_NONE) {
-    // surface normal at the hit point, Lambert term against the fixed light
-    const V3 ph = eye + best * d;
-    V3 n = mk(0, 0, 1);
-    if (kind < RCAP) {
-      const V3 a = ld3(sc.cap[kind][0]), ba = ld3(sc.cap[kind][1]) - a;
-      real q = dot(ph - a, ba) / max_(dot(ba, ba), (real)1e-20);
-      q = q < 0 ? (real)0 : (q > 1 ? (real)1 : q);
-      const V3 r = ph - (a + q * ba);
-      n = ((real)1 / max_(norm(r), (real)1e-12)) * r;
-    } else if (kind == KIND_OBJECT) {
-      const V3 r = ph - ld3(sc.sph[which]);
-      n = ((real)1 / max_(norm(r), (real)1e-12)) * r;
-    }
+  if ((flags & PIH_RENDER_SHADED) && h.kind != KIND_NONE) {
+    // Lambert term against the fixed light
+    const V3 n = kind_normal(sc, h, ray.o + h.t * ray.d);
     const real ndl = n.x * PIH_LIGHT_X + n.y * PIH_LIGHT_Y + n.z * PIH_LIGHT_Z;
     lit = PIH_LIGHT_AMBIENT + PIH_LIGHT_DIFFUSE * max_(ndl, (real)0);
   }
-  real4 o; o.x = depth; o.y = sc.rgb[kind][0] * lit; o.z = sc.rgb[kind][1] * lit; o.w = sc.rgb[kind][2] * lit;
-  kind_out = kind;
+  real4 o; o.x = depth_value(sc, ray, h.t, h.kind != KIND_NONE); o.y = sc.rgb[h.kind][0] * lit; o.z = sc.rgb[h.kind][1] * lit; o.w = sc.rgb[h.kind][2] * lit;
+  kind_out = h.kind;
   return o;
 }
 PIH_HD real4 shade(const FlyScene& sc, unsigned prims, real xc, real yc, int flags) {
@@ -315,7 +356,7 @@ struct NoLight {
 };
 
 #ifndef PIH_PLATFORM_DEFINED      // ---------------------------------------------------------------- device only: the kernels' shared pieces
-// THE tile walk of the camera kernels (pih_lit_view_kernel alone keeps a copy: pih_lit.hip says why).  The workgroup renders rows r0 .. r1 - 1 of its env's image (whose row 0 is row `row0` of out, W values a row: the index stays in size_t): each WAVE
+// THE tile walk of the camera kernels.  The workgroup renders rows r0 .. r1 - 1 of its env's image (whose row 0 is row `row0` of out, W values a row: the index stays in size_t): each WAVE
 // walks 16-row x 64-column tiles; lane i tests primitive i against the tile (prim_on_tile of the scene's namespace), the ballot is the
 // tile's primitive list (MASK: unsigned for the scenes of <= 32 primitives, unsigned long long for view::ViewScene); then one pixel per
 // lane, pixel(prims, xc, yc) -> the stored value: one tile row is one coalesced store of 64 values.

@@ -456,10 +456,7 @@ int pih_render_cam(pih_handle* h, float* out_dev, const float* cam_ptr, int widt
   const int fmt = flags & RENDER_FMT;
   const bool cam_on_device = (flags & PIH_RENDER_CAM_DEVICE) != 0;
   int rows; const int strips = render_strips(height, env_count, &rows);
-  if (fmt || cam_on_device)
-    fly_image_launch(fmt, dim3(strips, env_count), (hipStream_t)stream, h->state, out_dev, cam, cam_on_device ? cam_ptr : nullptr, h->cfg.n_envs, h->P.object, env_begin, width, height, rows, flags);
-  else      // the float4 image of one host camera: the kernel it has always been
-    fly_render_launch(dim3(strips, env_count), (hipStream_t)stream, h->state, out_dev, cam, h->cfg.n_envs, h->P.object, env_begin, width, height, rows, flags);
+  fly_image_launch(fmt, dim3(strips, env_count), (hipStream_t)stream, h->state, out_dev, cam, cam_on_device ? cam_ptr : nullptr, h->cfg.n_envs, h->P.object, env_begin, width, height, rows, flags);
   HIPCHK(h, hipGetLastError());
   return 0;
 }

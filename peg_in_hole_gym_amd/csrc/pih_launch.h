@@ -32,9 +32,7 @@ void ik_launch(bool ur5, hipStream_t stream, const Params& P, int n, const float
 void render_launch(dim3 grid, hipStream_t stream, const float* state, float* out, int env_begin, int W, int H, int rows_per_strip, int flags);
 void labels_launch(hipStream_t stream, const float* state, float* out, float* meta, int env_begin, int env_count, int S);
 
-// ---- pih_fly.hip: the random-fly task's step, reset and state-layout kernels, and the float4 image of one host camera
-void fly_render_launch(dim3 grid, hipStream_t stream, const float* state, float* out, const fly::FlyCam& cam,
-                       int n, int object, int env_begin, int W, int H, int rows_per_strip, int flags);
+// ---- pih_fly.hip: the random-fly task's step, reset and state-layout kernels
 size_t fly_mail_words(int n);                 // floats of the controller mailbox of n envs
 bool fly_fused_fits(int n, bool quad, int cus);      // are ALL workgroups of the fused launch resident at once on `cus` compute units?
 hipError_t fly_step_prepare(bool quad);       // the dynamic-LDS limit of the layout's step kernels, fused and not (once per handle)
@@ -44,7 +42,7 @@ void fly_reset_launch(hipStream_t stream, const Params& P, float* state, const u
 void fly_get_words_launch(hipStream_t stream, const float* soa, float* aos, int n, int word0, int nwords);      // words [word0, word0 + nwords) env-major
 void fly_set_state_launch(hipStream_t stream, const float* aos, float* soa, int n);
 
-// ---- pih_fly_image.hip: the kernels of the packed output formats and of the per-env cameras in device memory
+// ---- pih_fly_image.hip: the free camera of the random-fly task, every output format, one host camera or per-env cameras in device memory
 void fly_image_launch(int fmt, dim3 grid, hipStream_t stream, const float* state, void* out, const fly::FlyCam& cam, const float* cam_dev,
                       int n, int object, int env_begin, int W, int H, int rows_per_strip, int flags);
 // ---- pih_view.hip: the free camera of the peg-in-hole task

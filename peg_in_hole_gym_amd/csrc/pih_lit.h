@@ -2,11 +2,10 @@
 // formats of pih_fly_render.h (random-fly) and pih_view.h (peg-in-hole) under a caller-given light, with a specular term and cast shadows.
 // The model is stated once, in include/pih_render_light.h; lit_rgb and the two *_shadowed functions below restate it.
 //
-// The nearest-hit and normal code of shade_kind / shade_hit stands here a second time (trace_kind, trace_hit, kind_normal, hit_normal):
-// with those two functions split into trace + shade parts the compiler scheduled pih_view_kernel<0>, pih_fly_image_kernel<0> and
-// pih_fly_render_kernel differently (the latter two also one and two instructions longer), and tools/isa_fingerprint.py is to show every
-// older kernel unchanged.  The copies are bound to the originals by the tests: with specular 0 and shadow factor 1 a lit image has the
-// depth channel of the shaded image bit for bit (tests/test_gpu_render_lit.py).
+// The primary ray is the unlit cameras': the scene's walk (fly::nearest_hit, view::nearest_hit with fly::CameraRay), its normal
+// (fly::kind_normal, view::hit_normal), fly::depth_value and, for the depth-only format, the scene's own pixel_depth.  What is here is the
+// light: its test and set-up, the light-space table, the shadow ray (an ANY-hit walk with a cull of its own, so not the scenes' nearest-hit
+// walk) and the colour model.
 //
 // The shadow ray is the hot path, and the screen-space tile lists are no use for it: an occluder may be anywhere, behind the eye included.
 // So each workgroup builds a LIGHT-SPACE table once (light_table_*): per primitive the centre of its bounding sphere projected on two axes
@@ -67,7 +66,7 @@ PIH_HHD int light_degenerate(const LightWords& lw) {
 template <int N> struct LitEnv {
   real l[3], ex[3], ey[3];                  // unit direction towards the light; two unit axes perpendicular to it and to each other
   real colour[3], ambient, diffuse, specular, shininess, shadow;
-  real occ[N][4];                           // per primitive: bounding-sphere centre . ex, . ey, radius + LIT_CULL_SLACK, centre . l
+  real occ[N][4];                           // per primitive: bounding-sphere centre . ex, . ey, radius (with LIT_CULL_SLACK), centre . l
   unsigned long long mask;                  // the occluders to walk: bit i = primitive i exists
   int bad;                                  // light_degenerate's code (the words above are then PIH_LIGHT_DEFAULT's)
 };
@@ -88,9 +87,12 @@ template <int N> PIH_HD void light_setup(LitEnv<N>& le, const LightWords& lw, un
   le.shininess = w[LW_SHININESS]; le.shadow = w[LW_SHADOW];
   le.mask = mask; le.bad = code;
 }
-// table entry i: the sphere (c, r) holds primitive i
-template <int N> PIH_HD void occluder_entry(LitEnv<N>& le, int i, V3 c, real r) {
-  le.occ[i][0] = dot(c, ld3(le.ex)); le.occ[i][1] = dot(c, ld3(le.ey)); le.occ[i][2] = r + LIT_CULL_SLACK; le.occ[i][3] = dot(c, ld3(le.l));
+// after scene_setup_poses and light_setup, and a barrier (threads 0 .. N - 1): the light-space entry of primitive `tid` of the scene, from
+// the sphere that holds it (prim_ball of the scene's header) grown by LIT_CULL_SLACK
+template <class S, int N> PIH_HD void light_table(const S& sc, LitEnv<N>& le, int tid) {
+  if (tid >= N) return;
+  const fly::Ball b = prim_ball(sc, tid, LIT_CULL_SLACK);
+  le.occ[tid][0] = dot(b.c, ld3(le.ex)); le.occ[tid][1] = dot(b.c, ld3(le.ey)); le.occ[tid][2] = b.r; le.occ[tid][3] = dot(b.c, ld3(le.l));
 }
 // the origin of a shadow ray in light space, and the test a primitive has to pass before it is intersected
 struct LightPoint { real x, y, depth; };
@@ -121,16 +123,6 @@ using fly::FLY_NPRIM;
 using fly::RCAP;
 typedef LitEnv<FLY_NPRIM> FlyLit;
 
-// after scene_setup_poses and light_setup, and a barrier (threads 0 .. FLY_NPRIM - 1): the light-space entry of primitive `tid`
-PIH_HD void light_table(const FlyScene& sc, FlyLit& le, int tid) {
-  if (tid >= FLY_NPRIM) return;
-  if (tid < RCAP) {
-    const V3 a = ld3(sc.cap[tid][0]), b = ld3(sc.cap[tid][1]);
-    occluder_entry(le, tid, (real)0.5 * (a + b), sc.capr[tid] + (real)0.5 * norm(b - a));
-  } else {
-    occluder_entry(le, tid, ld3(sc.sph[tid - RCAP]), sc.sphr[tid - RCAP]);
-  }
-}
 // does the ray from o towards the light hit an occluder?  cull: use the light-space table (false: the host build's check of it)
 PIH_HD bool shadowed(const FlyScene& sc, const FlyLit& le, V3 o, bool cull) {
   const V3 l = ld3(le.l);
@@ -147,65 +139,21 @@ PIH_HD bool shadowed(const FlyScene& sc, const FlyLit& le, V3 o, bool cull) {
   return sh;
 }
 
-// the nearest hit of the ray through a pixel: fly::shade_kind's (see the header comment).  d = unit ray direction, inv = d . f, best = ray
-// parameter, kind = link 0 .. RCAP - 1, KIND_OBJECT (sphere `which`), KIND_TABLE or KIND_NONE
-struct FlyHit { V3 d; real inv, best; int kind, which; };
-PIH_HD FlyHit trace_kind(const FlyScene& sc, unsigned prims, real xc, real yc) {
-  using namespace fly;
-  const V3 eye = ld3(sc.eye);
-  const real inv = rsqrt_((real)1 + xc * xc + yc * yc);      // = d . f
-  const V3 d = inv * (ld3(sc.f) + xc * ld3(sc.s) + yc * ld3(sc.u));
-  const real tnear = sc.znear / inv, tfar = sc.zfar / inv;   // ray parameters of the clip planes
-  real best = PIH_BIG;
-  int kind = KIND_NONE, which = 0;
-  if (absr(d.z) > (real)1e-30) {
-    const real t = ((real)PIH_TABLE_Z - eye.z) / d.z;
-    if (t >= tnear && t <= tfar) { best = t; kind = KIND_TABLE; }
-  }
-  unsigned caps = prims & ((1u << RCAP) - 1u);
-  while (caps) {
-    const int L = __builtin_ctz(caps); caps &= caps - 1u;
-    const real t = ray_capsule(eye, d, ld3(sc.cap[L][0]), ld3(sc.cap[L][1]), sc.capr[L]);
-    if (t < best && t >= tnear && t <= tfar) { best = t; kind = L; }
-  }
-  unsigned sphs = prims >> RCAP;
-  while (sphs) {
-    const int i = __builtin_ctz(sphs); sphs &= sphs - 1u;
-    const real t = ray_sphere(eye - ld3(sc.sph[i]), d, sc.sphr[i]);
-    if (t < best && t >= tnear && t <= tfar) { best = t; kind = KIND_OBJECT; which = i; }
-  }
-  FlyHit h; h.d = d; h.inv = inv; h.best = best; h.kind = kind; h.which = which;
-  return h;
-}
-PIH_HD real depth_value(const FlyScene& sc, const FlyHit& h) {
-  real depth = 1;
-  if (h.kind != fly::KIND_NONE) {
-    const real z = h.best * h.inv;
-    depth = sc.zfar * (z - sc.znear) / (z * (sc.zfar - sc.znear));
-  }
-  return depth;
-}
-// surface normal at the hit point ph: radial on capsules and spheres, +z on the table
-PIH_HD V3 kind_normal(const FlyScene& sc, const FlyHit& h, V3 ph) {
-  V3 n = mk(0, 0, 1);
-  if (h.kind < RCAP) n = capsule_normal(ph, ld3(sc.cap[h.kind][0]), ld3(sc.cap[h.kind][1]));
-  else if (h.kind == fly::KIND_OBJECT) n = capsule_normal(ph, ld3(sc.sph[h.which]), ld3(sc.sph[h.which]));      // (radial: a sphere is a capsule of length 0)
-  return n;
-}
 // one lit pixel: (depth value, r, g, b); kind_out = what the ray hit
 PIH_HD real4 lit_kind(const FlyScene& sc, const FlyLit& le, unsigned prims, real xc, real yc, bool cull, int& kind_out) {
-  const FlyHit h = trace_kind(sc, prims, xc, yc);
-  real4 o; o.x = depth_value(sc, h); o.y = sc.rgb[h.kind][0]; o.z = sc.rgb[h.kind][1]; o.w = sc.rgb[h.kind][2];
+  const fly::CameraRay ray = fly::camera_ray(sc, xc, yc);
+  const fly::FlyHit h = fly::nearest_hit(sc, prims, ray);
+  real4 o; o.x = fly::depth_value(sc, ray, h.t, h.kind != fly::KIND_NONE); o.y = sc.rgb[h.kind][0]; o.z = sc.rgb[h.kind][1]; o.w = sc.rgb[h.kind][2];
   kind_out = h.kind;
   if (h.kind == fly::KIND_NONE) return o;
-  const V3 ph = ld3(sc.eye) + h.best * h.d, n = kind_normal(sc, h, ph);
+  const V3 ph = ray.o + h.t * ray.d, n = fly::kind_normal(sc, h, ph);
   const real ndl = dot(n, ld3(le.l));
   real s = 1;
   if (le.shadow != 1 && ndl > 0 && shadowed(sc, le, ph + (real)PIH_SHADOW_BIAS * n, cull)) s = le.shadow;
-  lit_rgb(le, sc.rgb[h.kind], n, h.d, ndl, s, o);
+  lit_rgb(le, sc.rgb[h.kind], n, ray.d, ndl, s, o);
   return o;
 }
-// one pixel of each format (`bad`: the env's camera or light is degenerate, wave-uniform)
+// the two coloured formats of one pixel (`bad`: the env's camera or light is degenerate, wave-uniform); the depth-only one is fly::pixel_depth
 PIH_HD real4 pixel_float4(const FlyScene& sc, const FlyLit& le, unsigned prims, real xc, real yc, bool cull, bool bad) {
   int kind;
   return bad ? fly::background() : lit_kind(sc, le, prims, xc, yc, cull, kind);
@@ -215,32 +163,11 @@ PIH_HD unsigned pixel_rgba8(const FlyScene& sc, const FlyLit& le, unsigned prims
   const real4 c = bad ? fly::background() : lit_kind(sc, le, prims, xc, yc, cull, kind);
   return fly::pack_rgba8(c, kind);
 }
-PIH_HD real pixel_depth(const FlyScene& sc, unsigned prims, real xc, real yc, bool bad) {
-  return bad ? (real)1 : depth_value(sc, trace_kind(sc, prims, xc, yc));
-}
 
 // ------------------------------------------------------------------------------------------------ peg-in-hole (the scene of pih_view.h)
 using view::VIEW_NPRIM;
 typedef LitEnv<VIEW_NPRIM> ViewLit;
 
-// after scene_setup_poses and light_setup, and a barrier (threads 0 .. VIEW_NPRIM - 1): the light-space entry of primitive `tid`
-PIH_HD void light_table(const ViewScene& sc, ViewLit& le, int tid) {
-  using namespace view;
-  if (tid >= VIEW_NPRIM) return;
-  if (tid < P_HAND) {
-    const V3 a = ld3(sc.org[tid]), b = ld3(sc.org[tid + 1]);
-    occluder_entry(le, tid, (real)0.5 * (a + b), ARM_R[tid] + (real)0.5 * norm(b - a));
-  } else if (tid < P_BOX) {
-    occluder_entry(le, tid, ld3(sc.hs[tid - P_HAND]), ASPH_R[HAND_SPH0 + tid - P_HAND]);
-  } else if (tid < P_PIPE) {
-    occluder_entry(le, tid, ld3(sc.fc[tid - P_BOX]), norm(ld3(FBOX_H)));
-  } else if (tid < P_TUBE) {
-    const V3 a = ld3(sc.vtx[tid - P_PIPE]), b = ld3(sc.vtx[tid - P_PIPE + 1]);
-    occluder_entry(le, tid, (real)0.5 * (a + b), (real)PIH_PIPE_RADIUS + (real)0.5 * norm(b - a));
-  } else {
-    occluder_entry(le, tid, ld3(HOLE_POS), (real)sqrt(PIH_HOLE_HALFLEN * PIH_HOLE_HALFLEN + PIH_HOLE_ROUT * PIH_HOLE_ROUT));
-  }
-}
 // does the ray from o towards the light hit an occluder?  The arm's and the pipe's capsules go through ONE call of ray_capsule.
 PIH_HD bool shadowed(const ViewScene& sc, const ViewLit& le, V3 o, bool cull) {
   using namespace view;
@@ -269,87 +196,23 @@ PIH_HD bool shadowed(const ViewScene& sc, const ViewLit& le, V3 o, bool cull) {
   return sh;
 }
 
-// the nearest hit of the ray through a pixel: view::shade_hit's (see the header comment).  col = the hit's flat colour, hit = primitive
-// index, HIT_TABLE or HIT_NONE
-struct ViewHit { V3 d; real inv, best, col; int hit; };
-PIH_HD ViewHit trace_hit(const ViewScene& sc, unsigned long long prims, real xc, real yc) {
-  using namespace view;
-  const V3 eye = ld3(sc.eye);
-  const real inv = rsqrt_((real)1 + xc * xc + yc * yc);      // = d . f
-  const V3 d = inv * (ld3(sc.f) + xc * ld3(sc.s) + yc * ld3(sc.u));
-  const real tnear = sc.znear / inv, tfar = sc.zfar / inv;   // ray parameters of the clip planes
-  real best = PIH_BIG, col = PIH_COL_BG;
-  int hit = HIT_NONE;
-  if (absr(d.z) > (real)1e-30) {
-    const real t = ((real)PIH_TABLE_Z - eye.z) / d.z;
-    if (t >= tnear && t <= tfar) { best = t; col = PIH_COL_TABLE; hit = HIT_TABLE; }
-  }
-  unsigned segs = (unsigned)(prims >> P_PIPE) & ((1u << NSEG) - 1u);
-  while (segs) {
-    const int sg = __builtin_ctz(segs); segs &= segs - 1u;
-    const real t = ray_capsule(eye, d, ld3(sc.vtx[sg]), ld3(sc.vtx[sg + 1]), PIH_PIPE_RADIUS);
-    if (t < best && t >= tnear && t <= tfar) { best = t; col = PIH_COL_PIPE; hit = P_PIPE + sg; }
-  }
-  if (prims & (1ull << P_TUBE)) {
-    const real t = ray_tube(eye, d);
-    if (t < best && t >= tnear && t <= tfar) { best = t; col = PIH_COL_PIPE; hit = P_TUBE; }
-  }
-  for (int f = 0; f < 2; f++)
-    if (prims & (1ull << (P_BOX + f))) {
-      const real t = ray_box(eye, d, ldm(sc.fR[f]), ld3(sc.fc[f]), ld3(FBOX_H));
-      if (t < best && t >= tnear && t <= tfar) { best = t; col = PIH_COL_FINGER; hit = P_BOX + f; }
-    }
-  unsigned hand = (unsigned)(prims >> P_HAND) & ((1u << VHAND) - 1u);
-  while (hand) {
-    const int i = __builtin_ctz(hand); hand &= hand - 1u;
-    const real t = ray_sphere(eye - ld3(sc.hs[i]), d, ASPH_R[HAND_SPH0 + i]);
-    if (t < best && t >= tnear && t <= tfar) { best = t; col = PIH_COL_FINGER; hit = P_HAND + i; }
-  }
-  // the arm comes last, in the order ARM_ORDER; while `hit` is a link, a later link needs the margin (pih_view.h)
-  unsigned ord = 0;
-  for (int k = 0; k < VARM; k++) ord |= (((unsigned)prims >> ((ARM_ORDER_NIBBLES >> (4 * k)) & 7u)) & 1u) << k;
-  while (ord) {
-    const int L = (int)((ARM_ORDER_NIBBLES >> (4 * __builtin_ctz(ord))) & 7u); ord &= ord - 1u;
-    const real t = ray_capsule(eye, d, ld3(sc.org[L]), ld3(sc.org[L + 1]), ARM_R[L]);
-    const real lim = hit < P_HAND ? best * ((real)1 - VIEW_ARM_TIE) : best;
-    if (t < lim && t >= tnear && t <= tfar) { best = t; col = VIEW_COL_ARM; hit = L; }
-  }
-  ViewHit h; h.d = d; h.inv = inv; h.best = best; h.col = col; h.hit = hit;
-  return h;
-}
-PIH_HD real depth_value(const ViewScene& sc, const ViewHit& h) {
-  real depth = 1;
-  if (h.hit != view::HIT_NONE) {
-    const real z = h.best * h.inv;
-    depth = sc.zfar * (z - sc.znear) / (z * (sc.zfar - sc.znear));
-  }
-  return depth;
-}
-// surface normal at the hit point ph of `hit` (the helpers of pih_render.h; radial on the hand's spheres; +z on the table)
-PIH_HD V3 hit_normal(const ViewScene& sc, int hit, V3 ph) {
-  using namespace view;
-  V3 n = mk(0, 0, 1);
-  if (hit < P_HAND) n = capsule_normal(ph, ld3(sc.org[hit]), ld3(sc.org[hit + 1]));
-  else if (hit < P_BOX) n = capsule_normal(ph, ld3(sc.hs[hit - P_HAND]), ld3(sc.hs[hit - P_HAND]));
-  else if (hit < P_PIPE) n = box_normal(ph, ldm(sc.fR[hit - P_BOX]), ld3(sc.fc[hit - P_BOX]));
-  else if (hit < P_TUBE) n = capsule_normal(ph, ld3(sc.vtx[hit - P_PIPE]), ld3(sc.vtx[hit - P_PIPE + 1]));
-  else if (hit == P_TUBE) n = tube_normal(ph);
-  return n;
-}
 // one lit pixel: (depth value, r, g, b); hit_out = what the ray hit
 PIH_HD real4 lit_hit(const ViewScene& sc, const ViewLit& le, unsigned long long prims, real xc, real yc, bool cull, int& hit_out) {
-  const ViewHit h = trace_hit(sc, prims, xc, yc);
-  real4 o; o.x = depth_value(sc, h); o.y = o.z = o.w = h.col;
+  const fly::CameraRay ray = fly::camera_ray(sc, xc, yc);
+  const view::ViewHit h = view::nearest_hit(sc, prims, ray);
+  const real col = view::hit_colour(h.hit);
+  real4 o; o.x = fly::depth_value(sc, ray, h.t, h.hit != view::HIT_NONE); o.y = o.z = o.w = col;
   hit_out = h.hit;
   if (h.hit == view::HIT_NONE) return o;
-  const V3 ph = ld3(sc.eye) + h.best * h.d, n = hit_normal(sc, h.hit, ph);
+  const V3 ph = ray.o + h.t * ray.d, n = view::hit_normal(sc, h.hit, ph);
   const real ndl = dot(n, ld3(le.l));
   real s = 1;
   if (le.shadow != 1 && ndl > 0 && shadowed(sc, le, ph + (real)PIH_SHADOW_BIAS * n, cull)) s = le.shadow;
-  const real base[3] = {h.col, h.col, h.col};
-  lit_rgb(le, base, n, h.d, ndl, s, o);
+  const real base[3] = {col, col, col};
+  lit_rgb(le, base, n, ray.d, ndl, s, o);
   return o;
 }
+// (the depth-only format is view::pixel_depth)
 PIH_HD real4 pixel_float4(const ViewScene& sc, const ViewLit& le, unsigned long long prims, real xc, real yc, bool cull, bool bad) {
   int hit;
   return bad ? fly::background() : lit_hit(sc, le, prims, xc, yc, cull, hit);
@@ -359,16 +222,13 @@ PIH_HD unsigned pixel_rgba8(const ViewScene& sc, const ViewLit& le, unsigned lon
   const real4 c = bad ? fly::background() : lit_hit(sc, le, prims, xc, yc, cull, hit);
   return fly::pack_byte(c.y) | (fly::pack_byte(c.z) << 8) | (fly::pack_byte(c.w) << 16) | (view::seg_of_hit(hit) << 24);
 }
-PIH_HD real pixel_depth(const ViewScene& sc, unsigned long long prims, real xc, real yc, bool bad) {
-  return bad ? (real)1 : depth_value(sc, trace_hit(sc, prims, xc, yc));
-}
 
 // ------------------------------------------------------------------------------------------------ both tasks
 // the three formats of one lit pixel, as fly::render_image takes them (`cull`: use the light-space table)
 template <class S, class L, class MASK> struct LitPixels {
   const S& sc; const L& le; bool cull, bad;
   PIH_HD unsigned as_rgba8(MASK prims, real xc, real yc) const { return pixel_rgba8(sc, le, prims, xc, yc, cull, bad); }
-  PIH_HD real as_depth(MASK prims, real xc, real yc) const { return lit::pixel_depth(sc, prims, xc, yc, bad); }      // (not view::pixel_depth)
+  PIH_HD real as_depth(MASK prims, real xc, real yc) const { return pixel_depth(sc, prims, xc, yc, bad); }      // (the light does not enter: the scene's own)
   PIH_HD real4 as_float4(MASK prims, real xc, real yc) const { return pixel_float4(sc, le, prims, xc, yc, cull, bad); }
 };
 // what a lit kernel hooks into its task's camera_setup (fly::NoLight is the unlit kernels'): thread 14 of the workgroup reads the env's row

@@ -1,5 +1,6 @@
-// pih_raycast.h -- the task-independent pieces of the analytic ray casters: ray-vs-sphere / capsule, the conservative screen bound of a
-// sphere, and the light and colour constants both cameras share (the wrist camera of pih_render.h, the free camera of pih_fly_render.h).
+// pih_raycast.h -- the task-independent pieces of the analytic ray casters: ray-vs-sphere / capsule, the radial normal of a capsule, the
+// conservative screen bound of a sphere, and the light and colour constants all cameras share (the wrist camera of pih_render.h, the free
+// cameras of pih_fly_render.h and pih_view.h).
 #pragma once
 #include "pih_common.h"
 
@@ -35,6 +36,14 @@ PIH_HD real ray_capsule(V3 o, V3 d, V3 a, V3 b, real r) {
   best = t1 < best ? t1 : best;
   best = t2 < best ? t2 : best;
   return best;
+}
+// outward unit normal of the capsule a .. b at the point ph of its surface (a == b: a sphere)
+PIH_HD V3 capsule_normal(V3 ph, V3 a, V3 b) {
+  const V3 ba = b - a;
+  real q = dot(ph - a, ba) / max_(dot(ba, ba), (real)1e-20);
+  q = q < 0 ? (real)0 : (q > 1 ? (real)1 : q);
+  const V3 r = ph - (a + q * ba);
+  return ((real)1 / max_(norm(r), (real)1e-12)) * r;
 }
 // conservative screen-space bound (in tan-angle units: u = x / depth, v = y / depth) of a sphere; false = cannot bound
 // (sphere reaches the eye plane), the caller then keeps the primitive for every strip

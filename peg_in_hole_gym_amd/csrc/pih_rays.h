@@ -25,6 +25,9 @@
 // sphere skips the primitive function (CULL; that part is an optimisation, measured in DESIGN.md 6.7).
 // Rays are incoherent, so there is no tile culling: every lane walks the whole primitive list in the same order (`prims` is wave-uniform),
 // and every scene read is a same-address LDS broadcast.
+// This header keeps its own walks (trace_view, trace_fly), normals and bounding spheres beside the cameras' (view::nearest_hit /
+// fly::nearest_hit, hit_normal / kind_normal, prim_ball): on those the random-fly kernel measured slower and 14 peg-in-hole rays left the
+// recorded bits (DESIGN.md 6.5 has the figures).  A primitive added to a scene has to be added here too.
 // Everything here is PIH_HD on `real`: the host build of tests/emul compiles the same per-ray code in fp64 and fp32.
 #pragma once
 #include "pih_view.h"

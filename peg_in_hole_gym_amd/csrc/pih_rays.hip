@@ -1,5 +1,5 @@
-// pih_rays.hip -- kernels of the batched ray tests (pih_rays.h; pih_ray_test of include/pih_robot.h).  A translation unit of its own, for
-// the reason pih_fly_image.hip states: tools/isa_fingerprint.py is to show every older kernel unchanged.
+// pih_rays.hip -- kernels of the batched ray tests (pih_rays.h; pih_ray_test of include/pih_robot.h).  A translation unit of its own
+// beside the step kernels'; its kernels' records are held to tests/golden/scene_bits.npz by tests/test_gpu_scene_bits.py.
 // Mapping: grid = (ray chunks, envs), 256 threads (4 waves).  The workgroup does the cameras' per-env set-up once, without a camera --
 // peg-in-hole: state record -> LDS, fk_all, the primitives' poses, their bounding spheres (four barriers); random-fly: pose words, the
 // poses, the spheres (two) -- and then one ray per lane, in a loop over its chunk of `chunk` rays (a multiple of 256; the launch function says how it is chosen).

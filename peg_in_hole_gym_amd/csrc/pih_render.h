@@ -75,14 +75,8 @@ PIH_HD real ray_tube(V3 o, V3 d) {
   return best;
 }
 
-// surface normals at a hit point ph, shared by the wrist camera below and the free camera of pih_view.h
-PIH_HD V3 capsule_normal(V3 ph, V3 a, V3 b) {
-  const V3 ba = b - a;
-  real q = dot(ph - a, ba) / max_(dot(ba, ba), (real)1e-20);
-  q = q < 0 ? (real)0 : (q > 1 ? (real)1 : q);
-  const V3 r = ph - (a + q * ba);
-  return ((real)1 / max_(norm(r), (real)1e-12)) * r;
-}
+// surface normals at a hit point ph of the hole tube and of a finger box (capsule_normal: pih_raycast.h), shared by the wrist camera below
+// and the scene of pih_view.h
 PIH_HD V3 tube_normal(V3 ph) {
   const V3 oc = ph - ld3(HOLE_POS);
   const real rr = (real)sqrt(oc.y * oc.y + oc.z * oc.z);
@@ -196,27 +190,9 @@ PIH_HD real4 shade(const Scene& sc, unsigned prims, real xc, real yc, int flags)
     // surface normal at the hit point, Lambert term against the fixed light
     const V3 ph = eye + best * d;
     V3 n = mk(0, 0, 1);
-    // (what capsule_normal, tube_normal and box_normal above compute, which pih_view.h calls.  Written out here as it always was: with the
-    //  calls pih_render_kernel comes out one instruction longer and in another schedule, and tools/isa_fingerprint.py is to show it unchanged)
-    if (kind == 2) {
-      const V3 a = ld3(sc.vtx[which]), ba = ld3(sc.vtx[which + 1]) - a;
-      real q = dot(ph - a, ba) / max_(dot(ba, ba), (real)1e-20);
-      q = q < 0 ? (real)0 : (q > 1 ? (real)1 : q);
-      const V3 r = ph - (a + q * ba);
-      n = ((real)1 / max_(norm(r), (real)1e-12)) * r;
-    } else if (kind == 3) {
-      const V3 oc = ph - ld3(HOLE_POS);
-      const real rr = (real)sqrt(oc.y * oc.y + oc.z * oc.z);
-      if (absr(oc.x) >= PIH_HOLE_HALFLEN - (real)1e-5) n = mk(oc.x > 0 ? (real)1 : (real)-1, 0, 0);
-      else { const real sgn = rr > (real)0.5 * (PIH_HOLE_RIN + PIH_HOLE_ROUT) ? (real)1 : (real)-1; const real k = sgn / max_(rr, (real)1e-12); n = mk(0, oc.y * k, oc.z * k); }
-    } else if (kind == 4) {
-      const M3 R = ldm(sc.fR[which]);
-      const V3 pl = tmul(R, ph - ld3(sc.fc[which])), h = ld3(FBOX_H);
-      const real ax = absr(pl.x) / h.x, ay = absr(pl.y) / h.y, az = absr(pl.z) / h.z;
-      V3 nl = mk(0, 0, 0);
-      if (ax >= ay && ax >= az) nl.x = pl.x > 0 ? (real)1 : (real)-1; else if (ay >= az) nl.y = pl.y > 0 ? (real)1 : (real)-1; else nl.z = pl.z > 0 ? (real)1 : (real)-1;
-      n = mul(R, nl);
-    }
+    if (kind == 2) n = capsule_normal(ph, ld3(sc.vtx[which]), ld3(sc.vtx[which + 1]));
+    else if (kind == 3) n = tube_normal(ph);
+    else if (kind == 4) n = box_normal(ph, ldm(sc.fR[which]), ld3(sc.fc[which]));
     const real ndl = n.x * PIH_LIGHT_X + n.y * PIH_LIGHT_Y + n.z * PIH_LIGHT_Z;
     col = col * (PIH_LIGHT_AMBIENT + PIH_LIGHT_DIFFUSE * max_(ndl, (real)0));
   }

@@ -1,5 +1,5 @@
 // pih_robot.hip -- kernels of the batched robot-model queries (pih_robot.h; the calls of include/pih_robot.h).  A translation unit of its
-// own, for the reason pih_fly_image.hip states: tools/isa_fingerprint.py is to show every older kernel unchanged.
+// own: the step kernels' code stays what tools/isa_fingerprint.py shows for it whatever changes here.
 // Mapping: one problem per lane, one wavefront per workgroup (64 problems), plain scalar code per lane; grid = ceil(n / 64).
 //   STAGED = false   every lane stores its own output rows: a store instruction of the wavefront touches 64 rows, W words apart
 //   STAGED = true    the lanes write their rows to LDS (row stride W | 1: odd, conflict-free), then the wavefront stores the 64 rows --

@@ -186,39 +186,40 @@ PIH_HD unsigned seg_of_hit(int hit) {
   return hit == P_TUBE ? (unsigned)PIH_VIEW_SEG_HOLE : (hit == HIT_TABLE ? (unsigned)PIH_VIEW_SEG_TABLE : (unsigned)PIH_SEG_NONE);
 }
 
-// one pixel: xc, yc = camera-plane coordinates of the pixel centre (already multiplied by tx / ty); prims = bit i set if primitive i
-// may cover the pixel (wave-uniform); hit_out = what the ray hit (primitive index, HIT_TABLE, HIT_NONE)
-PIH_HD real4 shade_hit(const ViewScene& sc, unsigned long long prims, real xc, real yc, int flags, int& hit_out) {
-  const V3 eye = ld3(sc.eye);
-  const real inv = rsqrt_((real)1 + xc * xc + yc * yc);      // = d . f
-  const V3 d = inv * (ld3(sc.f) + xc * ld3(sc.s) + yc * ld3(sc.u));
-  const real tnear = sc.znear / inv, tfar = sc.zfar / inv;   // ray parameters of the clip planes
-  real best = PIH_BIG, col = PIH_COL_BG;
+// ---- THE walk of this scene: the nearest hit of a pixel's ray (fly::CameraRay) among the table and the primitives of `prims` (bit i:
+// primitive i; wave-uniform), in the order table, pipe capsules, hole tube, finger boxes, hand spheres, arm; a later primitive takes the
+// ray only if it is nearer; a hit outside tnear .. tfar is dropped.  t = ray parameter (PIH_BIG: none), hit = primitive index, HIT_TABLE
+// or HIT_NONE
+struct ViewHit { real t; int hit; };
+PIH_HD ViewHit nearest_hit(const ViewScene& sc, unsigned long long prims, const fly::CameraRay& ray) {
+  const V3 eye = ray.o, d = ray.d;
+  const real tnear = ray.tnear, tfar = ray.tfar;
+  real best = PIH_BIG;
   int hit = HIT_NONE;
   if (absr(d.z) > (real)1e-30) {
     const real t = ((real)PIH_TABLE_Z - eye.z) / d.z;
-    if (t >= tnear && t <= tfar) { best = t; col = PIH_COL_TABLE; hit = HIT_TABLE; }
+    if (t >= tnear && t <= tfar) { best = t; hit = HIT_TABLE; }
   }
   unsigned segs = (unsigned)(prims >> P_PIPE) & ((1u << NSEG) - 1u);
   while (segs) {
     const int sg = __builtin_ctz(segs); segs &= segs - 1u;
     const real t = ray_capsule(eye, d, ld3(sc.vtx[sg]), ld3(sc.vtx[sg + 1]), PIH_PIPE_RADIUS);
-    if (t < best && t >= tnear && t <= tfar) { best = t; col = PIH_COL_PIPE; hit = P_PIPE + sg; }
+    if (t < best && t >= tnear && t <= tfar) { best = t; hit = P_PIPE + sg; }
   }
   if (prims & (1ull << P_TUBE)) {
     const real t = ray_tube(eye, d);
-    if (t < best && t >= tnear && t <= tfar) { best = t; col = PIH_COL_PIPE; hit = P_TUBE; }
+    if (t < best && t >= tnear && t <= tfar) { best = t; hit = P_TUBE; }
   }
   for (int f = 0; f < 2; f++)
     if (prims & (1ull << (P_BOX + f))) {
       const real t = ray_box(eye, d, ldm(sc.fR[f]), ld3(sc.fc[f]), ld3(FBOX_H));
-      if (t < best && t >= tnear && t <= tfar) { best = t; col = PIH_COL_FINGER; hit = P_BOX + f; }
+      if (t < best && t >= tnear && t <= tfar) { best = t; hit = P_BOX + f; }
     }
   unsigned hand = (unsigned)(prims >> P_HAND) & ((1u << VHAND) - 1u);
   while (hand) {
     const int i = __builtin_ctz(hand); hand &= hand - 1u;
     const real t = ray_sphere(eye - ld3(sc.hs[i]), d, ASPH_R[HAND_SPH0 + i]);
-    if (t < best && t >= tnear && t <= tfar) { best = t; col = PIH_COL_FINGER; hit = P_HAND + i; }
+    if (t < best && t >= tnear && t <= tfar) { best = t; hit = P_HAND + i; }
   }
   // the arm comes last, its links in the order ARM_ORDER (bit k of `ord`: link ARM_ORDER[k] is on); while `hit` is a link, a later link
   // needs the margin.  (A scalar bit scan like the pipe's: a counted loop is unrolled into seven copies of ray_capsule, 181 VGPRs.)
@@ -228,27 +229,51 @@ PIH_HD real4 shade_hit(const ViewScene& sc, unsigned long long prims, real xc, r
     const int L = (int)((ARM_ORDER_NIBBLES >> (4 * __builtin_ctz(ord))) & 7u); ord &= ord - 1u;
     const real t = ray_capsule(eye, d, ld3(sc.org[L]), ld3(sc.org[L + 1]), ARM_R[L]);
     const real lim = hit < P_HAND ? best * ((real)1 - VIEW_ARM_TIE) : best;
-    if (t < lim && t >= tnear && t <= tfar) { best = t; col = VIEW_COL_ARM; hit = L; }
+    if (t < lim && t >= tnear && t <= tfar) { best = t; hit = L; }
   }
-  real depth = 1;
-  if (hit != HIT_NONE) {
-    const real z = best * inv;
-    depth = sc.zfar * (z - sc.znear) / (z * (sc.zfar - sc.znear));
-  }
-  if ((flags & PIH_RENDER_SHADED) && hit != HIT_NONE) {
-    // surface normal at the hit point (the helpers of pih_render.h; radial on the hand's spheres), Lambert term against the fixed light
-    const V3 ph = eye + best * d;
-    V3 n = mk(0, 0, 1);
-    if (hit < P_HAND) n = capsule_normal(ph, ld3(sc.org[hit]), ld3(sc.org[hit + 1]));
-    else if (hit < P_BOX) n = capsule_normal(ph, ld3(sc.hs[hit - P_HAND]), ld3(sc.hs[hit - P_HAND]));      // (radial: a sphere is a capsule of length 0)
-    else if (hit < P_PIPE) n = box_normal(ph, ldm(sc.fR[hit - P_BOX]), ld3(sc.fc[hit - P_BOX]));
-    else if (hit < P_TUBE) n = capsule_normal(ph, ld3(sc.vtx[hit - P_PIPE]), ld3(sc.vtx[hit - P_PIPE + 1]));
-    else if (hit == P_TUBE) n = tube_normal(ph);
+  ViewHit h; h.t = best; h.hit = hit;
+  return h;
+}
+// the flat colour of what a ray hit
+PIH_HD real hit_colour(int hit) {
+  if (hit < P_HAND) return VIEW_COL_ARM;
+  if (hit < P_PIPE) return PIH_COL_FINGER;
+  if (hit <= P_TUBE) return PIH_COL_PIPE;
+  return hit == HIT_TABLE ? PIH_COL_TABLE : PIH_COL_BG;
+}
+// outward unit normal at the point ph of `hit` (the helpers of pih_raycast.h and pih_render.h; radial on the hand's spheres; +z on the table)
+PIH_HD V3 hit_normal(const ViewScene& sc, int hit, V3 ph) {
+  V3 n = mk(0, 0, 1);
+  if (hit < P_HAND) n = capsule_normal(ph, ld3(sc.org[hit]), ld3(sc.org[hit + 1]));
+  else if (hit < P_BOX) n = capsule_normal(ph, ld3(sc.hs[hit - P_HAND]), ld3(sc.hs[hit - P_HAND]));      // (radial: a sphere is a capsule of length 0)
+  else if (hit < P_PIPE) n = box_normal(ph, ldm(sc.fR[hit - P_BOX]), ld3(sc.fc[hit - P_BOX]));
+  else if (hit < P_TUBE) n = capsule_normal(ph, ld3(sc.vtx[hit - P_PIPE]), ld3(sc.vtx[hit - P_PIPE + 1]));
+  else if (hit == P_TUBE) n = tube_normal(ph);
+  return n;
+}
+// the sphere that holds primitive i < VIEW_NPRIM, grown by `pad` (fly::Ball says why the margin is added there)
+PIH_HD fly::Ball prim_ball(const ViewScene& sc, int i, real pad) {
+  if (i < P_HAND) return fly::capsule_ball(ld3(sc.org[i]), ld3(sc.org[i + 1]), ARM_R[i], pad);
+  if (i < P_BOX) return fly::sphere_ball(ld3(sc.hs[i - P_HAND]), ASPH_R[HAND_SPH0 + i - P_HAND], pad);
+  if (i < P_PIPE) return fly::sphere_ball(ld3(sc.fc[i - P_BOX]), norm(ld3(FBOX_H)), pad);
+  if (i < P_TUBE) return fly::capsule_ball(ld3(sc.vtx[i - P_PIPE]), ld3(sc.vtx[i - P_PIPE + 1]), PIH_PIPE_RADIUS, pad);
+  return fly::sphere_ball(ld3(HOLE_POS), (real)sqrt(PIH_HOLE_HALFLEN * PIH_HOLE_HALFLEN + PIH_HOLE_ROUT * PIH_HOLE_ROUT), pad);
+}
+
+// one pixel: xc, yc = camera-plane coordinates of the pixel centre (already multiplied by tx / ty); prims = bit i set if primitive i
+// may cover the pixel (wave-uniform); hit_out = what the ray hit (primitive index, HIT_TABLE, HIT_NONE)
+PIH_HD real4 shade_hit(const ViewScene& sc, unsigned long long prims, real xc, real yc, int flags, int& hit_out) {
+  const fly::CameraRay ray = fly::camera_ray(sc, xc, yc);
+  const ViewHit h = nearest_hit(sc, prims, ray);
+  real col = hit_colour(h.hit);
+  if ((flags & PIH_RENDER_SHADED) && h.hit != HIT_NONE) {
+    // Lambert term against the fixed light
+    const V3 n = hit_normal(sc, h.hit, ray.o + h.t * ray.d);
     const real ndl = n.x * PIH_LIGHT_X + n.y * PIH_LIGHT_Y + n.z * PIH_LIGHT_Z;
     col = col * (PIH_LIGHT_AMBIENT + PIH_LIGHT_DIFFUSE * max_(ndl, (real)0));
   }
-  real4 o; o.x = depth; o.y = col; o.z = col; o.w = col;
-  hit_out = hit;
+  real4 o; o.x = fly::depth_value(sc, ray, h.t, h.hit != HIT_NONE); o.y = col; o.z = col; o.w = col;
+  hit_out = h.hit;
   return o;
 }
 

@@ -1,12 +1,12 @@
-// pih_view.hip -- the free camera of the peg-in-hole task (pih_view.h; pih_render_view of include/pih_render_view.h).  A translation unit of its own,
-// for the reason pih_fly_image.hip states: tools/isa_fingerprint.py is to show every older kernel unchanged.
+// pih_view.hip -- the free camera of the peg-in-hole task (pih_view.h; pih_render_view of include/pih_render_view.h).  A translation unit of its own
+// beside pih_peg.hip, whose step kernel's code is held by tools/isa_fingerprint.py; this kernel is held by tests/test_gpu_scene_bits.py.
 //   FMT       0: float4 (depth, r, g, b) | PIH_RENDER_OUT_RGBA8: one 32-bit word (r, g, b, seg) | PIH_RENDER_OUT_DEPTH: one float
 //   cam_dev   != nullptr (PIH_RENDER_CAM_DEVICE): float[count, PIH_CAM_WORDS], row blockIdx.y is this workgroup's camera -- 13 wave-uniform
 //             loads; nullptr: `cam`, by value
 // Mapping as pih_render_kernel and pih_fly_image_kernel: grid = (strips, envs), 256 threads (4 waves).  The kernel is two calls:
 // view::camera_setup (pih_view.h: state record -> LDS, fk_all, camera row and fly::camera_or_preset with the wrist preset, the scene's two
 // phases; with fly::NoLight) and fly::render_image (pih_fly_render.h: the tile walk render_strip with a 64-bit ballot, in the format FMT);
-// pih_lit_view_kernel (pih_lit.hip) has the same steps written out, with the light.
+// pih_lit_view_kernel (pih_lit.hip) is the same two calls with the light hooked in.
 #include <hip/hip_runtime.h>
 #include "pih_view.h"
 #include "pih_launch.h"

@@ -105,8 +105,8 @@ def _case_handle(torch, case):
 @pytest.mark.gpu
 def test_per_env_cameras(torch_mod, oracle_mod):
     """N = 70: the camera of env e is row e of a device tensor (three cameras in turn); the full range and env_begin = 3, env_count = 5,
-    where row e belongs to env 3 + e.  The envs of RC.per_env_cases against the reference rendered with their own row, and against a call
-    with that row as the one host camera."""
+    where row e belongs to env 3 + e.  The envs of RC.per_env_cases against the reference rendered with their own row, and bit for bit
+    against a call with that row as the one host camera: both calls run the same kernel instance."""
     case = RC.per_env_cases(oracle_mod)["cycle"]
     (W, H), obj, cams = case["size"], case["obj"], case["cams"]
     g, st, cams_dev = _case_handle(torch_mod, case)
@@ -117,7 +117,7 @@ def test_per_env_cameras(torch_mod, oracle_mod):
     assert np.array_equal(_render_guarded(torch_mod, g, W, H, "float4", count=5, env_begin=3, camera=sub), f4[3:8])
     assert np.array_equal(_render_guarded(torch_mod, g, W, H, "rgba8", count=5, env_begin=3, camera=sub), u8[3:8])
     assert np.array_equal(g.render(W, H, camera=cams[3:8].tolist(), env_begin=3, env_count=5, fmt="rgba8").cpu().numpy(), u8[3:8])      # converted and uploaded
-    fig = RC.Figures(); zmax = dmax = cmax = 0.0; identical = True
+    fig = RC.Figures(); zmax = dmax = cmax = 0.0
     for e in case["checked"]:
         scene = R.fly_scene(oracle_mod, st[e], obj)
         ref = R.plain_reference(scene, cams[e], W, H)
@@ -129,12 +129,9 @@ def test_per_env_cameras(torch_mod, oracle_mod):
         # the same env with its row as the single host camera
         one4 = g.render(W, H, camera=cams[e].tolist(), env_begin=e, env_count=1).cpu().numpy()[0]
         one8 = g.render(W, H, camera=cams[e].tolist(), env_begin=e, env_count=1, fmt="rgba8").cpu().numpy()[0]
-        identical = identical and np.array_equal(one4, f4[e]) and np.array_equal(one8, u8[e])
-        agree = one8[..., 3] == u8[e][..., 3]
-        assert (~agree).mean() <= RC.CLASS_SHARE and np.array_equal(one8[agree], u8[e][agree])
-        assert np.abs(one4[..., 0] - f4[e][..., 0])[agree].max() <= RC.FLY_DEPTH_VALUE_TOL and np.abs(one4[..., 1:] - f4[e][..., 1:])[agree].max() <= RC.FLY_COLOUR_TOL
-    print("per-env cameras: %s; float4: max relative depth error %.3e, depth-buffer value %.3e, colour %.3e; bit-identical to the single-camera calls: %s"
-          % (fig.text(), zmax, dmax, cmax, identical))
+        assert np.array_equal(one4, f4[e]) and np.array_equal(one8, u8[e]), "env %d: the per-env call and the single-camera call differ" % e
+    print("per-env cameras: %s; float4: max relative depth error %.3e, depth-buffer value %.3e, colour %.3e; bit-identical to the single-camera calls"
+          % (fig.text(), zmax, dmax, cmax))
     fig.limits()
     assert zmax <= RC.FLY_DEPTH_REL_TOL and dmax <= RC.FLY_DEPTH_VALUE_TOL and cmax <= RC.FLY_COLOUR_TOL
 

@@ -2,12 +2,16 @@
 """Fingerprint of the gfx950 code of every kernel of the library (every csrc/*.hip of the tree), without a GPU: one line per kernel with a hash of its instruction
 stream, the instruction count and the VGPR / AGPR / SGPR / LDS / scratch numbers of the code object metadata.  A refactor that leaves
 the lines of the hot kernels unchanged leaves their speed unchanged (the step kernels sit at the 256-register limit).
-Used that way for the camera kernels' shared pieces (one tile walk, one scene set-up per task: DESIGN.md 6.5): both listings are
-profiles/camera_refactor_fingerprint.txt.  The 33 other kernels' lines had to stay identical; for the 14 camera kernels the resource
-columns had to, and the listing decided between forms of the same code -- (row0 + i) * W + j against e * H * W + i * W + j for the pixel
-index, the light hook under a thread test outside or inside the hook -- that differ by up to 8 VGPRs.  A line whose hash alone moved was
-then checked on the GPU: outputs byte for byte against the parent's build, times against the parent's spread (which sent
-pih_lit_view_kernel back to its own copy of the walk: its three lines are the parent's again).
+That is the rule for the STEP kernels (pih_step_kernel, the four pih_fly_step_kernel instances: what bench.py times) and for every
+kernel that is neither a camera nor a ray kernel: a refactor shows their lines unchanged, hash included.
+The 13 camera kernels are not held by their hashes -- that rule made every camera feature write its scene's primitive list
+again -- but by the contract the hash stood in for: their outputs are pinned bit for bit to a recording of the build
+before (tests/test_gpu_scene_bits.py, tests/golden/scene_bits.npz) and their times are measured against that build on one box
+(profiles/scene_share_bench.txt); the 4 ray kernels are held the same way, and as it happens their lines are the parent's too: that
+measurement sent them back to their own walk (pih_rays.h).  For them the listing shows registers, LDS and scratch (none may appear), and which instances a change left instruction for
+instruction alone.
+Listings: profiles/scene_share_fingerprint.txt (one walk, one normal, one bounding sphere per scene), profiles/camera_refactor_fingerprint.txt
+(one tile walk, one scene set-up per task).
 usage: python tools/isa_fingerprint.py [SOURCE_TREE]    (default: this checkout; e.g. a `git worktree add` of another commit)"""
 import glob
 import hashlib

@@ -38,7 +38,7 @@ def fly_bench():
     out8 = torch.empty(n, H, W, 4, dtype=torch.uint8, device="cuda")
     outd = torch.empty(n, H, W, device="cuda")
     cams = torch.tensor([_lib.FLY_CAM_DEFAULT] * n, device="cuda")      # per-env cameras in device memory: the default camera in every row, so the pixels are the same work
-    # (name, bytes stored per pixel, call); "float4 flat" is pih_fly_render_kernel, the kernel from before the packed formats
+    # (name, bytes stored per pixel, call); "float4 flat" is pih_fly_image_kernel<0> with one host camera, like every other case without per-env cameras
     cases = (("random-fly float4 flat", 16, lambda: fly.render(W, H, out=out)),
              ("random-fly float4 shaded", 16, lambda: fly.render(W, H, out=out, shaded=True)),
              ("random-fly rgba8 flat", 4, lambda: fly.render(W, H, out=out8, fmt="rgba8")),
