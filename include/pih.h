@@ -286,5 +286,9 @@ const char* pih_last_error(pih_handle* h);
  * in pih_robot.h.  Defined here for the same reason */
 #define PIH_RAY_WORDS 6
 #define PIH_RAY_HIT_WORDS 8
+/* words of a closest-point query (x, y, z, reach [m]) and of its record (signed distance, seg, closest point xyz, outward unit normal xyz) of
+ * pih_closest_points, declared in pih_robot.h.  Defined here for the same reason */
+#define PIH_POINT_WORDS 4
+#define PIH_CLOSEST_WORDS 8
 #include "pih_robot.h"
 #endif

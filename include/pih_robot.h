@@ -8,6 +8,7 @@
  *   pih_robot_mass_matrix              p.calculateMassMatrix(body, q)
  *   pih_robot_inverse_dynamics         p.calculateInverseDynamics(body, q, qd, qdd)  -- see the damping note below
  *   pih_ray_test                       p.rayTestBatch(from, to, parentObjectUniqueId, parentLinkIndex)  -- the scene query, at the end
+ *   pih_closest_points                 p.getClosestPoints(bodyA, bodyB, distance) for a point against the scene  -- after it
  *
  * Conventions: n problems, independent of the handle's env count (as pih_ik); both robots work on a handle of either task (as pih_ik /
  * pih_ik_ur5).  Every pointer is a DEVICE pointer to float32, row-major, contiguous.  Nothing synchronises: the work is enqueued on the
@@ -98,6 +99,39 @@ int pih_link_states(pih_handle* h, float* out_dev, int env_begin, int env_count,
                                    random-fly the six UR5 capsules (a sensor mounted on the hand looks out through it) */
 int pih_ray_test(pih_handle* h, float* out_dev, const float* rays_dev, int rays_per_env,
                  int env_begin, int env_count, int flags, void* stream);
+
+/* Batched closest-point queries against the same scene, at the envs' CURRENT state: for each of points_per_env points per env, how far it
+ * is from the nearest selected primitive, which one that is, the closest point on its surface and the outward normal there.
+ * A query is PIH_POINT_WORDS floats: the point x, y, z in the env-local frame, or with PIH_RAY_FRAME_EE in the end-effector frame of each
+ * env (the frames of pih_ray_test), and reach [m], the `distance` argument of p.getClosestPoints: only what is nearer than reach is
+ * reported.  points_dev float[env_count, points_per_env, 4], or with PIH_RAY_SHARED float[points_per_env, 4].  flags: these two bits.
+ * groups: a mask of PIH_GROUP_*, what the point is measured against.  A group the task does not have selects nothing.
+ * out_dev float[env_count, points_per_env, PIH_CLOSEST_WORDS], per query:
+ *   word 0      the smallest signed distance over the selected primitives, each the primitive's exact signed distance, negative inside it:
+ *               sphere and capsule |p - axis| - r; oriented box Euclidean outside, -(distance to the nearest face) inside; the hole tube
+ *               the 2-D box distance of the rectangle [-halflen, halflen] x [rin, rout] in (axial, radial) coordinates -- the bore counts
+ *               as outside, the hole's centre is +rin away; the table plane z - PIH_TABLE_Z, a half space
+ *   word 1      that primitive's segmentation value as a float, the values pih_ray_test reports
+ *   words 2..4  the closest point on its surface, words 5..7 the outward unit normal there, both env-local:
+ *               query point = closest point + distance x normal, inside and outside alike
+ *   miss        nothing selected is nearer than reach: reach, PIH_SEG_NONE, the query point (env-local), normal 0
+ * The primitives are walked in the order table, pipe capsules, tube, finger boxes, hand spheres, arm links (1, 5, 0, 2, 3, 4, 6; random-fly:
+ * table, links, object spheres) and a later one takes the query only if it is strictly nearer: an exact tie keeps the first.  Where the
+ * closest point is not unique (a sphere's centre, a capsule's axis, the tube's axis) one of them is reported, with its finite unit normal.
+ * A query with a word that is NaN, infinite or beyond 1e15, or with reach <= 0, gets the miss record with words 0 and 2..4 as given; no
+ * other query is affected, and no table is indexed by anything derived from query data.
+ * Errors: -2, and pih_last_error names the argument: a NULL handle (pih_last_error(NULL)), NULL out_dev or points_dev, points_per_env < 1
+ * or > 2^20, env_begin / env_count outside the handle's envs or env_count > 65535, groups with a bit outside PIH_GROUP_ALL or selecting
+ * nothing in the handle's task, an unknown flag bit, out_dev or points_dev not 16-byte aligned.  Nothing synchronises. */
+/* (PIH_POINT_WORDS = 4 and PIH_CLOSEST_WORDS = 8 are defined in pih.h, beside PIH_RAY_WORDS) */
+#define PIH_GROUP_ARM     1   /* peg-in-hole: 7 arm capsules + 4 hand spheres; random-fly: the 6 UR5 capsules */
+#define PIH_GROUP_FINGERS 2   /* peg-in-hole: the two finger-pad boxes */
+#define PIH_GROUP_OBJECT  4   /* peg-in-hole: the 24 pipe capsules; random-fly: the object's spheres */
+#define PIH_GROUP_HOLE    8   /* peg-in-hole: the hole tube */
+#define PIH_GROUP_TABLE   16  /* the table plane z = PIH_TABLE_Z, a half space: negative below it */
+#define PIH_GROUP_ALL     31
+int pih_closest_points(pih_handle* h, float* out_dev, const float* points_dev, int points_per_env,
+                       int groups, int env_begin, int env_count, int flags, void* stream);
 #ifdef __cplusplus
 }
 #endif

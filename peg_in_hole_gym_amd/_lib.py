@@ -29,6 +29,10 @@ LINK_STATE_WORDS = 13   # pos xyz, quat xyzw, linear velocity of the frame origi
 ROBOT_PANDA, ROBOT_UR5 = 0, 1                      # PIH_ROBOT_*: 9 DOF / 10 frames (9 = grasp-target), 6 DOF / 7 frames (6 = ee_link)
 # batched ray tests (pih_ray_test of include/pih_robot.h): a ray is from xyz, to xyz; a record is hit fraction, seg, position xyz, normal xyz
 RAY_WORDS, RAY_HIT_WORDS = 6, 8
+# batched closest-point queries (pih_closest_points): a query is x, y, z, reach; a record is signed distance, seg, closest point xyz, normal xyz
+POINT_WORDS, CLOSEST_WORDS = 4, 8
+GROUP_ARM, GROUP_FINGERS, GROUP_OBJECT, GROUP_HOLE, GROUP_TABLE, GROUP_ALL = 1, 2, 4, 8, 16, 31    # PIH_GROUP_*: what a point is measured against
+GROUPS = {"arm": GROUP_ARM, "fingers": GROUP_FINGERS, "object": GROUP_OBJECT, "hole": GROUP_HOLE, "table": GROUP_TABLE}
 RAY_FRAME_EE, RAY_SHARED, RAY_IGNORE_ROBOT = 1, 2, 4    # PIH_RAY_*: rays in the end-effector frame | one ray set for all envs | the arm is transparent
 FIELD_STATE, FIELD_TIP_POSE, FIELD_CONTACT_FORCE, FIELD_DEBUG, FIELD_EE_POS = 0, 1, 2, 3, 4
 TASK_PEG_IN_HOLE, TASK_RANDOM_FLY = 0, 1
@@ -49,7 +53,7 @@ EXPORTS = ["pih_default_config", "pih_abi_version", "pih_task_dims", "pih_object
            "pih_get_state", "pih_set_state", "pih_ik", "pih_ik_ur5", "pih_render", "pih_render_ex", "pih_render_cam", "pih_grasp_labels", "pih_timing", "pih_timing2", "pih_set_timing", "pih_last_error"]
 LIGHT_EXPORTS = ["pih_render_lit"]      # what include/pih_render_light.h declares (tests/test_render_lit.py compares it with that header)
 ROBOT_EXPORTS = ["pih_robot_dims", "pih_link_states_frames", "pih_robot_fk", "pih_robot_jacobian", "pih_robot_mass_matrix", "pih_robot_inverse_dynamics",
-                 "pih_link_states", "pih_ray_test"]      # what include/pih_robot.h declares (tests/test_robot_query.py compares it with that header)
+                 "pih_link_states", "pih_ray_test", "pih_closest_points"]      # what include/pih_robot.h declares (tests/test_robot_query.py compares it with that header)
 VIEW_EXPORTS = ["pih_render_view"]      # what include/pih_render_view.h declares on top of that (tests/test_peg_view.py compares it with that header)
 
 
@@ -111,6 +115,7 @@ def load():
     L.pih_robot_mass_matrix.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp]
     L.pih_robot_inverse_dynamics.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, vp, vp]
     L.pih_link_states.argtypes = [vp, vp, C.c_int, C.c_int, vp]
+    L.pih_closest_points.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]      # (h, out, points, points_per_env, groups, env_begin, env_count, flags, stream)
     L.pih_ray_test.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]        # (h, out, rays, rays_per_env, env_begin, env_count, flags, stream)
     L.pih_grasp_labels.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp]
     L.pih_reseed.argtypes = [vp, C.c_uint64]

@@ -655,6 +655,28 @@ int pih_ray_test(pih_handle* h, float* out_dev, const float* rays_dev, int rays_
   return 0;
 }
 
+// ---- batched closest-point queries (include/pih_robot.h; kernels in pih_dist.hip)
+int pih_closest_points(pih_handle* h, float* out_dev, const float* points_dev, int points_per_env, int groups, int env_begin, int env_count, int flags, void* stream) {
+  if (!h) return robot_bad(h, "pih_closest_points", "h", "is NULL");
+  if (!out_dev) return robot_bad(h, "pih_closest_points", "out_dev", "is NULL");
+  if (!points_dev) return robot_bad(h, "pih_closest_points", "points_dev", "is NULL");
+  if (points_per_env < 1) return robot_bad(h, "pih_closest_points", "points_per_env", "is smaller than 1");
+  if (points_per_env > (1 << 20)) return robot_bad(h, "pih_closest_points", "points_per_env", "is larger than 2^20");
+  if (env_begin < 0 || env_count <= 0 || env_begin > h->cfg.n_envs || env_count > h->cfg.n_envs - env_begin)
+    return robot_bad(h, "pih_closest_points", "env_begin / env_count", "is outside the handle's envs");
+  if (env_count > 65535) return robot_bad(h, "pih_closest_points", "env_count", "is larger than 65535 per call");
+  if ((groups & ~PIH_GROUP_ALL) != 0) return robot_bad(h, "pih_closest_points", "groups", "has a bit outside PIH_GROUP_ALL");
+  if ((groups & (h->fly ? (PIH_GROUP_ARM | PIH_GROUP_OBJECT | PIH_GROUP_TABLE) : PIH_GROUP_ALL)) == 0)
+    return robot_bad(h, "pih_closest_points", "groups", "selects nothing in this task");
+  if ((flags & ~(PIH_RAY_FRAME_EE | PIH_RAY_SHARED)) != 0) return robot_bad(h, "pih_closest_points", "flags", "has an unknown bit");
+  if ((reinterpret_cast<uintptr_t>(out_dev) & 15) != 0) return robot_bad(h, "pih_closest_points", "out_dev", "must be 16-byte aligned");
+  if ((reinterpret_cast<uintptr_t>(points_dev) & 15) != 0) return robot_bad(h, "pih_closest_points", "points_dev", "must be 16-byte aligned");
+  PIH_ENTER(h);
+  closest_points_launch(h->fly, (hipStream_t)stream, h->state, out_dev, points_dev, points_per_env, groups, h->cfg.n_envs, h->P.object, env_begin, env_count, flags);
+  HIPCHK(h, hipGetLastError());
+  return 0;
+}
+
 const char* pih_last_error(pih_handle* h) { return h ? h->err.c_str() : g_err.c_str(); }
 
 }  // extern "C"

@@ -63,4 +63,7 @@ int link_states_frames(int task_id);
 // ---- pih_rays.hip: the batched ray tests of include/pih_robot.h
 void ray_test_launch(bool fly_task, hipStream_t stream, const float* state, float* out, const float* rays_dev, int rays_per_env,
                      int n_envs, int object, int env_begin, int env_count, int flags);
+// ---- pih_dist.hip: the batched closest-point queries of include/pih_robot.h
+void closest_points_launch(bool fly_task, hipStream_t stream, const float* state, float* out, const float* points, int points_per_env,
+                           int groups, int n_envs, int object, int env_begin, int env_count, int flags);
 }  // namespace pih

@@ -129,6 +129,12 @@ class PegInHole(MetaEnv):
         (PihVecEnv.ray_test: frame, ignore_robot, env_begin, env_count, out) -> the backend's [envs, rays, 8] tensor"""
         return self._backend.ray_test(rays, **kw)
 
+    def closest_points(self, points, **kw):
+        """getClosestPoints of points against the scene of render_view -- groups "arm", "fingers", "object" (the pipe), "hole", "table" --
+        at the current state (PihVecEnv.closest_points: reach, frame, groups, env_begin, env_count, out) -> the backend's
+        [envs, points, 8] tensor"""
+        return self._backend.closest_points(points, **kw)
+
 
 class RandomFly(MetaEnv):
     """'random-fly' (README.md:38: task='random-fly', args=['Banana', 1/120.]): the UR5 of assets/urdf/ur5.urdf driven by
@@ -175,3 +181,8 @@ class RandomFly(MetaEnv):
         """rayTestBatch against the scene of render(camera=...) -- UR5, object, table -- at the current state (PihVecEnv.ray_test: frame,
         ignore_robot, env_begin, env_count, out) -> the backend's [envs, rays, 8] tensor"""
         return self._backend.ray_test(rays, **kw)
+
+    def closest_points(self, points, **kw):
+        """getClosestPoints of points against the scene of render(camera=...) -- groups "arm" (the UR5), "object", "table" -- at the
+        current state (PihVecEnv.closest_points: reach, frame, groups, env_begin, env_count, out) -> the backend's [envs, points, 8] tensor"""
+        return self._backend.closest_points(points, **kw)

@@ -349,6 +349,56 @@ class PihVecEnv:
             self._chk(self.L.pih_ray_test(self.h, out.data_ptr(), rays.data_ptr(), int(R), int(env_begin), int(count), flags, self._stream()), "pih_ray_test")
         return out
 
+    def closest_points(self, points, reach=None, frame="env", groups=("arm", "fingers", "object", "hole", "table"), env_begin=0, env_count=None, out=None):
+        """getClosestPoints of points against the scene of ray_test, at the envs' CURRENT state (pih_closest_points, include/pih_robot.h).
+        points: [P, 3 | 4] = x, y, z (and reach), the same queries for every env of the call, or [count, P, 3 | 4], one set per env.  A
+            3-column tensor takes the scalar `reach` for every query (required then; with 4 columns `reach` must be None).  reach [m] is
+            the `distance` argument of getClosestPoints: only what is nearer is reported.
+        frame: "env" | "ee", as for ray_test.
+        groups: what the points are measured against: names of _lib.GROUPS ("arm", "fingers", "object", "hole", "table") or a mask of
+            _lib.GROUP_*.  A group the task does not have selects nothing; a mask that selects nothing at all is an error.
+        -> float32 [count, P, 8] on the device: signed distance (negative inside a primitive), what is nearest (the seg values of
+        ray_test as floats), the closest point on its surface xyz and the outward unit normal there xyz, both env-local: point = closest
+        point + distance x normal.  Nothing within reach: reach, _lib.SEG_NONE, the query point, normal 0.  A query with a NaN / Inf word
+        or reach <= 0 reports that too; the others of the call are not affected.  out: a contiguous float32 tensor of that shape on this
+        handle's device (ValueError otherwise)."""
+        count = self.n - env_begin if env_count is None else env_count
+        if frame not in self._RAY_FRAME:
+            raise ValueError("closest_points: frame must be one of %s, got %r" % (sorted(self._RAY_FRAME), frame))
+        if isinstance(groups, str):
+            groups = (groups,)
+        if not isinstance(groups, int):
+            unknown = [g for g in groups if g not in _lib.GROUPS]
+            if unknown:
+                raise ValueError("closest_points: groups must be names of %s, got %r" % (sorted(_lib.GROUPS), unknown))
+            mask = 0
+            for g in groups:
+                mask |= _lib.GROUPS[g]
+            groups = mask
+        points = torch.as_tensor(points).to(device=self.device, dtype=torch.float32)
+        if points.ndim not in (2, 3) or points.shape[-1] not in (3, _lib.POINT_WORDS) or points.shape[-2] < 1 or (points.ndim == 3 and points.shape[0] != count):
+            raise ValueError("closest_points: points must have shape [P, 3 | 4] (shared) or [%d, P, 3 | 4] (one set per env of the call) with P >= 1, got %s"
+                             % (count, tuple(points.shape)))
+        if (points.shape[-1] == 3) != (reach is not None):
+            raise ValueError("closest_points: give `reach` with 3-column points and only then (a fourth column is the reach of each query)")
+        if reach is not None:
+            points = torch.cat([points, torch.full(points.shape[:-1] + (1,), float(reach), device=self.device)], dim=-1)
+        points = points.contiguous()
+        if points.data_ptr() % 16:
+            points = points.clone()            # (a view into a larger tensor: the kernel loads a query as one aligned 16-byte word)
+        P = points.shape[-2]
+        shape = (count, P, _lib.CLOSEST_WORDS)
+        if out is None:
+            out = torch.empty(shape, device=self.device)
+        elif not (torch.is_tensor(out) and out.dtype == torch.float32 and tuple(out.shape) == shape and self._here(out) and out.is_contiguous()):
+            raise ValueError("closest_points: out must be a contiguous float32 tensor of shape %s on %s" % (shape, self.device))
+        flags = self._RAY_FRAME[frame] | (_lib.RAY_SHARED if points.ndim == 2 else 0)
+        self._points_keep = points             # (a converted copy lives until the next call: the launch is asynchronous)
+        with torch.cuda.device(self.device):
+            self._chk(self.L.pih_closest_points(self.h, out.data_ptr(), points.data_ptr(), int(P), int(groups), int(env_begin), int(count), flags, self._stream()),
+                      "pih_closest_points")
+        return out
+
     def ray_fan(self, origin, axis, half_angle_deg, rings, per_ring, length):
         """float32 [1 + rings * per_ring, 6] device tensor: a cone of rays from `origin` about `axis` (module function ray_fan), for
         ray_test -- with frame="ee" a proximity sensor that rides on the hand.  Built on the device, no host round trip."""
