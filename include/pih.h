@@ -61,7 +61,10 @@ enum {
   PIH_DBG_FLY_LAMBDA = 200,    /* + c: normal multiplier of compacted contact c */
   /* both tasks, config.debug = 2 */
   PIH_DBG_CYCLES = 900,        /* + k: shader-clock cycles of phase k.  peg-in-hole: 0 fk, 1 controller rows, 2 collide, 3 aba, 4 rows, 5 pgs,
-                                  6 integrate, 7 fk2, and the sub-phase stamps 8, 9, 10, 15; random-fly: 0 kinematics + candidates, 1 aba, 2 motor rows,
+                                  6 integrate, 7 fk2, the sub-phase stamps 8, 9, 10, 15 of aba, and those of collide: 16 its entry, 17 constants,
+                                  sample positions and the candidates of the sample tests, 18 slots of table, tube, attach, weld, arm spheres vs
+                                  table, 19 slots of the pads, 20 of arm spheres vs pipe, 21 pairs (collide<W>, the nine-pass form: 17 samples +
+                                  table + tube, 18 attach + weld + arm spheres vs table, 19 pads, 20 arm spheres vs pipe, 21 pairs); random-fly: 0 kinematics + candidates, 1 aba, 2 motor rows,
                                   3 contact rows, 4 IK targets, 5 pgs, 6 integrate */
   PIH_DBG_T_START = 940,       /* start of the env's wavefront on the chip-wide 100 MHz clock, as bits 0..15, 16..31, 32..47 (3) */
   PIH_DBG_T_END = 943,         /* its end, the same way (3).  random-fly writes 940 .. 947 on the wavefront's first env only */

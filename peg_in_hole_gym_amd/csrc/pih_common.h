@@ -601,56 +601,186 @@ template <class W> PIH_HD void controller_rows(W& w, Shared& sh, const Params& P
 }
 
 // ------------------------------------------------------------------------------------------------ collision
+// The geometric tests, one function each.  collide<W> below states the pass order with them (host harness); the wave form of pih_wave.h
+// evaluates the sample tests in one walk over the pipe samples and hands out the slots afterwards, in the same order.
+// A candidate: is there a contact, its point, its normal and its depth.
+struct Cand { bool valid; V3 p, n; real depth; };
+PIH_HD Cand no_cand(real depth = 0) { Cand c; c.valid = false; c.p = mk(0, 0, 0); c.n = mk(0, 0, 0); c.depth = depth; return c; }
+PIH_HD V3 sample_point(const Shared& sh, int L, real y) { return ld3(sh.LO[L]) + mul(ldm(sh.a.LR[L]), mk(0, y, 0)); }
+PIH_HD int vertex_key(int slink, real sy) { return sy > (real)0.02 && slink == 23 ? 24 : slink; }       // vertex ordinal of a vertex sample
+PIH_HD void emit_contact(Shared& sh, int slot, int la, int lb, int key, V3 p, V3 n, real depth, real mu) {
+  sh.c_la[slot] = la; sh.c_lb[slot] = lb; sh.c_key[slot] = key; st3(sh.c_p[slot], p); st3(sh.c_n[slot], n);
+  sh.c_depth[slot] = depth; sh.c_mu[slot] = clampr(mu, -PIH_MAX_FRICTION, PIH_MAX_FRICTION);
+}
+// sphere (centre c, radius rs) vs the table plane: the pipe's vertex samples (rs = r) and the arm spheres
+PIH_HD Cand sphere_vs_table(V3 c, real rs, real margin) {
+  Cand o; o.depth = c.z - (real)PIH_TABLE_Z - rs; o.valid = o.depth < margin;
+  o.p = mk(c.x, c.y, c.z - rs - (real)0.5 * o.depth); o.n = mk(0, 0, 1);
+  return o;
+}
+// sample sphere vs the hole tube (axis x through `hole`): exact SDF of the solid of revolution of a rectangle in (axial a, radial rho)
+PIH_HD Cand sample_vs_tube(V3 sp, V3 hole, real r, real margin) {
+  const real hl = (real)PIH_HOLE_HALFLEN, rcx = (real)(0.5 * (PIH_HOLE_RIN + PIH_HOLE_ROUT)), hw = (real)(0.5 * (PIH_HOLE_ROUT - PIH_HOLE_RIN));
+  Cand o = no_cand();
+  V3 d = sp - hole;
+  real a = d.x, rho = (real)sqrt(d.y * d.y + d.z * d.z);
+  real dx = absr(a) - hl, dy = absr(rho - rcx) - hw;
+  if (!(dx > r + margin || dy > r + margin)) {
+    real sa = a >= 0 ? (real)1 : (real)-1, sr = rho >= rcx ? (real)1 : (real)-1, ga, gr, sdf;
+    if (dx <= 0 && dy <= 0) { if (dx > dy) { ga = sa; gr = 0; sdf = dx; } else { ga = 0; gr = sr; sdf = dy; } }
+    else { real mx = dx > 0 ? dx : 0, my = dy > 0 ? dy : 0; sdf = (real)sqrt(mx * mx + my * my); ga = sa * mx / sdf; gr = sr * my / sdf; }
+    o.depth = sdf - r;
+    // (on the axis the nearest point of the wall is a whole circle: there is no radial direction, and rho < Rin means gr != 0 -- no
+    //  contact rather than one along an invented direction; reached only at a margin above Rin - r = 5.36 mm)
+    if (o.depth < margin && rho > (real)1e-9) {
+      V3 rh = mk(0, d.y / rho, d.z / rho);
+      o.n = mk(ga, gr * rh.y, gr * rh.z); o.p = sp - (r + (real)0.5 * o.depth) * o.n; o.valid = true;
+    }
+  }
+  return o;
+}
+// sample sphere vs a finger pad box (frame Rf, centre bc, half extents bh); pre-filter on the distance to the box centre, exact for any
+// margin: a sphere within r + margin of the box has its centre within that plus the half diagonal (+ 0.1 mm against rounding, as the
+// self-collision broad phase): padreach
+PIH_HD real pad_reach(V3 bh, real r, real margin) { return norm(bh) + r + margin + (real)1e-4; }
+PIH_HD Cand sample_vs_pad(V3 sp, const M3& Rf, V3 bc, V3 bh, real padreach, real r, real margin) {
+  Cand o = no_cand();
+  V3 d = sp - bc;
+  if (dot(d, d) <= padreach * padreach) {
+    V3 pl = tmul(Rf, d);
+    V3 q = mk(clampr(pl.x, -bh.x, bh.x), clampr(pl.y, -bh.y, bh.y), clampr(pl.z, -bh.z, bh.z));
+    bool inside = q.x == pl.x && q.y == pl.y && q.z == pl.z;
+    V3 nl; real sdf;
+    if (inside) {
+      real bx = bh.x - absr(pl.x), by = bh.y - absr(pl.y), bz = bh.z - absr(pl.z);
+      int ax = 0; real best = bx;
+      if (by < best) { best = by; ax = 1; }
+      if (bz < best) { best = bz; ax = 2; }
+      nl = mk(ax == 0 ? (pl.x >= 0 ? (real)1 : (real)-1) : 0, ax == 1 ? (pl.y >= 0 ? (real)1 : (real)-1) : 0, ax == 2 ? (pl.z >= 0 ? (real)1 : (real)-1) : 0);
+      sdf = -best;
+    } else { V3 df = pl - q; sdf = norm(df); nl = ((real)1 / sdf) * df; }
+    o.depth = sdf - r;
+    if (o.depth < margin) { o.n = mul(Rf, nl); o.p = sp - (r + (real)0.5 * o.depth) * o.n; o.valid = true; }
+  }
+  return o;
+}
+// sample sphere vs the hand / flange / wrist spheres PIH_ARM_PIPE_SPH0.. (centre(s), radius(s)): the deepest one, its index in bs
+template <class FC, class FR> PIH_HD Cand sample_vs_arm_spheres(V3 sp, FC centre, FR radius, real r, real margin, int& bs) {
+  Cand o = no_cand(margin);
+  bs = 0;
+#pragma unroll
+  for (int s = PIH_ARM_PIPE_SPH0; s < PIH_ARM_NSPH; s++) {
+    const V3 d = sp - centre(s);
+    const real d2 = dot(d, d), reach = margin + r + radius(s);      // (depth <= margin: out of reach, out of the running)
+    if (d2 < reach * reach) {
+      const real dist = (real)sqrt(d2), dep = dist - r - radius(s);
+      if (dep < o.depth && dist > (real)1e-9) { o.depth = dep; bs = s; o.n = ((real)1 / dist) * d; o.valid = true; }
+    }
+  }
+  if (o.valid) o.p = sp - (r + (real)0.5 * o.depth) * o.n;
+  return o;
+}
+// idx -> (s, t) of the 253 self-collision pairs in key order: row s has (22 - s) entries (t = s+2..23), C(s) = s (45 - s) / 2 pairs come
+// before it: closed form + one correction step either way instead of a per-lane search loop of up to 22 trips (the whole wave waited
+// for the longest)
+PIH_HD void pair_of_index(int idx, int& s, int& t) {
+  s = (int)((real)0.5 * ((real)45 - (real)sqrt((real)(2025 - 8 * idx))));
+  if ((s + 1) * (44 - s) / 2 <= idx) s++;
+  if (s * (45 - s) / 2 > idx) s--;
+  t = s + 2 + idx - s * (45 - s) / 2;
+}
+// vertex v = first sample of segment v (v<24) / last sample (v=24): sample index of vertex v
+PIH_HD int vertex_sample(int v) { return v == 0 ? 0 : (v == 24 ? NSAMP - 1 : 7 + 5 * (v - 1)); }
+// capsule segments p1 q1 and p2 q2 of the pipe (radius r each)
+PIH_HD Cand segment_pair(V3 p1, V3 q1, V3 p2, V3 q2, real r, real margin) {
+  Cand o = no_cand();
+  V3 dm = (p1 + q1) - (p2 + q2);
+  // broad phase on the segment midpoints, exact for any geometry and margin: two segments closer than 2 r + margin have midpoints
+  // closer than that plus half of each length (dm = 2 x the midpoint difference).  With the fixed 12 cm of before, every pair two
+  // links apart (midpoints 11 cm apart on a straight pipe) went through the closest-point code; now a wave whose pairs are
+  // all out of reach skips it
+  V3 d1 = q1 - p1, d2 = q2 - p2;
+  real a = dot(d1, d1), e = dot(d2, d2);
+  const real reach = (real)sqrt(a) + (real)sqrt(e) + 2 * (2 * r + margin) + (real)1e-4;
+  if (dot(dm, dm) <= reach * reach) {
+    V3 rr = p1 - p2;
+    real f = dot(d2, rr), ss, tt;
+    const real EPS = (real)1e-12;
+    if (a <= EPS && e <= EPS) { ss = tt = 0; }
+    else if (a <= EPS) { ss = 0; tt = clampr(f / e, 0, 1); }
+    else {
+      real c = dot(d1, rr);
+      if (e <= EPS) { tt = 0; ss = clampr(-c / a, 0, 1); }
+      else {
+        real b = dot(d1, d2), den = a * e - b * b;
+        ss = den > EPS ? clampr((b * f - c * e) / den, 0, 1) : (real)0;
+        tt = (b * ss + f) / e;
+        if (tt < 0) { tt = 0; ss = clampr(-c / a, 0, 1); } else if (tt > 1) { tt = 1; ss = clampr((b - c) / a, 0, 1); }
+      }
+    }
+    V3 c1 = p1 + ss * d1, c2 = p2 + tt * d2, d = c1 - c2;
+    real dist = norm(d); o.depth = dist - 2 * r;
+    if (o.depth < margin && dist >= (real)1e-9) { o.n = ((real)1 / dist) * d; o.p = (real)0.5 * (c1 + c2); o.valid = true; }
+  }
+  return o;
+}
+// p7 attach (envs/peg_in_hole.py:99-104), restated as a ball joint between the grasp point of the grasped pipe link
+// (childFramePosition = random_vector) and the grasp-target origin (parentFramePosition = 0): link L, point, normal, distance as depth
+PIH_HD Cand attach_ball_contact(Shared& sh, int& L) {
+  Cand o;
+  int g = (int)sh.S[PIH_S_GRASP];
+  L = g == 0 ? ANL : NL - 1;
+  V3 a1 = ld3(sh.LO[L]) + mul(ldm(sh.a.LR[L]), mk(0, (g == 0 ? (real)0.045 : (real)0.015) + sh.S[PIH_S_RANDY], 0));
+  V3 ee; M3 eR; ee_pose(sh, ee, eR);
+  V3 d = a1 - ee; real dist = norm(d);
+  o.n = dist > (real)1e-9 ? ((real)1 / dist) * d : mk(1, 0, 0);
+  o.p = (real)0.5 * (a1 + ee); o.depth = dist; o.valid = true;
+  return o;
+}
+// ... and the WELD's three bilateral ANGULAR rows: `p` carries the rotation-vector error, n = x so that (n, t1, t2) is an orthonormal
+// triad: the child frame R_link R_cf, R_cf = quat(euler(0, -pi, pi/2 + targetOrn[2])) as the reference passes it (childFrameOrientation,
+// envs/peg_in_hole.py:101), must coincide with the parent frame (link 11, parentFrameOrientation = identity)
+PIH_HD Cand attach_weld_contact(Shared& sh, int& L) {
+  Cand o;
+  int g = (int)sh.S[PIH_S_GRASP];
+  L = g == 0 ? ANL : NL - 1;
+  V3 ee; M3 eR; ee_pose(sh, ee, eR);
+  const M3 Rcf = q_to_m(quat_from_euler(0, -PIH_PI, PIH_PI / 2 + sh.S[PIH_S_ATTACH_QZ]));
+  const M3 Rc = mul(ldm(sh.a.LR[L]), Rcf);
+  M3 eRt; for (int r = 0; r < 3; r++) for (int c = 0; c < 3; c++) eRt.m[3 * r + c] = eR.m[3 * c + r];
+  const Q4 qe = m_to_q(mul(Rc, eRt));
+  const V3 xyz = mk(qe.x, qe.y, qe.z);
+  const real sn = norm(xyz); real ang = 2 * (real)atan2(sn, qe.w);
+  if (ang > PIH_PI) ang -= 2 * PIH_PI;
+  o.p = sn > (real)1e-12 ? (ang / sn) * xyz : mk(0, 0, 0);
+  o.n = mk(1, 0, 0); o.depth = 0; o.valid = true;
+  return o;
+}
+
 template <class W> PIH_HD void collide(W& w, Shared& sh, const Params& P) {
   const real r = (real)PIH_PIPE_RADIUS, margin = P.margin;
-  w.par(NSAMP, [&](int i) {
-    int L = ANL + SAMP_LINK[i];
-    V3 p = ld3(sh.LO[L]) + mul(ldm(sh.a.LR[L]), mk(0, SAMP_Y[i], 0));
-    st3(sh.a.SP[i], p);
-  });
-  auto emit = [&](int slot, int la, int lb, int key, V3 p, V3 n, real depth, real mu) {
-    sh.c_la[slot] = la; sh.c_lb[slot] = lb; sh.c_key[slot] = key; st3(sh.c_p[slot], p); st3(sh.c_n[slot], n);
-    sh.c_depth[slot] = depth; sh.c_mu[slot] = clampr(mu, -PIH_MAX_FRICTION, PIH_MAX_FRICTION);
-  };
+  w.stamp(16);
+  w.par(NSAMP, [&](int i) { st3(sh.a.SP[i], sample_point(sh, ANL + SAMP_LINK[i], SAMP_Y[i])); });
+  auto emit = [&](int slot, int la, int lb, int key, V3 p, V3 n, real depth, real mu) { emit_contact(sh, slot, la, lb, key, p, n, depth, mu); };
   w.alloc_reset(0);
   // table plane: vertices only
   w.par_all(NSAMP, [&](int i, bool in) {
-    bool valid = false; V3 sp = mk(0, 0, 0); real depth = 0; int L = 0;
-    if (in && SAMP_VERTEX[i]) {
-      sp = ld3(sh.a.SP[i]); depth = sp.z - (real)PIH_TABLE_Z - r; L = ANL + SAMP_LINK[i];
-      valid = depth < margin;
-    }
-    int slot = w.alloc(valid);
-    if (valid && slot < CMAX) {
-      int vi = 0;   // vertex ordinal = key
-      { int s = SAMP_LINK[i]; vi = SAMP_Y[i] > (real)0.02 && s == 23 ? 24 : s; }
-      emit(slot, L, -1, vi, mk(sp.x, sp.y, sp.z - r - (real)0.5 * depth), mk(0, 0, 1), depth, L_MU[L] * (real)PIH_TABLE_MU);
+    Cand c = no_cand();
+    if (in && SAMP_VERTEX[i]) c = sphere_vs_table(ld3(sh.a.SP[i]), r, margin);
+    int slot = w.alloc(c.valid);
+    if (c.valid && slot < CMAX) {
+      const int L = ANL + SAMP_LINK[i];
+      emit(slot, L, -1, vertex_key(SAMP_LINK[i], SAMP_Y[i]), c.p, c.n, c.depth, L_MU[L] * (real)PIH_TABLE_MU);   // vertex ordinal = key
     }
   });
-  // hole tube: exact SDF of the solid of revolution of a rectangle in (axial a, radial rho)
-  const real hl = (real)PIH_HOLE_HALFLEN, rcx = (real)(0.5 * (PIH_HOLE_RIN + PIH_HOLE_ROUT)), hw = (real)(0.5 * (PIH_HOLE_ROUT - PIH_HOLE_RIN));
+  // hole tube
   w.par_all(NSAMP, [&](int i, bool in) {
-    bool valid = false; V3 n = mk(0, 0, 0), p = mk(0, 0, 0); real depth = 0; int L = 0;
-    if (in) {
-      V3 sp = ld3(sh.a.SP[i]); V3 d = sp - ld3(HOLE_POS);
-      real a = d.x, rho = (real)sqrt(d.y * d.y + d.z * d.z);
-      real dx = absr(a) - hl, dy = absr(rho - rcx) - hw;
-      if (!(dx > r + margin || dy > r + margin)) {
-        real sa = a >= 0 ? (real)1 : (real)-1, sr = rho >= rcx ? (real)1 : (real)-1, ga, gr, sdf;
-        if (dx <= 0 && dy <= 0) { if (dx > dy) { ga = sa; gr = 0; sdf = dx; } else { ga = 0; gr = sr; sdf = dy; } }
-        else { real mx = dx > 0 ? dx : 0, my = dy > 0 ? dy : 0; sdf = (real)sqrt(mx * mx + my * my); ga = sa * mx / sdf; gr = sr * my / sdf; }
-        depth = sdf - r;
-        // (on the axis the nearest point of the wall is a whole circle: there is no radial direction, and rho < Rin means gr != 0 -- no
-        //  contact rather than one along an invented direction; reached only at a margin above Rin - r = 5.36 mm)
-        if (depth < margin && rho > (real)1e-9) {
-          V3 rh = mk(0, d.y / rho, d.z / rho);
-          n = mk(ga, gr * rh.y, gr * rh.z); p = sp - (r + (real)0.5 * depth) * n; L = ANL + SAMP_LINK[i]; valid = true;
-        }
-      }
-    }
-    int slot = w.alloc(valid);
-    if (valid && slot < CMAX) emit(slot, L, -1, 100 + i, p, n, depth, L_MU[L] * (real)PIH_HOLE_MU);
+    Cand c = no_cand();
+    if (in) c = sample_vs_tube(ld3(sh.a.SP[i]), ld3(HOLE_POS), r, margin);
+    int slot = w.alloc(c.valid);
+    if (c.valid && slot < CMAX) { const int L = ANL + SAMP_LINK[i]; emit(slot, L, -1, 100 + i, c.p, c.n, c.depth, L_MU[L] * (real)PIH_HOLE_MU); }
   });
+  w.stamp(17);
   // p7 attach (envs/peg_in_hole.py:99-104), restated as a ball joint between the grasp point of the grasped pipe link
   // (childFramePosition = random_vector) and the grasp-target origin (parentFramePosition = 0), active in FSM states 4..6:
   // one contact whose three rows are bilateral (mu < 0 marks it); emitted before the finger contacts so it is never dropped
@@ -661,37 +791,13 @@ template <class W> PIH_HD void collide(W& w, Shared& sh, const Params& P) {
     w.par_all(1, [&](int i, bool in) {
       bool valid = in && i == 0 && attached;
       int slot = w.alloc(valid);
-      if (valid && slot < CMAX) {
-        int g = (int)sh.S[PIH_S_GRASP];
-        int L = g == 0 ? ANL : NL - 1;
-        V3 a1 = ld3(sh.LO[L]) + mul(ldm(sh.a.LR[L]), mk(0, (g == 0 ? (real)0.045 : (real)0.015) + sh.S[PIH_S_RANDY], 0));
-        V3 ee; M3 eR; ee_pose(sh, ee, eR);
-        V3 d = a1 - ee; real dist = norm(d);
-        V3 n = dist > (real)1e-9 ? ((real)1 / dist) * d : mk(1, 0, 0);
-        emit(slot, L, PIH_EE_PARENT, 2000, (real)0.5 * (a1 + ee), n, dist, (real)-1);
-      }
+      if (valid && slot < CMAX) { int L; const Cand c = attach_ball_contact(sh, L); emit(slot, L, PIH_EE_PARENT, 2000, c.p, c.n, c.depth, (real)-1); }
     });
-    // ... and, as a WELD (default; config.attach_ball = 1 keeps the ball joint alone), three bilateral ANGULAR rows (mu = -2 marks
-    // them; `p` carries the rotation-vector error, n = x so that (n, t1, t2) is an orthonormal triad): the child frame
-    // R_link R_cf, R_cf = quat(euler(0, -pi, pi/2 + targetOrn[2])) as the reference passes it (childFrameOrientation,
-    // envs/peg_in_hole.py:101), must coincide with the parent frame (link 11, parentFrameOrientation = identity)
+    // ... and, as a WELD (default; config.attach_ball = 1 keeps the ball joint alone), three bilateral ANGULAR rows (mu = -2 marks them)
     w.par_all(1, [&](int i, bool in) {
       bool valid = in && i == 0 && attached && !P.attachball;
       int slot = w.alloc(valid);
-      if (valid && slot < CMAX) {
-        int g = (int)sh.S[PIH_S_GRASP];
-        int L = g == 0 ? ANL : NL - 1;
-        V3 ee; M3 eR; ee_pose(sh, ee, eR);
-        const M3 Rcf = q_to_m(quat_from_euler(0, -PIH_PI, PIH_PI / 2 + sh.S[PIH_S_ATTACH_QZ]));
-        const M3 Rc = mul(ldm(sh.a.LR[L]), Rcf);
-        M3 eRt; for (int r = 0; r < 3; r++) for (int c = 0; c < 3; c++) eRt.m[3 * r + c] = eR.m[3 * c + r];
-        const Q4 qe = m_to_q(mul(Rc, eRt));
-        const V3 xyz = mk(qe.x, qe.y, qe.z);
-        const real sn = norm(xyz); real ang = 2 * (real)atan2(sn, qe.w);
-        if (ang > PIH_PI) ang -= 2 * PIH_PI;
-        const V3 th = sn > (real)1e-12 ? (ang / sn) * xyz : mk(0, 0, 0);
-        emit(slot, L, PIH_EE_PARENT, 2001, th, mk(1, 0, 0), 0, (real)-2);
-      }
+      if (valid && slot < CMAX) { int L; const Cand c = attach_weld_contact(sh, L); emit(slot, L, PIH_EE_PARENT, 2001, c.p, c.n, c.depth, (real)-2); }
     });
     nca += w.alloc_count() - before;
   }
@@ -703,56 +809,34 @@ template <class W> PIH_HD void collide(W& w, Shared& sh, const Params& P) {
     const int before = w.alloc_count();
     const int allowed = CAMAX - nca;
     w.par_all(PIH_ARM_NSPH, [&](int i, bool in) {
-      bool valid = false; V3 cw = mk(0, 0, 0); real depth = 0, rs = 0; int L = 0;
-      if (in) {
-        L = ASPH_LINK[i]; rs = ASPH_R[i];
-        cw = ld3(sh.a.ASP[i]);
-        depth = cw.z - (real)PIH_TABLE_Z - rs;
-        valid = depth < margin;
-      }
-      int slot = w.alloc(valid);
-      if (valid && slot < CMAX && (slot - before) < allowed) emit(slot, L, -1, 3000 + i, mk(cw.x, cw.y, cw.z - rs - (real)0.5 * depth), mk(0, 0, 1), depth, L_MU[L] * (real)PIH_TABLE_MU);
+      Cand c = no_cand();
+      if (in) c = sphere_vs_table(ld3(sh.a.ASP[i]), ASPH_R[i], margin);
+      int slot = w.alloc(c.valid);
+      if (c.valid && slot < CMAX && (slot - before) < allowed) { const int L = ASPH_LINK[i]; emit(slot, L, -1, 3000 + i, c.p, c.n, c.depth, L_MU[L] * (real)PIH_TABLE_MU); }
     });
     int used = w.alloc_count() - before;
     if (used > allowed) { used = allowed; w.alloc_reset(before + allowed); }
     nca += used;
   }
-  // finger pad boxes (arm links 7, 8); pre-filter on the distance to the box centre, exact for any margin: a sphere within r + margin of
-  // the box has its centre within that plus the half diagonal (+ 0.1 mm against rounding, as the self-collision broad phase)
-  const real padreach = norm(ld3(FBOX_H)) + r + margin + (real)1e-4;
+  w.stamp(18);
+  // finger pad boxes (arm links 7, 8)
+  const real padreach = pad_reach(ld3(FBOX_H), r, margin);
   for (int f = 0; f < 2; f++) {
     const int LF = PIH_FINGER_LINK0 + f;
     M3 Rf = ldm(sh.a.LR[LF]); V3 bc = ld3(sh.LO[LF]) + mul(Rf, ld3(FBOX_C[f])); V3 bh = ld3(FBOX_H);
     const int before = w.alloc_count();
     const int allowed = CAMAX - nca;   // arm-involving contacts are capped
     w.par_all(NSAMP, [&](int i, bool in) {
-      bool valid = false; V3 n = mk(0, 0, 0), p = mk(0, 0, 0); real depth = 0; int L = 0;
-      if (in) {
-        V3 sp = ld3(sh.a.SP[i]); V3 d = sp - bc;
-        if (dot(d, d) <= padreach * padreach) {
-          V3 pl = tmul(Rf, d);
-          V3 q = mk(clampr(pl.x, -bh.x, bh.x), clampr(pl.y, -bh.y, bh.y), clampr(pl.z, -bh.z, bh.z));
-          bool inside = q.x == pl.x && q.y == pl.y && q.z == pl.z;
-          V3 nl; real sdf;
-          if (inside) {
-            real bx = bh.x - absr(pl.x), by = bh.y - absr(pl.y), bz = bh.z - absr(pl.z);
-            int ax = 0; real best = bx;
-            if (by < best) { best = by; ax = 1; }
-            if (bz < best) { best = bz; ax = 2; }
-            nl = mk(ax == 0 ? (pl.x >= 0 ? (real)1 : (real)-1) : 0, ax == 1 ? (pl.y >= 0 ? (real)1 : (real)-1) : 0, ax == 2 ? (pl.z >= 0 ? (real)1 : (real)-1) : 0);
-            sdf = -best;
-          } else { V3 df = pl - q; sdf = norm(df); nl = ((real)1 / sdf) * df; }
-          depth = sdf - r;
-          if (depth < margin) { n = mul(Rf, nl); p = sp - (r + (real)0.5 * depth) * n; L = ANL + SAMP_LINK[i]; valid = true; }
-        }
-      }
-      int slot = w.alloc(valid);
-      if (valid && slot < CMAX && (slot - before) < allowed) emit(slot, L, LF, 300 + f * NSAMP + i, p, n, depth, L_MU[L] * L_MU[LF]);
+      Cand c = no_cand();
+      if (in) c = sample_vs_pad(ld3(sh.a.SP[i]), Rf, bc, bh, padreach, r, margin);
+      int slot = w.alloc(c.valid);
+      if (c.valid && slot < CMAX && (slot - before) < allowed) { const int L = ANL + SAMP_LINK[i]; emit(slot, L, LF, 300 + f * NSAMP + i, c.p, c.n, c.depth, L_MU[L] * L_MU[LF]); }
     });
     int used = w.alloc_count() - before;
     if (used > allowed) { used = allowed; w.alloc_reset(before + allowed); }   // the dropped ones are the tail of this pass
     nca += used;
   }
+  w.stamp(19);
   // ... vs the pipe (enable_arm_collision bit 1; the reference loads the full panda.urdf collision model, envs/utils.py:31-34, so
   // hand and wrist cannot pass through the pipe): every pipe sample sphere against the hand / flange / wrist spheres
   // PIH_ARM_PIPE_SPH0.. (the finger tips are covered by the pad boxes above), deepest sphere per sample; keys 5000 + sphere * NSAMP +
@@ -761,74 +845,33 @@ template <class W> PIH_HD void collide(W& w, Shared& sh, const Params& P) {
     const int before = w.alloc_count();
     const int allowed = CAMAX - nca;
     w.par_all(NSAMP, [&](int i, bool in) {
-      bool valid = false; V3 n = mk(0, 0, 0), p = mk(0, 0, 0); real depth = margin; int L = 0, bs = 0;
-      if (in) {
-        const V3 sp = ld3(sh.a.SP[i]);
-#pragma unroll
-        for (int s = PIH_ARM_PIPE_SPH0; s < PIH_ARM_NSPH; s++) {
-          const V3 d = sp - ld3(sh.a.ASP[s]);
-          const real d2 = dot(d, d), reach = margin + r + ASPH_R[s];      // (depth <= margin: out of reach, out of the running)
-          if (d2 < reach * reach) {
-            const real dist = (real)sqrt(d2), dep = dist - r - ASPH_R[s];
-            if (dep < depth && dist > (real)1e-9) { depth = dep; bs = s; n = ((real)1 / dist) * d; valid = true; }
-          }
-        }
-        if (valid) { p = sp - (r + (real)0.5 * depth) * n; L = ANL + SAMP_LINK[i]; }
+      Cand c = no_cand(); int bs = 0;
+      if (in) c = sample_vs_arm_spheres(ld3(sh.a.SP[i]), [&](int s) { return ld3(sh.a.ASP[s]); }, [&](int s) { return ASPH_R[s]; }, r, margin, bs);
+      int slot = w.alloc(c.valid);
+      if (c.valid && slot < CMAX && (slot - before) < allowed) {
+        const int L = ANL + SAMP_LINK[i];
+        emit(slot, L, ASPH_LINK[bs], 5000 + bs * NSAMP + i, c.p, c.n, c.depth, L_MU[L] * L_MU[ASPH_LINK[bs]]);
       }
-      int slot = w.alloc(valid);
-      if (valid && slot < CMAX && (slot - before) < allowed) emit(slot, L, ASPH_LINK[bs], 5000 + bs * NSAMP + i, p, n, depth, L_MU[L] * L_MU[ASPH_LINK[bs]]);
     });
     int used = w.alloc_count() - before;
     if (used > allowed) { used = allowed; w.alloc_reset(before + allowed); }
     nca += used;
   }
+  w.stamp(20);
   // pipe self collision: capsule segments s < t, non adjacent (253 pairs, enumerated in key order)
   if (P.selfcol) {
     w.par_all(253, [&](int idx, bool in) {
-      bool valid = false; V3 n = mk(0, 0, 0), p = mk(0, 0, 0); real depth = 0; int s = 0, t = 0;
+      Cand c = no_cand(); int s = 0, t = 0;
       if (in) {
-        // idx -> (s,t): row s has (22 - s) entries (t = s+2..23), C(s) = s (45 - s) / 2 pairs come before it: closed form + one
-        // correction step either way instead of a per-lane search loop of up to 22 trips (the whole wave waited for the longest)
-        s = (int)((real)0.5 * ((real)45 - (real)sqrt((real)(2025 - 8 * idx))));
-        if ((s + 1) * (44 - s) / 2 <= idx) s++;
-        if (s * (45 - s) / 2 > idx) s--;
-        t = s + 2 + idx - s * (45 - s) / 2;
-        // vertex v = first sample of segment v (v<24) / last sample (v=24): sample index of vertex v
-        auto vtx = [&](int v) -> V3 { int si = v == 0 ? 0 : (v == 24 ? NSAMP - 1 : 7 + 5 * (v - 1)); return ld3(sh.a.SP[si]); };
-        V3 p1 = vtx(s), q1 = vtx(s + 1), p2 = vtx(t), q2 = vtx(t + 1);
-        V3 dm = (p1 + q1) - (p2 + q2);
-        // broad phase on the segment midpoints, exact for any geometry and margin: two segments closer than 2 r + margin have midpoints
-        // closer than that plus half of each length (dm = 2 x the midpoint difference).  With the fixed 12 cm of before, every pair two
-        // links apart (midpoints 11 cm apart on a straight pipe) went through the closest-point code; now a wave whose pairs are
-        // all out of reach skips it
-        V3 d1 = q1 - p1, d2 = q2 - p2;
-        real a = dot(d1, d1), e = dot(d2, d2);
-        const real reach = (real)sqrt(a) + (real)sqrt(e) + 2 * (2 * r + margin) + (real)1e-4;
-        if (dot(dm, dm) <= reach * reach) {
-          V3 rr = p1 - p2;
-          real f = dot(d2, rr), ss, tt;
-          const real EPS = (real)1e-12;
-          if (a <= EPS && e <= EPS) { ss = tt = 0; }
-          else if (a <= EPS) { ss = 0; tt = clampr(f / e, 0, 1); }
-          else {
-            real c = dot(d1, rr);
-            if (e <= EPS) { tt = 0; ss = clampr(-c / a, 0, 1); }
-            else {
-              real b = dot(d1, d2), den = a * e - b * b;
-              ss = den > EPS ? clampr((b * f - c * e) / den, 0, 1) : (real)0;
-              tt = (b * ss + f) / e;
-              if (tt < 0) { tt = 0; ss = clampr(-c / a, 0, 1); } else if (tt > 1) { tt = 1; ss = clampr((b - c) / a, 0, 1); }
-            }
-          }
-          V3 c1 = p1 + ss * d1, c2 = p2 + tt * d2, d = c1 - c2;
-          real dist = norm(d); depth = dist - 2 * r;
-          if (depth < margin && dist >= (real)1e-9) { n = ((real)1 / dist) * d; p = (real)0.5 * (c1 + c2); valid = true; }
-        }
+        pair_of_index(idx, s, t);
+        auto vtx = [&](int v) -> V3 { return ld3(sh.a.SP[vertex_sample(v)]); };
+        c = segment_pair(vtx(s), vtx(s + 1), vtx(t), vtx(t + 1), r, margin);
       }
-      int slot = w.alloc(valid);
-      if (valid && slot < CMAX) emit(slot, ANL + s, ANL + t, 1000 + s * 24 + t, p, n, depth, L_MU[ANL + s] * L_MU[ANL + t]);
+      int slot = w.alloc(c.valid);
+      if (c.valid && slot < CMAX) emit(slot, ANL + s, ANL + t, 1000 + s * 24 + t, c.p, c.n, c.depth, L_MU[ANL + s] * L_MU[ANL + t]);
     });
   }
+  w.stamp(21);
   int nc = w.alloc_count(); if (nc > CMAX) nc = CMAX;
   sh.nc = nc; sh.nca = nca;
 }

@@ -240,6 +240,218 @@ PIH_HD void link_velocities_scan(Shared& sh, int lane) {
 }
 PIH_HD void link_velocities(Wave& w, Shared& sh) { w.sync(); link_velocities_scan(sh, w.lane()); w.sync(); }
 
+// ------------------------------------------------------------------------------------------------ collision detection
+// GPU form of collide<W> (pih_common.h; the host harness keeps the template): the same tests (sphere_vs_table, sample_vs_tube, ...), the
+// same contacts in the same slots, in three parts instead of nine passes that each fetched their table entries and sample positions anew.
+//   1. Model constants once: lane l holds link, y and vertex flag of its two samples l and l + 64 (lanes >= 59: one), lanes 0..8 those of
+//      their arm sphere -- one batch of independent loads, one wait.  Tables read at compile-time indices (sphere radii in the unrolled
+//      loop, pad boxes, the hole) and the friction of a link picked at run time (link_mu) come from constexpr copies of the pih_model.h
+//      macros: immediates, and a select where a dependent load L_MU[ANL + SAMP_LINK[i]] stood in front of every emit.
+//   2. One walk: the lane computes its samples' positions (stored to LDS for the pair pass; its own consumers start from the pinned
+//      register, a rounded value as the one read back would be) and, per sample, the table, tube, pad 0, pad 1 and arm-sphere
+//      candidates into registers.  The five tests share nothing but the position, so their chains overlap.
+//   3. Slots afterwards, in the order of the template -- ORDER CONTRACT: pass-major, chunk-minor: table, tube, attach ball, weld, arm
+//      spheres vs table, pad 0, pad 1, arm spheres vs pipe, then the 253 pairs in their four chunks.  Every capped pass takes
+//      allowed = CAMAX - nca at its start, emits under slot < CMAX and slot - before < allowed, and on overflow puts the counter back to
+//      before + allowed; nca counts `used` whether or not the slots lie below CMAX.  Every w.alloc (a ballot) is reached by all 64
+//      lanes; a lane whose sample index is >= NSAMP never holds a candidate.
+constexpr double K_LMU[NL] = PIH_LINK_MU;
+constexpr int K_ASPH_LINK[PIH_ARM_NSPH] = PIH_ARM_SPH_LINK;
+constexpr double K_ASPH_R[PIH_ARM_NSPH] = PIH_ARM_SPH_R;
+constexpr double K_FBOX_C[2][3] = PIH_FINGER_BOX_C;
+constexpr double K_FBOX_H[3] = PIH_FINGER_BOX_H;
+constexpr double K_HOLE_POS[3] = PIH_HOLE_POS;
+// L_MU[L0 + k], k = 0 .. N - 1 picked at run time: the value most links share, and one select per link that differs
+template <int L0, int N> PIH_HD real link_mu(int k) {
+  real mu = (real)K_LMU[L0 + N / 2];
+#pragma unroll
+  for (int j = 0; j < N; j++) if (K_LMU[L0 + j] != K_LMU[L0 + N / 2]) mu = k == j ? (real)K_LMU[L0 + j] : mu;
+  return mu;
+}
+PIH_HD real pipe_link_mu(int s) { return link_mu<ANL, ONL>(s); }                  // L_MU[ANL + s]
+PIH_HD void arm_sphere_link(int s, int& link, real& mu) {                          // ASPH_LINK[s], L_MU[ASPH_LINK[s]]
+  link = K_ASPH_LINK[0]; mu = (real)K_LMU[K_ASPH_LINK[0]];
+#pragma unroll
+  for (int j = 1; j < PIH_ARM_NSPH; j++) { link = s == j ? K_ASPH_LINK[j] : link; mu = s == j ? (real)K_LMU[K_ASPH_LINK[j]] : mu; }
+}
+PIH_HD void pin(V3& v) { __asm__ volatile("" : "+v"(v.x), "+v"(v.y), "+v"(v.z)); }
+// Where -ffast-math associates a sum differently once its terms are constants or sit in another block, the contact's last bits move
+// (tests/test_gpu_collision_bits.py).  Two places did, and are written in the association of the nine-pass form:
+//   - arm sphere vs table: depth = c.z + (-TABLE_Z - rs), p.z = c.z - (rs + 0.5 depth), each bracket rounded on its own;
+//   - arm spheres vs pipe: the radii are held as opaque scalar values (arm_sphere_radius), so that reach = (margin + r) + R and
+//     dep = dist + (-r - R) are formed as with the radii loaded from the table.
+PIH_HD Cand arm_sphere_vs_table(V3 c, real rs, real margin) {
+  Cand o;
+  real k = -(real)PIH_TABLE_Z - rs; __asm__ volatile("" : "+v"(k));
+  o.depth = c.z + k; o.valid = o.depth < margin;
+  real t = rs + (real)0.5 * o.depth; __asm__ volatile("" : "+v"(t));
+  o.p = mk(c.x, c.y, c.z - t); o.n = mk(0, 0, 1);
+  return o;
+}
+PIH_HD real arm_sphere_radius(int s) { real v = (real)K_ASPH_R[s]; __asm__ volatile("" : "+s"(v)); return v; }
+PIH_HD void collide(Wave& w, Shared& sh, const Params& P) {
+  const real r = (real)PIH_PIPE_RADIUS, margin = P.margin;
+  const int lane = w.lane();
+  w.stamp(16);
+  // ---- 1. constants
+  bool inr[2]; int sidx[2], slink[2], svert[2]; real sy[2];
+#pragma unroll
+  for (int c = 0; c < 2; c++) {
+    sidx[c] = lane + 64 * c; inr[c] = sidx[c] < NSAMP;
+    const int j = inr[c] ? sidx[c] : NSAMP - 1;
+    slink[c] = SAMP_LINK[j]; sy[c] = SAMP_Y[j]; svert[c] = SAMP_VERTEX[j];
+  }
+  const bool isph = lane < PIH_ARM_NSPH;
+  const int jsph = isph ? lane : 0;
+  const int alink = ASPH_LINK[jsph]; const real arad = ASPH_R[jsph]; const V3 acen = ld3(ASPH_C[jsph]);
+  // ---- 2. sample positions, arm sphere centres
+  w.sync();
+  V3 sp[2];
+#pragma unroll
+  for (int c = 0; c < 2; c++) {
+    sp[c] = sample_point(sh, ANL + slink[c], sy[c]);
+    if (inr[c]) st3(sh.a.SP[sidx[c]], sp[c]);
+    pin(sp[c]);
+  }
+  // arm collision spheres (pih_model.h PIH_ARM_SPH_*, PROVISIONAL stand-ins for the Panda collision meshes of pybullet_data)
+  V3 cw = mk(0, 0, 0);
+  if (P.armcol) {
+    cw = ld3(sh.LO[alink]) + mul(ldm(sh.a.LR[alink]), acen);
+    if (isph) st3(sh.a.ASP[lane], cw);
+    pin(cw);
+  }
+  w.sync();
+  // ... the candidates of both samples
+  const V3 hole = mk((real)K_HOLE_POS[0], (real)K_HOLE_POS[1], (real)K_HOLE_POS[2]);
+  const V3 bh = mk((real)K_FBOX_H[0], (real)K_FBOX_H[1], (real)K_FBOX_H[2]);
+  const real padreach = pad_reach(bh, r, margin);
+  M3 Rf[2]; V3 bc[2];
+#pragma unroll
+  for (int f = 0; f < 2; f++) {
+    Rf[f] = ldm(sh.a.LR[PIH_FINGER_LINK0 + f]);
+    bc[f] = ld3(sh.LO[PIH_FINGER_LINK0 + f]) + mul(Rf[f], mk((real)K_FBOX_C[f][0], (real)K_FBOX_C[f][1], (real)K_FBOX_C[f][2]));
+  }
+  const bool armpipe = (P.armcol & 2) != 0;
+  V3 ac[PIH_ARM_NSPH]; real ar[PIH_ARM_NSPH];
+#pragma unroll
+  for (int s = 0; s < PIH_ARM_NSPH; s++) { ac[s] = armpipe && s >= PIH_ARM_PIPE_SPH0 ? ld3(sh.a.ASP[s]) : mk(0, 0, 0); ar[s] = arm_sphere_radius(s); }
+  Cand ct[2], ch[2], cp[2][2], ca[2]; int bs[2];
+#pragma unroll
+  for (int c = 0; c < 2; c++) {
+    ct[c] = no_cand(); ch[c] = no_cand(); cp[0][c] = no_cand(); cp[1][c] = no_cand(); ca[c] = no_cand(); bs[c] = 0;
+    if (inr[c] && svert[c]) ct[c] = sphere_vs_table(sp[c], r, margin);                       // table plane: vertices only
+    if (inr[c]) ch[c] = sample_vs_tube(sp[c], hole, r, margin);
+    if (inr[c]) cp[0][c] = sample_vs_pad(sp[c], Rf[0], bc[0], bh, padreach, r, margin);
+    if (inr[c]) cp[1][c] = sample_vs_pad(sp[c], Rf[1], bc[1], bh, padreach, r, margin);
+    if (armpipe && inr[c]) ca[c] = sample_vs_arm_spheres(sp[c], [&](int s) { return ac[s]; }, [&](int s) { return ar[s]; }, r, margin, bs[c]);
+  }
+  w.stamp(17);
+  // ---- 3. slots
+  w.alloc_reset(0);
+#pragma unroll
+  for (int c = 0; c < 2; c++) {
+    const int slot = w.alloc(ct[c].valid);
+    if (ct[c].valid && slot < CMAX)
+      emit_contact(sh, slot, ANL + slink[c], -1, vertex_key(slink[c], sy[c]), ct[c].p, ct[c].n, ct[c].depth, pipe_link_mu(slink[c]) * (real)PIH_TABLE_MU);
+  }
+#pragma unroll
+  for (int c = 0; c < 2; c++) {
+    const int slot = w.alloc(ch[c].valid);
+    if (ch[c].valid && slot < CMAX) emit_contact(sh, slot, ANL + slink[c], -1, 100 + sidx[c], ch[c].p, ch[c].n, ch[c].depth, pipe_link_mu(slink[c]) * (real)PIH_HOLE_MU);
+  }
+  // attach ball and weld (scripted mode, FSM states 4..6; mu = -1 / -2 marks their bilateral rows): in front of every capped pass, never dropped
+  int nca = 0;
+  {
+    const bool attached = P.mode == 1 && sh.S[PIH_S_FSM] >= 4 && sh.S[PIH_S_FSM] <= 6;
+    const int before = w.alloc_count();
+    {
+      const bool valid = lane == 0 && attached;
+      const int slot = w.alloc(valid);
+      if (valid && slot < CMAX) { int L; const Cand c = attach_ball_contact(sh, L); emit_contact(sh, slot, L, PIH_EE_PARENT, 2000, c.p, c.n, c.depth, (real)-1); }
+    }
+    {
+      const bool valid = lane == 0 && attached && !P.attachball;
+      const int slot = w.alloc(valid);
+      if (valid && slot < CMAX) { int L; const Cand c = attach_weld_contact(sh, L); emit_contact(sh, slot, L, PIH_EE_PARENT, 2001, c.p, c.n, c.depth, (real)-2); }
+    }
+    nca += w.alloc_count() - before;
+  }
+  // arm spheres vs the table plane (enable_arm_collision bit 0; keys 3000+): they count against the arm-contact cap and come before the
+  // finger contacts, so a finger-vs-pipe contact is what gets dropped first
+  if (P.armcol & 1) {
+    const int before = w.alloc_count();
+    const int allowed = CAMAX - nca;
+    Cand c = no_cand();
+    if (isph) c = arm_sphere_vs_table(cw, arad, margin);
+    const int slot = w.alloc(c.valid);
+    if (c.valid && slot < CMAX && (slot - before) < allowed) {
+      int L; real mu; arm_sphere_link(lane, L, mu);
+      emit_contact(sh, slot, L, -1, 3000 + lane, c.p, c.n, c.depth, mu * (real)PIH_TABLE_MU);
+    }
+    int used = w.alloc_count() - before;
+    if (used > allowed) { used = allowed; w.alloc_reset(before + allowed); }
+    nca += used;
+  }
+  w.stamp(18);
+  // finger pad boxes (arm links 7, 8): arm-involving contacts are capped, the dropped ones are the tail of the pass
+#pragma unroll
+  for (int f = 0; f < 2; f++) {
+    const int LF = PIH_FINGER_LINK0 + f;
+    const int before = w.alloc_count();
+    const int allowed = CAMAX - nca;
+#pragma unroll
+    for (int c = 0; c < 2; c++) {
+      const Cand& k = cp[f][c];
+      const int slot = w.alloc(k.valid);
+      if (k.valid && slot < CMAX && (slot - before) < allowed)
+        emit_contact(sh, slot, ANL + slink[c], LF, 300 + f * NSAMP + sidx[c], k.p, k.n, k.depth, pipe_link_mu(slink[c]) * (real)K_LMU[LF]);
+    }
+    int used = w.alloc_count() - before;
+    if (used > allowed) { used = allowed; w.alloc_reset(before + allowed); }
+    nca += used;
+  }
+  w.stamp(19);
+  // arm spheres vs the pipe (enable_arm_collision bit 1; keys 5000 + sphere * NSAMP + sample): last of the arm-involving contacts, the
+  // first to be dropped at the cap
+  if (armpipe) {
+    const int before = w.alloc_count();
+    const int allowed = CAMAX - nca;
+#pragma unroll
+    for (int c = 0; c < 2; c++) {
+      const int slot = w.alloc(ca[c].valid);
+      if (ca[c].valid && slot < CMAX && (slot - before) < allowed) {
+        int lb; real mub; arm_sphere_link(bs[c], lb, mub);
+        emit_contact(sh, slot, ANL + slink[c], lb, 5000 + bs[c] * NSAMP + sidx[c], ca[c].p, ca[c].n, ca[c].depth, pipe_link_mu(slink[c]) * mub);
+      }
+    }
+    int used = w.alloc_count() - before;
+    if (used > allowed) { used = allowed; w.alloc_reset(before + allowed); }
+    nca += used;
+  }
+  w.stamp(20);
+  // pipe self collision: capsule segments s < t, non adjacent (253 pairs, enumerated in key order), four chunks
+  // (as in the template; it only loses its L_MU loads.  With the four chunks' candidates in front of their slots the generated code was the
+  //  same four divergent blocks one after another, and the bench 0.2 % lower: DESIGN 11)
+  if (P.selfcol) {
+#pragma unroll
+    for (int b = 0; b < 253; b += 64) {
+      const int idx = b + lane;
+      Cand c = no_cand(); int s = 0, t = 0;
+      if (idx < 253) {
+        pair_of_index(idx, s, t);
+        auto vtx = [&](int v) -> V3 { return ld3(sh.a.SP[vertex_sample(v)]); };
+        c = segment_pair(vtx(s), vtx(s + 1), vtx(t), vtx(t + 1), r, margin);
+      }
+      const int slot = w.alloc(c.valid);
+      if (c.valid && slot < CMAX) emit_contact(sh, slot, ANL + s, ANL + t, 1000 + s * 24 + t, c.p, c.n, c.depth, pipe_link_mu(s) * pipe_link_mu(t));
+    }
+  }
+  w.stamp(21);
+  int nc = w.alloc_count(); if (nc > CMAX) nc = CMAX;
+  sh.nc = nc; sh.nca = nca;
+  w.sync();
+}
+
 // ------------------------------------------------------------------------------------------------ ABA inward sweep
 // Inward sweep of the articulated-body algorithm, LANE = ENTRY of the articulated inertia: lane l < 48 owns entry
 // (i, j) = (l >> 3, l & 7) of the 6 x 8 array [ I^A (6 x 6, rows/cols 0-2 angular, 3-5 linear, i.e. [[A, B], [B^T, C]]) |
