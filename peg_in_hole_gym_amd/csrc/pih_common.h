@@ -691,18 +691,36 @@ PIH_HD void pair_of_index(int idx, int& s, int& t) {
 }
 // vertex v = first sample of segment v (v<24) / last sample (v=24): sample index of vertex v
 PIH_HD int vertex_sample(int v) { return v == 0 ? 0 : (v == 24 ? NSAMP - 1 : 7 + 5 * (v - 1)); }
-// capsule segments p1 q1 and p2 q2 of the pipe (radius r each)
-PIH_HD Cand segment_pair(V3 p1, V3 q1, V3 p2, V3 q2, real r, real margin) {
+// capsule segments p1 q1 and p2 q2 of the pipe (radius r each): a broad-phase predicate, the closest-point code, and segment_pair, their
+// composition.
+// Broad phase on the segment midpoints, exact for any geometry and margin: two segments closer than 2 r + margin have midpoints
+// closer than that plus half of each length (dm = 2 x the midpoint difference; a, e = the squared lengths).  With the fixed 12 cm of
+// before, every pair two links apart (midpoints 11 cm apart on a straight pipe) went through the closest-point code; now a wave whose
+// pairs are all out of reach skips it
+PIH_HD bool segment_pair_in_reach(V3 dm, real a, real e, real r, real margin) {
+  const real reach = (real)sqrt(a) + (real)sqrt(e) + 2 * (2 * r + margin) + (real)1e-4;
+  return dot(dm, dm) <= reach * reach;
+}
+// The same predicate from per-segment records, formed once per segment instead of once per pair: m = p + q and len = |q - p|.
+// It may round differently from the per-pair expression (the sums are associated differently, len is rounded before it is added), and
+// that is allowed because the predicate is only a filter: a pair emits a contact only at depth < margin, i.e. with its axes closer
+// than 2 r + margin, and then |m_s - m_t| <= len_s + len_t + 2 (2 r + margin) holds exactly; the threshold here lies above that by
+// 1e-4 m (and the pair's midpoints lie inside it by half of each length unless the closest points are the far ends).  Against
+// thresholds of 0.05 .. 0.3 m that slack is a relative 3e-4 and more, orders of magnitude above the few ulp (6e-8 each) the fp32
+// sums, the square root and the two squares can be off by.  (tests/test_pair_pass.py: every contact of the reference is a survivor.)
+struct SegRec { V3 m; real len; };
+PIH_HD SegRec segment_record(V3 p, V3 q) { SegRec o; const V3 d = q - p; o.m = p + q; o.len = (real)sqrt(dot(d, d)); return o; }
+PIH_HD bool segments_in_reach(V3 ms, real lens, V3 mt, real lent, real r, real margin) {
+  const V3 dm = ms - mt;
+  const real reach = lens + lent + 2 * (2 * r + margin) + (real)1e-4;
+  return dot(dm, dm) <= reach * reach;
+}
+// closest points of the two axes (Ericson's clamp chain) -> the contact, if the capsules are within the margin
+PIH_HD Cand segment_closest(V3 p1, V3 q1, V3 p2, V3 q2, real r, real margin) {
   Cand o = no_cand();
-  V3 dm = (p1 + q1) - (p2 + q2);
-  // broad phase on the segment midpoints, exact for any geometry and margin: two segments closer than 2 r + margin have midpoints
-  // closer than that plus half of each length (dm = 2 x the midpoint difference).  With the fixed 12 cm of before, every pair two
-  // links apart (midpoints 11 cm apart on a straight pipe) went through the closest-point code; now a wave whose pairs are
-  // all out of reach skips it
   V3 d1 = q1 - p1, d2 = q2 - p2;
   real a = dot(d1, d1), e = dot(d2, d2);
-  const real reach = (real)sqrt(a) + (real)sqrt(e) + 2 * (2 * r + margin) + (real)1e-4;
-  if (dot(dm, dm) <= reach * reach) {
+  {
     V3 rr = p1 - p2;
     real f = dot(d2, rr), ss, tt;
     const real EPS = (real)1e-12;
@@ -723,6 +741,11 @@ PIH_HD Cand segment_pair(V3 p1, V3 q1, V3 p2, V3 q2, real r, real margin) {
     if (o.depth < margin && dist >= (real)1e-9) { o.n = ((real)1 / dist) * d; o.p = (real)0.5 * (c1 + c2); o.valid = true; }
   }
   return o;
+}
+PIH_HD Cand segment_pair(V3 p1, V3 q1, V3 p2, V3 q2, real r, real margin) {
+  const V3 dm = (p1 + q1) - (p2 + q2), d1 = q1 - p1, d2 = q2 - p2;
+  if (!segment_pair_in_reach(dm, dot(d1, d1), dot(d2, d2), r, margin)) return no_cand();
+  return segment_closest(p1, q1, p2, q2, r, margin);
 }
 // p7 attach (envs/peg_in_hole.py:99-104), restated as a ball joint between the grasp point of the grasped pipe link
 // (childFramePosition = random_vector) and the grasp-target origin (parentFramePosition = 0): link L, point, normal, distance as depth

@@ -251,7 +251,7 @@ PIH_HD void link_velocities(Wave& w, Shared& sh) { w.sync(); link_velocities_sca
 //      register, a rounded value as the one read back would be) and, per sample, the table, tube, pad 0, pad 1 and arm-sphere
 //      candidates into registers.  The five tests share nothing but the position, so their chains overlap.
 //   3. Slots afterwards, in the order of the template -- ORDER CONTRACT: pass-major, chunk-minor: table, tube, attach ball, weld, arm
-//      spheres vs table, pad 0, pad 1, arm spheres vs pipe, then the 253 pairs in their four chunks.  Every capped pass takes
+//      spheres vs table, pad 0, pad 1, arm spheres vs pipe, then the 253 pairs in key order (one list of the pairs in reach).  Every capped pass takes
 //      allowed = CAMAX - nca at its start, emits under slot < CMAX and slot - before < allowed, and on overflow puts the counter back to
 //      before + allowed; nca counts `used` whether or not the slots lie below CMAX.  Every w.alloc (a ballot) is reached by all 64
 //      lanes; a lane whose sample index is >= NSAMP never holds a candidate.
@@ -289,6 +289,26 @@ PIH_HD Cand arm_sphere_vs_table(V3 c, real rs, real margin) {
   return o;
 }
 PIH_HD real arm_sphere_radius(int s) { real v = (real)K_ASPH_R[s]; __asm__ volatile("" : "+s"(v)); return v; }
+// pair_of_index for idx = lane + 64 k, k a constant after unrolling: row s starts at C(s) = s (45 - s) / 2, and only a few rows start
+// inside a chunk of 64 (3, 3, 5, 10), so s is the rows that start at or before the chunk plus one compare per row that starts inside
+// it: no square root, no corrections.  Lanes past the last pair (chunk 3, lanes 61 ..) get the last pair.
+PIH_HD void pair_of_chunk_lane(int k, int lane, int& s, int& t) {
+  const int lo = 64 * k, idx = k < 3 ? lo + lane : (lane < 253 - 192 ? lo + lane : 252);
+  s = 0;
+#pragma unroll
+  for (int j = 1; j < 22; j++) {
+    const int cj = j * (45 - j) / 2;
+    if (cj <= lo) s++;
+    else if (cj <= lo + 63) s += idx >= cj;
+  }
+  t = s + 2 + idx - s * (45 - s) / 2;
+}
+// vertex_sample without its two branches: 7 + 5 (v - 1) is NSAMP - 1 at v = 24 by itself, only vertex 0 is apart (the narrow rounds call
+// it at four run-time indices per lane; as written in pih_common.h each call became two divergent blocks)
+static_assert(7 + 5 * (24 - 1) == NSAMP - 1, "the last vertex is the last sample");
+PIH_HD int vertex_sample_flat(int v) { return 5 * v + (v == 0 ? 0 : 2); }
+constexpr int PAIR_REC_WORDS = 4 * 24;                     // the pair pass's per-segment records, then its survivor list, in sh.a.IAP
+static_assert(PAIR_REC_WORDS + 253 <= NL * 28 && PAIR_REC_WORDS % 4 == 0, "records and list of the pair pass alias ArenaA::IAP");
 PIH_HD void collide(Wave& w, Shared& sh, const Params& P) {
   const real r = (real)PIH_PIPE_RADIUS, margin = P.margin;
   const int lane = w.lane();
@@ -429,19 +449,55 @@ PIH_HD void collide(Wave& w, Shared& sh, const Params& P) {
     nca += used;
   }
   w.stamp(20);
-  // pipe self collision: capsule segments s < t, non adjacent (253 pairs, enumerated in key order), four chunks
-  // (as in the template; it only loses its L_MU loads.  With the four chunks' candidates in front of their slots the generated code was the
-  //  same four divergent blocks one after another, and the bench 0.2 % lower: DESIGN 11)
+  // pipe self collision: capsule segments s < t, non adjacent (253 pairs, enumerated in key order).  The template filters every pair by
+  // itself (four vertices, two square roots per pair, chunk after chunk); in the benchmark's steady state 70 % of the envs have NO pair
+  // in reach and the rest a handful, so here the filter runs from 24 per-segment records, branch-free for all four chunks at once, and
+  // the closest-point code runs over ONE compacted list of the survivors, 64 at a time: no round without a survivor.
+  //   - records (lanes 0 .. 23): m = p + q, len = |q - p| of the lane's segment, from the vertex samples stored above
+  //   - broad phase: lane l holds the pairs l, l + 64, l + 128, l + 192; eight 16-byte record reads in one batch, four predicates
+  //     (segments_in_reach: a filter that may round differently from the template's, see there)
+  //   - list: four ballots; the prefix popcounts put every survivor at its position in pair-index order -- which is key order, so the
+  //     slots handed out below are the template's (ORDER CONTRACT).  An entry is s * 32 + t.
+  //   - narrow rounds: lane l takes entry j0 + l, segment_closest (the template's arithmetic), then w.alloc and emit_contact as ever:
+  //     a pair emits under slot < CMAX, the counter counts on beyond CMAX.
+  // Records and list live in the first 96 + 253 words of sh.a.IAP, which nothing reads or writes between the end of the last step and
+  // aba()'s own-inertia pass (pih_step.h), after collide.  The ballots and w.alloc are reached by all 64 lanes: the round count is
+  // wave-uniform.
   if (P.selfcol) {
+    real4* const rec = reinterpret_cast<real4*>(&sh.a.IAP[0][0]);
+    int* const list = reinterpret_cast<int*>(&sh.a.IAP[0][0] + PAIR_REC_WORDS);
+    if (lane < 24) {
+      const SegRec g = segment_record(ld3(sh.a.SP[vertex_sample(lane)]), ld3(sh.a.SP[vertex_sample(lane + 1)]));
+      real4 o; o.x = g.m.x; o.y = g.m.y; o.z = g.m.z; o.w = g.len;
+      rec[lane] = o;
+    }
+    int ps[4], pt[4];
 #pragma unroll
-    for (int b = 0; b < 253; b += 64) {
-      const int idx = b + lane;
-      Cand c = no_cand(); int s = 0, t = 0;
-      if (idx < 253) {
-        pair_of_index(idx, s, t);
-        auto vtx = [&](int v) -> V3 { return ld3(sh.a.SP[vertex_sample(v)]); };
-        c = segment_pair(vtx(s), vtx(s + 1), vtx(t), vtx(t + 1), r, margin);
-      }
+    for (int k = 0; k < 4; k++) pair_of_chunk_lane(k, lane, ps[k], pt[k]);
+    w.sync();
+    real4 rs[4], rt[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) { rs[k] = rec[ps[k]]; rt[k] = rec[pt[k]]; }
+    unsigned long long hit[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+      const bool in = segments_in_reach(mk(rs[k].x, rs[k].y, rs[k].z), rs[k].w, mk(rt[k].x, rt[k].y, rt[k].z), rt[k].w, r, margin);
+      hit[k] = __ballot(k < 3 ? in : in & (lane < 253 - 192));                          // (no &&: the four predicates stay one block)
+    }
+    int nsurv = 0;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+      if ((hit[k] >> lane) & 1) list[nsurv + __popcll(hit[k] & ((1ull << lane) - 1ull))] = ps[k] * 32 + pt[k];
+      nsurv += __popcll(hit[k]);
+    }
+    w.sync();
+    for (int j0 = 0; j0 < nsurv; j0 += 64) {
+      const bool has = j0 + lane < nsurv;
+      const int e = has ? list[j0 + lane] : 2;                 // (an idle lane reads the vertices of the pair (0, 2) and keeps no candidate)
+      const int s = e >> 5, t = e & 31;
+      auto vtx = [&](int v) -> V3 { return ld3(sh.a.SP[vertex_sample_flat(v)]); };
+      Cand c = segment_closest(vtx(s), vtx(s + 1), vtx(t), vtx(t + 1), r, margin);
+      c.valid = c.valid && has;
       const int slot = w.alloc(c.valid);
       if (c.valid && slot < CMAX) emit_contact(sh, slot, ANL + s, ANL + t, 1000 + s * 24 + t, c.p, c.n, c.depth, pipe_link_mu(s) * pipe_link_mu(t));
     }
