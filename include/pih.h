@@ -293,5 +293,8 @@ const char* pih_last_error(pih_handle* h);
  * pih_closest_points, declared in pih_robot.h.  Defined here for the same reason */
 #define PIH_POINT_WORDS 4
 #define PIH_CLOSEST_WORDS 8
+/* words of a probe's record of pih_robot_clearance, declared in pih_robot.h (signed distance, obstacle seg, point on the probe xyz, point on
+ * the obstacle xyz, unit normal on the obstacle xyz, probe seg).  Defined here for the same reason */
+#define PIH_CLEAR_WORDS 12
 #include "pih_robot.h"
 #endif

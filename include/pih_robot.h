@@ -9,6 +9,8 @@
  *   pih_robot_inverse_dynamics         p.calculateInverseDynamics(body, q, qd, qdd)  -- see the damping note below
  *   pih_ray_test                       p.rayTestBatch(from, to, parentObjectUniqueId, parentLinkIndex)  -- the scene query, at the end
  *   pih_closest_points                 p.getClosestPoints(bodyA, bodyB, distance) for a point against the scene  -- after it
+ *   pih_robot_clearance                p.resetJointState(robot, q) + p.getClosestPoints(robot, body, distance, linkIndexA) per link, for
+ *                                      many joint configurations per env  -- the last one
  *
  * Conventions: n problems, independent of the handle's env count (as pih_ik); both robots work on a handle of either task (as pih_ik /
  * pih_ik_ur5).  Every pointer is a DEVICE pointer to float32, row-major, contiguous.  Nothing synchronises: the work is enqueued on the
@@ -132,6 +134,50 @@ int pih_ray_test(pih_handle* h, float* out_dev, const float* rays_dev, int rays_
 #define PIH_GROUP_ALL     31
 int pih_closest_points(pih_handle* h, float* out_dev, const float* points_dev, int points_per_env,
                        int groups, int env_begin, int env_count, int flags, void* stream);
+
+/* Robot clearance for many joint configurations: the body-to-body form of p.getClosestPoints.  For each of configs_per_env joint
+ * configurations q per env, how far every link of the handle's task's robot -- the Panda on peg-in-hole, the UR5 on random-fly -- placed
+ * at q is from the pipe / the flying object and the table AT THE ENV'S CURRENT STATE, and where the two closest points are.
+ *   q_dev     float[env_count, configs_per_env, ndof], or with PIH_RAY_SHARED float[configs_per_env, ndof]; ndof as pih_robot_dims reports
+ *             it (Panda 9: the two finger words are read and checked but move no probe; UR5 6).  Rows need only float alignment.
+ *             NULL, allowed only with configs_per_env == 1: every env is measured at its own current joint state --
+ *             p.getClosestPoints(robot, body, distance) as PyBullet answers it
+ *   probes    the round primitives the task's free camera draws for the arm and pih_closest_points measures as PIH_GROUP_ARM, placed by
+ *             the forward kinematics of pih_robot_fk at q.  Panda, PIH_CLEAR_PROBES_PANDA = 11: the capsules of links 0 .. 6 (from the
+ *             parent's origin to the link's), then the four hand spheres (seg 6).  UR5, PIH_CLEAR_PROBES_UR5 = 6: the link capsules.
+ *             A sphere is a capsule of zero length
+ *   groups    PIH_GROUP_OBJECT (peg-in-hole: the 24 pipe capsules; random-fly: the object's spheres) and / or PIH_GROUP_TABLE (the half
+ *             space below z = PIH_TABLE_Z)
+ *   reach     [m] > 0, the `distance` argument of p.getClosestPoints: only what is nearer than reach is reported
+ * out_dev float[env_count, configs_per_env, probes, PIH_CLEAR_WORDS], 16-byte aligned, per probe:
+ *   word 0       the signed distance between the two surfaces, negative for an overlap.  Exact: capsule - capsule the distance of the two
+ *                axis segments minus both radii, capsule - sphere the point - segment distance minus both radii, capsule - table
+ *                z - r - PIH_TABLE_Z of the lower end point
+ *   word 1       the nearest obstacle primitive's segmentation value as a float, the values pih_ray_test reports
+ *   words 2..4   the closest point on the probe's surface, words 5..7 the closest point on the obstacle's surface, env-local
+ *   words 8..10  the unit normal on the obstacle, towards the probe (contactNormalOnB):
+ *                point on probe = point on obstacle + distance x normal, for overlapping and separated pairs alike
+ *   word 11      the probe's own segmentation value (its link), always
+ *   miss         nothing selected is nearer than reach: reach, PIH_SEG_NONE, the probe's first axis end point in both point slots, normal 0
+ * Where the closest pair is not unique (parallel axes, a horizontal capsule over the table, intersecting axes) one closest pair is reported
+ * with a finite unit normal; where the axes touch, the normal is a perpendicular of both.  The obstacles are walked in the order table,
+ * then the object's primitives by index, and a later one replaces the running nearest only if it is strictly nearer.
+ * A configuration with a word that is NaN, infinite or beyond 1e15 gets the miss record with the point words 0 for all its probes; no
+ * other configuration is affected, and no table is indexed by anything derived from q.
+ * Not measured: the finger-pad boxes as probes (box - capsule has no short exact form); PIH_GROUP_HOLE (the capsule - tube
+ * distance is a quartic, and the step never collides the arm with the hole fixture: pih_closest_points on chosen points measures against
+ * the hole); the arm against itself (it needs an allowed-pair table); a GRASPED pipe stays where the env's state has it and does not move
+ * with q -- callers who plan with the pipe in hand leave PIH_GROUP_OBJECT out.
+ * Errors: -2, and pih_last_error names the argument: a NULL handle (pih_last_error(NULL)) or out_dev, q_dev == NULL with
+ * configs_per_env != 1, configs_per_env < 1 or > 2^20, reach not finite or <= 0, env_begin / env_count outside the handle's envs or
+ * env_count > 65535, a flag bit other than PIH_RAY_SHARED, a groups bit outside PIH_GROUP_OBJECT | PIH_GROUP_TABLE or a mask that selects
+ * nothing, out_dev not 16-byte aligned.  Nothing synchronises. */
+/* (PIH_CLEAR_WORDS = 12 is defined in pih.h, beside PIH_CLOSEST_WORDS) */
+#define PIH_CLEAR_PROBES_PANDA 11   /* arm capsules of links 0..6, then the 4 hand spheres (seg 6) */
+#define PIH_CLEAR_PROBES_UR5   6    /* the six link capsules */
+int pih_robot_clearance_probes(int task_id);   /* 11 / 6, < 0 for an unknown task */
+int pih_robot_clearance(pih_handle* h, float* out_dev, const float* q_dev, int configs_per_env, float reach,
+                        int groups, int env_begin, int env_count, int flags, void* stream);
 #ifdef __cplusplus
 }
 #endif

@@ -32,6 +32,10 @@ RAY_WORDS, RAY_HIT_WORDS = 6, 8
 # batched closest-point queries (pih_closest_points): a query is x, y, z, reach; a record is signed distance, seg, closest point xyz, normal xyz
 POINT_WORDS, CLOSEST_WORDS = 4, 8
 GROUP_ARM, GROUP_FINGERS, GROUP_OBJECT, GROUP_HOLE, GROUP_TABLE, GROUP_ALL = 1, 2, 4, 8, 16, 31    # PIH_GROUP_*: what a point is measured against
+# robot clearance for many joint configurations (pih_robot_clearance): a record per probe is signed distance, obstacle seg, point on the probe xyz,
+# point on the obstacle xyz, unit normal on the obstacle xyz, probe seg; the probes are 7 arm capsules + 4 hand spheres (Panda), 6 capsules (UR5)
+CLEAR_WORDS, CLEAR_PROBES_PANDA, CLEAR_PROBES_UR5 = 12, 11, 6
+CLEAR_GROUPS = GROUP_OBJECT | GROUP_TABLE          # what pih_robot_clearance measures against
 GROUPS = {"arm": GROUP_ARM, "fingers": GROUP_FINGERS, "object": GROUP_OBJECT, "hole": GROUP_HOLE, "table": GROUP_TABLE}
 RAY_FRAME_EE, RAY_SHARED, RAY_IGNORE_ROBOT = 1, 2, 4    # PIH_RAY_*: rays in the end-effector frame | one ray set for all envs | the arm is transparent
 FIELD_STATE, FIELD_TIP_POSE, FIELD_CONTACT_FORCE, FIELD_DEBUG, FIELD_EE_POS = 0, 1, 2, 3, 4
@@ -53,7 +57,7 @@ EXPORTS = ["pih_default_config", "pih_abi_version", "pih_task_dims", "pih_object
            "pih_get_state", "pih_set_state", "pih_ik", "pih_ik_ur5", "pih_render", "pih_render_ex", "pih_render_cam", "pih_grasp_labels", "pih_timing", "pih_timing2", "pih_set_timing", "pih_last_error"]
 LIGHT_EXPORTS = ["pih_render_lit"]      # what include/pih_render_light.h declares (tests/test_render_lit.py compares it with that header)
 ROBOT_EXPORTS = ["pih_robot_dims", "pih_link_states_frames", "pih_robot_fk", "pih_robot_jacobian", "pih_robot_mass_matrix", "pih_robot_inverse_dynamics",
-                 "pih_link_states", "pih_ray_test", "pih_closest_points"]      # what include/pih_robot.h declares (tests/test_robot_query.py compares it with that header)
+                 "pih_link_states", "pih_ray_test", "pih_closest_points", "pih_robot_clearance_probes", "pih_robot_clearance"]      # what include/pih_robot.h declares (tests/test_robot_query.py compares it with that header)
 VIEW_EXPORTS = ["pih_render_view"]      # what include/pih_render_view.h declares on top of that (tests/test_peg_view.py compares it with that header)
 
 
@@ -116,6 +120,8 @@ def load():
     L.pih_robot_inverse_dynamics.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, vp, vp]
     L.pih_link_states.argtypes = [vp, vp, C.c_int, C.c_int, vp]
     L.pih_closest_points.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]      # (h, out, points, points_per_env, groups, env_begin, env_count, flags, stream)
+    L.pih_robot_clearance_probes.argtypes = [C.c_int]
+    L.pih_robot_clearance.argtypes = [vp, vp, vp, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, vp]      # (h, out, q or None, configs_per_env, reach, groups, env_begin, env_count, flags, stream)
     L.pih_ray_test.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]        # (h, out, rays, rays_per_env, env_begin, env_count, flags, stream)
     L.pih_grasp_labels.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp]
     L.pih_reseed.argtypes = [vp, C.c_uint64]
@@ -149,6 +155,14 @@ def robot_dims(robot):
 def link_states_frames(task_id):
     """frames per env of PihVecEnv.link_states for a task (peg-in-hole: 10 Panda frames + 24 pipe links; random-fly: 7 UR5 frames + the object)"""
     k = load().pih_link_states_frames(int(task_id))
+    if k < 0:
+        raise PihError("unknown task_id %r" % (task_id,))
+    return k
+
+
+def clearance_probes(task_id):
+    """probes per configuration of PihVecEnv.robot_clearance for a task (peg-in-hole: 11, random-fly: 6)"""
+    k = load().pih_robot_clearance_probes(int(task_id))
     if k < 0:
         raise PihError("unknown task_id %r" % (task_id,))
     return k

@@ -6,7 +6,7 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 # One translation unit each, linked into one library: the C ABI first, then the kernels.  (Every csrc/*.hip: tests/test_sources.py.)
-SRCS = [os.path.join(HERE, f) for f in ("pih_hip.hip", "pih_peg.hip", "pih_fly.hip", "pih_fly_image.hip", "pih_view.hip", "pih_lit.hip", "pih_robot.hip", "pih_rays.hip", "pih_dist.hip")]
+SRCS = [os.path.join(HERE, f) for f in ("pih_hip.hip", "pih_peg.hip", "pih_fly.hip", "pih_fly_image.hip", "pih_view.hip", "pih_lit.hip", "pih_robot.hip", "pih_rays.hip", "pih_dist.hip", "pih_clear.hip")]
 SRC = SRCS[0]
 OUT = os.path.join(HERE, "libpih_hip.so")
 DEPS = SRCS + glob.glob(os.path.join(HERE, "*.h")) + glob.glob(os.path.join(HERE, "..", "..", "include", "*.h"))

@@ -677,6 +677,31 @@ int pih_closest_points(pih_handle* h, float* out_dev, const float* points_dev, i
   return 0;
 }
 
+// ---- robot clearance for many joint configurations (include/pih_robot.h; kernels in pih_clear.hip)
+int pih_robot_clearance_probes(int task_id) { return robot_clearance_probes(task_id); }
+int pih_robot_clearance(pih_handle* h, float* out_dev, const float* q_dev, int configs_per_env, float reach, int groups, int env_begin, int env_count, int flags, void* stream) {
+  if (!h) return robot_bad(h, "pih_robot_clearance", "h", "is NULL");
+  if (!out_dev) return robot_bad(h, "pih_robot_clearance", "out_dev", "is NULL");
+  if (configs_per_env < 1) return robot_bad(h, "pih_robot_clearance", "configs_per_env", "is smaller than 1");
+  if (configs_per_env > (1 << 20)) return robot_bad(h, "pih_robot_clearance", "configs_per_env", "is larger than 2^20");
+  if (!q_dev && configs_per_env != 1) return robot_bad(h, "pih_robot_clearance", "q_dev", "is NULL with configs_per_env != 1 (NULL = each env's current joint state)");
+  unsigned reach_bits; memcpy(&reach_bits, &reach, sizeof reach_bits);      // (the library is built with -ffast-math: the exponent says it)
+  if ((reach_bits & 0x7f800000u) == 0x7f800000u || (reach_bits >> 31) != 0 || (reach_bits & 0x7fffffffu) == 0)
+    return robot_bad(h, "pih_robot_clearance", "reach", "is not finite or not larger than 0");
+  if (env_begin < 0 || env_count <= 0 || env_begin > h->cfg.n_envs || env_count > h->cfg.n_envs - env_begin)
+    return robot_bad(h, "pih_robot_clearance", "env_begin / env_count", "is outside the handle's envs");
+  if (env_count > 65535) return robot_bad(h, "pih_robot_clearance", "env_count", "is larger than 65535 per call");
+  if ((flags & ~PIH_RAY_SHARED) != 0) return robot_bad(h, "pih_robot_clearance", "flags", "has an unknown bit (only PIH_RAY_SHARED is known)");
+  if ((groups & ~(PIH_GROUP_OBJECT | PIH_GROUP_TABLE)) != 0)
+    return robot_bad(h, "pih_robot_clearance", "groups", "has a bit outside PIH_GROUP_OBJECT | PIH_GROUP_TABLE (fingers, hole and the arm itself are not measured)");
+  if (groups == 0) return robot_bad(h, "pih_robot_clearance", "groups", "selects nothing");
+  if ((reinterpret_cast<uintptr_t>(out_dev) & 15) != 0) return robot_bad(h, "pih_robot_clearance", "out_dev", "must be 16-byte aligned");
+  PIH_ENTER(h);
+  robot_clearance_launch(h->fly, (hipStream_t)stream, h->state, out_dev, q_dev, configs_per_env, reach, groups, h->cfg.n_envs, h->P.object, env_begin, env_count, flags);
+  HIPCHK(h, hipGetLastError());
+  return 0;
+}
+
 const char* pih_last_error(pih_handle* h) { return h ? h->err.c_str() : g_err.c_str(); }
 
 }  // extern "C"

@@ -66,4 +66,8 @@ void ray_test_launch(bool fly_task, hipStream_t stream, const float* state, floa
 // ---- pih_dist.hip: the batched closest-point queries of include/pih_robot.h
 void closest_points_launch(bool fly_task, hipStream_t stream, const float* state, float* out, const float* points, int points_per_env,
                            int groups, int n_envs, int object, int env_begin, int env_count, int flags);
+// ---- pih_clear.hip: the robot clearance queries of include/pih_robot.h (q = nullptr: each env's own joint state)
+void robot_clearance_launch(bool fly_task, hipStream_t stream, const float* state, float* out, const float* q, int configs_per_env, float reach,
+                            int groups, int n_envs, int object, int env_begin, int env_count, int flags);
+int robot_clearance_probes(int task_id);
 }  // namespace pih

@@ -135,6 +135,12 @@ class PegInHole(MetaEnv):
         [envs, points, 8] tensor"""
         return self._backend.closest_points(points, **kw)
 
+    def robot_clearance(self, q=None, **kw):
+        """getClosestPoints(panda, body, distance, linkIndexA) of the Panda's 7 link capsules and 4 hand spheres placed at joint values q
+        (None: the current ones) against the pipe ("object") and the table at the current state (PihVecEnv.robot_clearance: reach, groups,
+        env_begin, env_count, out) -> the backend's [envs, configurations, 11, 12] tensor"""
+        return self._backend.robot_clearance(q, **kw)
+
 
 class RandomFly(MetaEnv):
     """'random-fly' (README.md:38: task='random-fly', args=['Banana', 1/120.]): the UR5 of assets/urdf/ur5.urdf driven by
@@ -186,3 +192,9 @@ class RandomFly(MetaEnv):
         """getClosestPoints of points against the scene of render(camera=...) -- groups "arm" (the UR5), "object", "table" -- at the
         current state (PihVecEnv.closest_points: reach, frame, groups, env_begin, env_count, out) -> the backend's [envs, points, 8] tensor"""
         return self._backend.closest_points(points, **kw)
+
+    def robot_clearance(self, q=None, **kw):
+        """getClosestPoints(ur5, body, distance, linkIndexA) of the UR5's 6 link capsules placed at joint values q (None: the current
+        ones) against the flying object and the table at the current state (PihVecEnv.robot_clearance: reach, groups, env_begin,
+        env_count, out) -> the backend's [envs, configurations, 6, 12] tensor"""
+        return self._backend.robot_clearance(q, **kw)

@@ -399,6 +399,52 @@ class PihVecEnv:
                       "pih_closest_points")
         return out
 
+    def robot_clearance(self, q=None, reach=1.0, groups=("object", "table"), env_begin=0, env_count=None, out=None):
+        """getClosestPoints(robot, body, distance, linkIndexA) for every link of the task's robot placed at joint values q, against the
+        pipe / the flying object and the table at the envs' CURRENT state (pih_robot_clearance, include/pih_robot.h).
+        q: [C, ndof], the same C configurations for every env of the call, or [count, C, ndof], one set per env; ndof = 9 (Panda: the two
+            finger words move no probe) or 6 (UR5).  None: every env at its own current joint state (C = 1).
+        reach [m] > 0: only what is nearer is reported.
+        groups: "object" and / or "table" (names of _lib.GROUPS or a mask of _lib.GROUP_*).  The hole, the fingers and the arm itself are
+            not measured: any other group is an error, as is a mask that selects nothing.
+        -> float32 [count, C, NP, 12] on the device, NP = 11 probes (Panda: the capsules of links 0 .. 6, the four hand spheres) or 6 (UR5),
+        per probe: signed distance of the two surfaces (negative = overlap), the nearest obstacle's seg value, the closest point on the
+        probe xyz, the closest point on the obstacle xyz, the unit normal on the obstacle towards the probe xyz (point on probe = point on
+        obstacle + distance x normal), the probe's own seg (its link).  Nothing within reach: reach, _lib.SEG_NONE, the probe's first axis
+        end point twice, normal 0.  A configuration with a NaN / Inf word reports that with the points 0 for all its probes; the others of
+        the call are not affected.  out: a contiguous float32 tensor of that shape on this handle's device (ValueError otherwise)."""
+        count = self.n - env_begin if env_count is None else env_count
+        if isinstance(groups, str):
+            groups = (groups,)
+        if not isinstance(groups, int):
+            unknown = [g for g in groups if g not in _lib.GROUPS]
+            if unknown:
+                raise ValueError("robot_clearance: groups must be names of %s, got %r" % (sorted(_lib.GROUPS), unknown))
+            mask = 0
+            for g in groups:
+                mask |= _lib.GROUPS[g]
+            groups = mask
+        fly = self.task_id == _lib.TASK_RANDOM_FLY
+        ndof = _lib.robot_dims(_lib.ROBOT_UR5 if fly else _lib.ROBOT_PANDA)[0]
+        if q is not None:
+            q = torch.as_tensor(q).to(device=self.device, dtype=torch.float32)
+            if q.ndim not in (2, 3) or q.shape[-1] != ndof or q.shape[-2] < 1 or (q.ndim == 3 and q.shape[0] != count):
+                raise ValueError("robot_clearance: q must have shape [C, %d] (shared) or [%d, C, %d] (one set per env of the call) with C >= 1, got %s"
+                                 % (ndof, count, ndof, tuple(q.shape)))
+            q = q.contiguous()
+        Cn = 1 if q is None else q.shape[-2]
+        shape = (count, Cn, _lib.clearance_probes(self.task_id), _lib.CLEAR_WORDS)
+        if out is None:
+            out = torch.empty(shape, device=self.device)
+        elif not (torch.is_tensor(out) and out.dtype == torch.float32 and tuple(out.shape) == shape and self._here(out) and out.is_contiguous()):
+            raise ValueError("robot_clearance: out must be a contiguous float32 tensor of shape %s on %s" % (shape, self.device))
+        flags = _lib.RAY_SHARED if q is not None and q.ndim == 2 else 0
+        self._clear_keep = q                   # (a converted copy lives until the next call: the launch is asynchronous)
+        with torch.cuda.device(self.device):
+            self._chk(self.L.pih_robot_clearance(self.h, out.data_ptr(), None if q is None else q.data_ptr(), int(Cn), float(reach), int(groups),
+                                                 int(env_begin), int(count), flags, self._stream()), "pih_robot_clearance")
+        return out
+
     def ray_fan(self, origin, axis, half_angle_deg, rings, per_ring, length):
         """float32 [1 + rings * per_ring, 6] device tensor: a cone of rays from `origin` about `axis` (module function ray_fan), for
         ray_test -- with frame="ee" a proximity sensor that rides on the hand.  Built on the device, no host round trip."""
